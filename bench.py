@@ -10,13 +10,17 @@ VALU-bound blend; every frame is still rendered in full and bit-identically);
 `serial_ms_per_frame` reports one frame at a time.  With --gpus N (one process per GPU,
 launched by torch.distributed.run) the frame's 16-px tile rows are split into N strips, every
 rank renders its strip and rank 0 gathers the frame over RCCL (strong scaling: the frame is
-fixed, N grows).  The untimed diagnostic passes (serial frame time, stage breakdown, in-flight
-blend events) run before the W warmup frames, so the K timed frames measure a device that has
-been rendering, as a viewer's does.
+fixed, N grows).  258 untimed settling frames (194 serial, 64 in flight) run before the W warmup
+frames, so the K timed frames measure a device that has been rendering, as a viewer's does.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the blend) on the roof
-that bounds it, VALU: its instructions per launch (a committed rocprofv3 SQ profile of this
-build) over its launch duration from HIP events of a serial pass, with the HBM roof from the
+Prints ONE JSON line on rank 0.  A plain run sets up, settles, warms up, times the K frames and
+prints the headline (`value`, `ms_per_step`, the configuration).  --dump-outputs DIR then writes
+what the last timed frame returned to its caller as DIR/<name>.npy.  --full adds the diagnostics,
+which take measurements of their own: the settling frames become the instrumented passes (serial
+frame time, stage breakdown, in-flight blend events), and after the timed frames come the frame
+statistics, `roofline` and `cpu_baseline`.  `roofline` is for the dominant kernel (the blend) on
+the roof that bounds it, VALU: its instructions per launch (a committed rocprofv3 SQ profile of
+this build) over its launch duration from HIP events of a serial pass, with the HBM roof from the
 committed FETCH/WRITE counters beside it; `cpu_baseline` times, on rank 0 at N = 1, the
 reference's own CPU sort path (renderer_ogl.py:10-19, restated and pinned in oracle/) and the
 CPU oracle of the whole forward (oracle/, a C port, OpenMP over the host cores).
@@ -78,7 +82,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report the diagnostics: serial frame time, stage "
+                         "breakdown, in-flight blend events, frame statistics, roofline and the "
+                         "CPU baselines (a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames, write what the last timed frame returned to its "
+                         "caller as DIR/<name>.npy (float32 / float64, at most 64 MB in all: a "
+                         "fixed seeded sample of an array that does not fit)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
     ap.add_argument("--sim-strip", default=None, metavar="R/N",
                     help="diagnostic, 1 GPU: render only strip R of an N-way partition (no "
                          "gather) to estimate one rank's share of an N-GPU frame")
@@ -102,7 +115,8 @@ def parse():
                     help="GSR_OPT_SECOND_STREAM of the in-flight frames (default: FramePipeline's "
                          "choice -- off at depth >= 3 without frame graphs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="CPU-oracle time to sample for cpu_baseline (whole frames; at least one)")
+                    help="with --full: CPU-oracle time to sample for cpu_baseline (whole frames; "
+                         "at least one)")
     return ap.parse_args()
 
 
@@ -365,8 +379,39 @@ def cpu_baseline(scene, seconds):
                      "affinity_cpus": len(os.sched_getaffinity(0)), "thread_env": env}}
 
 
+DUMP_BUDGET = 64_000_000  # bytes --dump-outputs may write in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` (name -> numpy array) as out_dir/<name>.npy, floats as they are (float32 /
+    float64) and integers as floats, within DUMP_BUDGET bytes in all: smallest first, each
+    whole while it fits an equal share of what is left; of an array that does not, the elements
+    at a sorted sample of flat indices drawn without replacement from
+    numpy.random.default_rng(DUMP_SEED) -- the same elements in every run of the same shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    todo = []
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):  # float32 where it holds every value exactly
+            a = a.astype(np.float32 if a.size and np.abs(a).max() < 2 ** 24 else np.float64)
+        todo.append((name, a))
+    todo.sort(key=lambda t: t[1].nbytes)
+    left = DUMP_BUDGET - 1024 * len(todo)  # the .npy headers
+    for n, (name, a) in enumerate(todo):
+        share = left // (len(todo) - n)
+        if a.nbytes > share:
+            keep = np.random.default_rng(DUMP_SEED).choice(a.size, share // a.itemsize,
+                                                           replace=False)
+            keep.sort()
+            a = a.reshape(-1)[keep]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
+    full = args.full
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -426,7 +471,9 @@ def main():
         gather.finish()
         torch.cuda.synchronize()
 
-    def step(i):
+    last = {}  # step(i, keep=True): what the frame returned to its caller (--dump-outputs)
+
+    def step(i, keep=False):
         with pipe.frame() as slot:
             if gather is not None:
                 if len(gather.pending) == len(gather.slots) - 1:
@@ -439,17 +486,25 @@ def main():
                     # strip skip the per-Gaussian work (gsr.h gsr_outputs.radii)
                     res = scene.render(i, mine, slot, out_color=buf, radii=False)
                     K = res.num_rendered
+                    if keep:
+                        last["num_rendered"] = K
                     row_pairs = tile_row_pairs(mine[1] - mine[0], local, slot)
                 else:  # more GPUs than tile rows: nothing to render
                     K, row_pairs = 0, torch.zeros((0,), dtype=torch.int32, device=dev)
                 gather.submit(buf, layout)
                 balancer.observe(i, row_pairs)
                 return K
-            return scene.render(i, rows, slot, radii=rows is None).num_rendered
+            res = scene.render(i, rows, slot, radii=rows is None)
+            if keep:
+                last.update(num_rendered=res.num_rendered, color=res.color, radii=res.radii)
+            return res.num_rendered
 
     def drain():
+        """Finish the pending gathers; rank 0 gets the last gathered frame."""
+        frame = None
         while gather is not None and gather.pending:
-            gather.finish()
+            frame = gather.finish()
+        return frame
 
     lib = _lib.load_library()
     ctxs = [_lib.context(local, slot) for slot in range(args.inflight)]
@@ -476,7 +531,8 @@ def main():
         """(2) Serial frame rate: one frame in flight (slot 0, the caller's stream, no gather,
         the second stream on: a lone frame overlaps its own two halves) -- the frame time of a
         viewer that renders each frame before starting the next; (3) the per-stage breakdown
-        (events at every stage boundary) of 30 more such forwards."""
+        (events at every stage boundary) of 30 more such forwards.  A plain run renders the same
+        130 frames as settling frames and measures neither."""
         _lib.check(lib.gsr_set_option(ctx, _lib.GSR_OPT_FRAME_GRAPHS, graphs_serial),
                    "gsr_set_option")
         _lib.check(lib.gsr_set_option(ctx, _lib.GSR_OPT_SECOND_STREAM, 1), "gsr_set_option")
@@ -487,17 +543,21 @@ def main():
             scene.render(i, rows, radii=rows is None)
         torch.cuda.synchronize()
         ms = 1e3 * (time.perf_counter() - t1) / n_serial
-        _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
+        if full:
+            _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
         torch.cuda.synchronize()
         for i in range(30):
             scene.render(i, rows, radii=rows is None)
         torch.cuda.synchronize()
+        if not full:
+            return None, None
         _lib.check(lib.gsr_stage_times(ctx, buf, len(names)), "gsr_stage_times")
         _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
         return ms, {n: float(buf[i]) for i, n in enumerate(names)}
 
-    # The untimed diagnostic passes run first, so the device has been rendering for ~200 frames
-    # when the timed region starts: a run of 20 timed frames after 5 warmup frames measured
+    # The untimed settling frames (with --full: the diagnostic passes) run first, so the device
+    # has been rendering for ~200 frames when the timed region starts: a run of 20 timed frames
+    # after 5 warmup frames measured
     # 3,160-3,250 frames/s against 3,670-3,720 after 100+ frames of rendering (the same binary;
     # the GPU settles over the first ~30 ms of load), and the metric is the steady frame rate of
     # a viewer that keeps rendering.  Their sizes are fixed (not tied to --steps) for that reason.
@@ -517,18 +577,21 @@ def main():
         _lib.check(lib.gsr_set_option(c, _lib.GSR_OPT_FRAME_GRAPHS, graphs_inflight),
                    "gsr_set_option")
 
-    # (1) The blend's event time with frames in flight (events around the blend on every 8th
-    # forward of slot 0; these frames run on the stream path).
+    # (1) 64 settling frames in flight; with --full the blend's event time with frames in flight
+    # (events around the blend on every 8th forward of slot 0; these frames run on the stream
+    # path).
     n_pre = 0
-    _lib.check(lib.gsr_set_timing(ctx, 2), "gsr_set_timing")
+    if full:
+        _lib.check(lib.gsr_set_timing(ctx, 2), "gsr_set_timing")
     for i in range(64):
         step(n_pre + i)
     n_pre += 64
     drain()
     torch.cuda.synchronize()
-    _lib.check(lib.gsr_stage_times(ctx, buf, len(names)), "gsr_stage_times")
-    _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
-    blend_ms_timed = float(buf[names.index("blend")])
+    if full:
+        _lib.check(lib.gsr_stage_times(ctx, buf, len(names)), "gsr_stage_times")
+        _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
+        blend_ms_timed = float(buf[names.index("blend")])
     if world > 1:
         if balancer is not None:  # the split these frames ended with (for the serial passes)
             rows = balancer.current[rank]
@@ -553,8 +616,8 @@ def main():
     t0 = time.perf_counter()
     K_total = 0
     for i in range(args.steps):
-        K_total += step(n_pre + args.warmup + i)
-    drain()
+        K_total += step(n_pre + args.warmup + i, keep=i == args.steps - 1)
+    gathered = drain()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -569,51 +632,69 @@ def main():
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     t_max = float(t_max.item())
 
-    # Frame statistics for the algorithmic byte counts (frame 0 of the camera path, full frame).
-    res = scene.render(0, rows)
-    # the list entries that frame binned (tight binning: fewer than upstream's num_rendered)
-    K_list, T_all = ctypes.c_int64(), ctypes.c_int32()
-    _lib.check(_lib.load_library().gsr_get_binning(
-        _lib.context(local, 0), None, None, None, ctypes.byref(K_list), ctypes.byref(T_all),
-        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gsr_get_binning")
+    # --dump-outputs: what the last timed frame handed its caller -- one GPU: the image, the
+    # radii (full frames) and num_rendered; N GPUs: rank 0's gathered frame and its strip's
+    # num_rendered.  The scene, camera path and frame index are fixed by the arguments, so two
+    # builds run with the same arguments write arrays that can be compared entry for entry.
+    if args.dump_outputs and rank == 0:
+        if gather is not None:
+            last["color"] = gathered
+        dump_outputs(args.dump_outputs,
+                     {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor)
+                          else np.asarray(v)) for k, v in last.items() if v is not None})
+    last.clear()
+
     P = scene.P
-    P_v = int((res.radii > 0).sum().item())
-    view = scene.cams[0][0]
-    from gaussiansplattingviewer_amd.rasterizer import GaussianRasterizer, GaussianRasterizationSettings
-    P_f = int(GaussianRasterizer(GaussianRasterizationSettings(
-        H, W, 1.0, 1.0, scene.bg, 1.0, view, scene.cams[0][1], scene.deg, scene.cams[0][2],
-        False, False)).markVisible(scene.xyz).sum().item())
-    K_mean = K_total / args.steps
-    T_strip = ((rows[1] - rows[0]) if rows else gy) * ((W + 15) // 16)
-    rows_px = (min(H, rows[1] * 16) - rows[0] * 16) if rows else H
-    sh_bytes = 4 * 3 * (scene.deg + 1) ** 2
-    alg = algorithmic_bytes(P, P_f, P_v, K_mean, T_strip, W, rows_px, sh_bytes)
-    # The roofline kernel is the blend: the largest share of GPU time in the rocprofv3 trace and
-    # the last kernel on the frame's critical path.  Its launch duration: the serial stage pass
-    # (one frame at a time, events on the forward's stream bracket the kernel alone), which is
-    # what the committed serial rocprofv3 trace reports for it; the timed region's blend events
-    # (two frames in flight, the other frame's kernels sharing the CUs) are reported beside it.
-    dom_ms = stage_ms["blend"]
-    default_opts = args.blend == "fast"  # the committed profiles are of the default arithmetic
-    # profiles are keyed by config (and the simulated strip: <tag>_<config>-strip<R><N>_*.json)
-    prof_key = args.config + (f"-strip{args.sim_strip.replace('/', '')}" if args.sim_strip else "")
-    if world > 1:
-        prof_key = None  # no profile of a rank's strip of a multi-GPU frame
-    roofline = blend_roofline(prof_key if default_opts else None, dom_ms, blend_ms_timed,
-                              alg["blend"])
-    roofline["frame_alg_gbs"] = round(sum(alg.values()) / (t_max / args.steps) / 1e9, 2)
-    # the design's own minimum bytes (frame 0's list length) over the same frame time
-    dsg = design_bytes(P, P_f, P_v, int(K_list.value), T_strip, W, rows_px, sh_bytes)
-    dsg_gbs = sum(dsg.values()) / (t_max / args.steps) / 1e9
-    roofline["frame_design"] = {
-        "bytes_per_frame": int(sum(dsg.values())), "gbs": round(dsg_gbs, 2),
-        "frac_of_hbm": round(dsg_gbs / HBM_PEAK_GBS, 4),
-        "per_stage_bytes": {k: int(v) for k, v in dsg.items()},
-        "note": "this design's minimum HBM bytes per frame (bench.design_bytes: the 4-B list "
-                "words it bins, one read + write of the depth sort's 8-B pairs, the 48-B blend "
-                "records per list entry) over the timed frame time; frame_alg_gbs above is "
-                "SURVEY.md 8(d)'s upstream model (12-B pairs, upstream's K), which can exceed "
-                "the peak on this design"}
+
+    def diagnostics():
+        """--full: the frame statistics and the blend's roofline (one more frame, the binning
+        read back, the frustum count), from the instrumented passes above."""
+        # Frame statistics for the algorithmic byte counts (frame 0 of the camera path, full frame).
+        res = scene.render(0, rows)
+        # the list entries that frame binned (tight binning: fewer than upstream's num_rendered)
+        K_list, T_all = ctypes.c_int64(), ctypes.c_int32()
+        _lib.check(_lib.load_library().gsr_get_binning(
+            _lib.context(local, 0), None, None, None, ctypes.byref(K_list), ctypes.byref(T_all),
+            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gsr_get_binning")
+        P_v = int((res.radii > 0).sum().item())
+        view = scene.cams[0][0]
+        from gaussiansplattingviewer_amd.rasterizer import GaussianRasterizer, GaussianRasterizationSettings
+        P_f = int(GaussianRasterizer(GaussianRasterizationSettings(
+            H, W, 1.0, 1.0, scene.bg, 1.0, view, scene.cams[0][1], scene.deg, scene.cams[0][2],
+            False, False)).markVisible(scene.xyz).sum().item())
+        K_mean = K_total / args.steps
+        T_strip = ((rows[1] - rows[0]) if rows else gy) * ((W + 15) // 16)
+        rows_px = (min(H, rows[1] * 16) - rows[0] * 16) if rows else H
+        sh_bytes = 4 * 3 * (scene.deg + 1) ** 2
+        alg = algorithmic_bytes(P, P_f, P_v, K_mean, T_strip, W, rows_px, sh_bytes)
+        # The roofline kernel is the blend: the largest share of GPU time in the rocprofv3 trace and
+        # the last kernel on the frame's critical path.  Its launch duration: the serial stage pass
+        # (one frame at a time, events on the forward's stream bracket the kernel alone), which is
+        # what the committed serial rocprofv3 trace reports for it; the timed region's blend events
+        # (two frames in flight, the other frame's kernels sharing the CUs) are reported beside it.
+        dom_ms = stage_ms["blend"]
+        default_opts = args.blend == "fast"  # the committed profiles are of the default arithmetic
+        # profiles are keyed by config (and the simulated strip: <tag>_<config>-strip<R><N>_*.json)
+        prof_key = args.config + (f"-strip{args.sim_strip.replace('/', '')}" if args.sim_strip else "")
+        if world > 1:
+            prof_key = None  # no profile of a rank's strip of a multi-GPU frame
+        roofline = blend_roofline(prof_key if default_opts else None, dom_ms, blend_ms_timed,
+                                  alg["blend"])
+        roofline["frame_alg_gbs"] = round(sum(alg.values()) / (t_max / args.steps) / 1e9, 2)
+        # the design's own minimum bytes (frame 0's list length) over the same frame time
+        dsg = design_bytes(P, P_f, P_v, int(K_list.value), T_strip, W, rows_px, sh_bytes)
+        dsg_gbs = sum(dsg.values()) / (t_max / args.steps) / 1e9
+        roofline["frame_design"] = {
+            "bytes_per_frame": int(sum(dsg.values())), "gbs": round(dsg_gbs, 2),
+            "frac_of_hbm": round(dsg_gbs / HBM_PEAK_GBS, 4),
+            "per_stage_bytes": {k: int(v) for k, v in dsg.items()},
+            "note": "this design's minimum HBM bytes per frame (bench.design_bytes: the 4-B list "
+                    "words it bins, one read + write of the depth sort's 8-B pairs, the 48-B blend "
+                    "records per list entry) over the timed frame time; frame_alg_gbs above is "
+                    "SURVEY.md 8(d)'s upstream model (12-B pairs, upstream's K), which can exceed "
+                    "the peak on this design"}
+        return P_f, P_v, K_mean, K_list, T_strip, roofline
+
     fps = args.steps / t_max
     line = {
         "metric": METRIC,
@@ -638,16 +719,7 @@ def main():
                                    f"image strips x{world}" + (" + RCCL gather" if world > 1 else "")),
                    "blend_arithmetic": args.blend},
         "msplats_per_sec": round(P * fps / 1e6, 2),
-        "frame_stats": {"P_frustum": P_f, "P_visible": P_v, "K_pairs_mean": round(K_mean, 1),
-                        "K_list_frame0": int(K_list.value), "tiles": T_strip,
-                        "note": "K_pairs_mean is upstream's num_rendered (the SURVEY.md §8(d) "
-                                "bytes use it: an upper bound); K_list_frame0 the (Gaussian, "
-                                "tile) entries frame 0 binned and blended (tight binning on "
-                                "full frames keeps only tiles the alpha >= 1/255 ellipse "
-                                "reaches); msplats_per_sec counts Gaussians, not pairs"},
-        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-        "stage_ms_note": "HIP events at every stage boundary, separate 30-frame serial pass "
-                         "(each event adds a few us); the timed region records no events",
+        "full": full,
         "inflight": args.inflight,
         "second_stream": pipe.second_stream,
         "streams": {"plan": rank_stream_plan(args.inflight, pipe.second_stream),
@@ -664,11 +736,15 @@ def main():
                              "HIP fixes a stream's hardware queue when the stream is first used; "
                              "a rank takes 8 queues so that RCCL's streams do not share the "
                              "frame streams' queues")},
-        "timed_after": ("194 serial (64 untimed, 100 for the serial rate, 30 with stage events) "
-                        "then 64 in-flight (blend events) untimed diagnostic frames, then the W "
-                        "warmup frames" if world == 1 else
-                        "64 in-flight (blend events) + 130 serial (rate, stage events) untimed "
-                        "diagnostic frames, then the W warmup frames"),
+        "timed_after": (("194 serial (64 untimed, 100 for the serial rate, 30 with stage events) "
+                         "then 64 in-flight (blend events) untimed diagnostic frames, then the W "
+                         "warmup frames" if world == 1 else
+                         "64 in-flight (blend events) + 130 serial (rate, stage events) untimed "
+                         "diagnostic frames, then the W warmup frames") if full else
+                        ("194 serial then 64 in-flight" if world == 1 else
+                         "64 in-flight then 130 serial") +
+                        " untimed settling frames (--full instruments them), then the W warmup "
+                        "frames"),
         "strip_layout": (None if balancer is None else
                          {"tile_rows": [list(t) for t in balancer.current],
                           "rebalances": len(balancer.history),
@@ -683,13 +759,27 @@ def main():
                                  "Gaussians, two in flight; 2 deferred-K chains on one stream: "
                                  "strip frames below 4M Gaussians) and of the serial pass "
                                  "(direct launches, as a caller without the pipeline)"},
-        "serial_ms_per_frame": round(serial_ms, 4),
-        "serial_note": "one frame in flight at a time (no FramePipeline overlap), this rank",
-        "roofline": roofline,
-        "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(scene, args.cpu_seconds)
+    if full:
+        P_f, P_v, K_mean, K_list, T_strip, roofline = diagnostics()
+        line.update({
+            "frame_stats": {"P_frustum": P_f, "P_visible": P_v, "K_pairs_mean": round(K_mean, 1),
+                            "K_list_frame0": int(K_list.value), "tiles": T_strip,
+                            "note": "K_pairs_mean is upstream's num_rendered (the SURVEY.md §8(d) "
+                                    "bytes use it: an upper bound); K_list_frame0 the (Gaussian, "
+                                    "tile) entries frame 0 binned and blended (tight binning on "
+                                    "full frames keeps only tiles the alpha >= 1/255 ellipse "
+                                    "reaches); msplats_per_sec counts Gaussians, not pairs"},
+            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+            "stage_ms_note": "HIP events at every stage boundary, separate 30-frame serial pass "
+                             "(each event adds a few us); the timed region records no events",
+            "serial_ms_per_frame": round(serial_ms, 4),
+            "serial_note": "one frame in flight at a time (no FramePipeline overlap), this rank",
+            "roofline": roofline,
+            "cpu_baseline": None,
+        })
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(scene, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

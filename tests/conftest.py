@@ -24,6 +24,17 @@ def golden():
 
 
 @pytest.fixture(scope="session")
+def sort_backend(golden):
+    """The reference's sort-backend vectors (make_golden.save_sort_backend stores them in three
+    files) as one dict with the keys they were captured under."""
+    g = dict(golden("sort_backend.npz"))
+    a, b = golden("sort_backend_100k_a.npz"), golden("sort_backend_100k_b.npz")
+    g["100k_front__index"] = a["100k_front__index"]
+    g["xyz_100k"] = np.concatenate([a["xyz_100k__rows0"], b["xyz_100k__rows1"]])
+    return g
+
+
+@pytest.fixture(scope="session")
 def oracle_mod():
     import oracle
     oracle.lib()

@@ -11,6 +11,8 @@ Captured:
   sort_backend.npz  -- renderer_ogl._sort_gaussian_cpu (renderer_ogl.py:10-19): the float32
                        depth array the reference sorts (recorded inside its call) and the
                        int32 index it returns, for several (xyz, view) cases incl. ties.
+                       The 100k case's positions and index lie in sort_backend_100k_a.npz and
+                       sort_backend_100k_b.npz (save_sort_backend: every file below 1 MiB).
   camera.npz        -- util.Camera.get_project_matrix / get_htanfovxy_focal (util.py:82-113)
                        at the four benchmark resolutions.
   naive_gaussian.npz-- util_gau.naive_gaussian() (util_gau.py:25-60).
@@ -74,6 +76,19 @@ def _views():
         "oblique": look_at((2.5, 1.5, -3.0), (0.1, -0.2, 0.3), (0.0, -1.0, 0.0)),
         "viewer_default": look_at((-3.0, 0.0, 1.5), (-3.0, 0.0, 0.5), (0.0, -1.0, 0.0)),
     }
+
+
+def save_sort_backend(out):
+    """The sort-backend vectors in three files, each below the repository's 1 MiB limit for a
+    committed file: the 100k case's positions in two halves (with its index beside the first),
+    everything else in sort_backend.npz.  tests/conftest.py `sort_backend` puts them together."""
+    half = len(out["xyz_100k"]) // 2
+    a = {"xyz_100k__rows0": out["xyz_100k"][:half], "100k_front__index": out["100k_front__index"]}
+    b = {"xyz_100k__rows1": out["xyz_100k"][half:]}
+    rest = {k: v for k, v in out.items() if k != "xyz_100k" and k not in a}
+    np.savez_compressed(os.path.join(HERE, "sort_backend.npz"), **rest)
+    np.savez_compressed(os.path.join(HERE, "sort_backend_100k_a.npz"), **a)
+    np.savez_compressed(os.path.join(HERE, "sort_backend_100k_b.npz"), **b)
 
 
 def make_ply_ref(util_gau, tmpdir):
@@ -211,7 +226,7 @@ def main(only=None):
         out[f"{name}__view"] = view.astype(np.float32)
         out[f"{name}__depth"] = seen[0]
         out[f"{name}__index"] = index
-    np.savez_compressed(os.path.join(HERE, "sort_backend.npz"), **out)
+    save_sort_backend(out)
 
     # --- camera ---------------------------------------------------------------------
     cam_out = {}

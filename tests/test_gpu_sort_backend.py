@@ -1,5 +1,5 @@
 """GPU: the device depth-sort backend (replacing renderer_ogl.py:10-53) against the reference's
-own outputs (tests/golden/sort_backend.npz) and stable-sort properties at full size."""
+own outputs (tests/golden/sort_backend*.npz) and stable-sort properties at full size."""
 import numpy as np
 import pytest
 import torch
@@ -13,8 +13,8 @@ CASES = ["10k_front", "10k_oblique", "10k_viewer_default", "100k_front", "ties_f
 
 
 @pytest.mark.parametrize("case", CASES)
-def test_depth_bits_and_order_vs_reference(gpu, golden, case):
-    g = golden("sort_backend.npz")
+def test_depth_bits_and_order_vs_reference(gpu, sort_backend, case):
+    g = sort_backend
     xyz = g["xyz_" + case.split("_")[0]]
     view = g[case + "__view"]
     ref_depth = g[case + "__depth"]
@@ -28,8 +28,8 @@ def test_depth_bits_and_order_vs_reference(gpu, golden, case):
     np.testing.assert_array_equal(ref_depth[idx], ref_depth[ref_idx])
 
 
-def test_sort_backend_contract(gpu, golden):
-    g = golden("sort_backend.npz")
+def test_sort_backend_contract(gpu, sort_backend):
+    g = sort_backend
     gaus = type("G", (), {})()
     gaus.xyz = g["xyz_10k"]
     out = _sort_gaussian_hip(gaus, g["10k_front__view"])

@@ -13,8 +13,8 @@ def _xyz(g, case):
 
 
 @pytest.mark.parametrize("case", SORT_CASES)
-def test_view_depth_bit_exact_vs_reference(golden, oracle_mod, case):
-    g = golden("sort_backend.npz")
+def test_view_depth_bit_exact_vs_reference(sort_backend, oracle_mod, case):
+    g = sort_backend
     d = oracle_mod.view_depth(_xyz(g, case), g[case + "__view"])
     ref = g[case + "__depth"]
     assert d.dtype == np.float32
@@ -22,10 +22,10 @@ def test_view_depth_bit_exact_vs_reference(golden, oracle_mod, case):
 
 
 @pytest.mark.parametrize("case", SORT_CASES)
-def test_stable_argsort_and_reference_order(golden, oracle_mod, case):
+def test_stable_argsort_and_reference_order(sort_backend, oracle_mod, case):
     """The reference uses np.argsort's default (unstable) kind: its order must equal the
     stable order on the sorted depth sequence and everywhere outside tie groups."""
-    g = golden("sort_backend.npz")
+    g = sort_backend
     depth = g[case + "__depth"]
     ref_idx = g[case + "__index"][:, 0]
     ours = oracle_mod.argsort_stable(depth)
@@ -40,8 +40,8 @@ def test_stable_argsort_and_reference_order(golden, oracle_mod, case):
 
 
 @pytest.mark.parametrize("case", SORT_CASES)
-def test_cpu_baseline_restatement_matches_reference(golden, oracle_mod, case):
-    g = golden("sort_backend.npz")
+def test_cpu_baseline_restatement_matches_reference(sort_backend, oracle_mod, case):
+    g = sort_backend
     idx = oracle_mod.sort_gaussian_cpu(_xyz(g, case), g[case + "__view"])
     assert idx.dtype == np.int32 and idx.shape == (len(_xyz(g, case)), 1)
     np.testing.assert_array_equal(idx, g[case + "__index"])

@@ -8,6 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/configs
 run() {  # name args...
     local name=$1; shift
+    set -- --full "$@"  # the summary line below reads the serial frame time and the frame statistics
     timeout -k 10 300 python bench.py "$@" > gpurun_out/configs/$name.log 2>&1 || { echo "$name failed"; tail -5 gpurun_out/configs/$name.log; exit 1; }
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['ms_per_step'], d['serial_ms_per_frame'], d['frame_stats'])" gpurun_out/configs/$name.log $name
 }

@@ -15,7 +15,7 @@ TAG=${TAG:-r03}
 OUT=gpurun_out/prof_${TAG}_${CONFIG}
 mkdir -p "$OUT"
 sha256sum gaussiansplattingviewer_amd/libgsr.so | cut -c1-16 > "$OUT/lib.sha"
-ARGS="--config $CONFIG --inflight 1 --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${EXTRA:-}"
+ARGS="--full --config $CONFIG --inflight 1 --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline ${EXTRA:-}"
 pass() {  # name rocprof-args...
     local name=$1; shift
     timeout -k 10 ${PASS_SECS:-300} rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o pmc \
