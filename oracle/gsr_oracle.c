@@ -478,6 +478,137 @@ void oracle_render(const OracleIn *in, const uint32_t *ranges, const uint32_t *p
         }
 }
 
+/* forward.cu: renderCUDA per pixel with every operation in double (exp from libm), for judging
+ * a float32 blend (the C oracle above, or the HIP kernel in either arithmetic mode) against the
+ * true value of upstream's formula on the same float32 records and lists.  Per pixel it also
+ * says whether the pixel's discrete decisions can be told apart from float32 rounding
+ * (`stable`) and, if so, how far a correct float32 blend may lie from the double result
+ * (`bound`, absolute, for each colour channel and for final_T).
+ *
+ * u = 2^-24 (one float32 rounding, relative), ulp = 2^-23.
+ *
+ * Exponent.  For one splat at one pixel, dx, dy from the float32 centre,
+ *     dp = KAPPA u M + C0 u (1 + |ln o|),
+ *     M  = (|a| Dx^2 + |c| Dy^2) / 2 + |b| Dx Dy,   Dx = |dx| + 7, Dy = |dy| + 7
+ * bounds the absolute error of ln(alpha_raw) = power + ln(o) in any of the evaluations.  The
+ * +7 makes M cover the terms of the quadratic expanded about any point of the pixel's 8x8
+ * quadrant (|e| + |u| <= |dx| + 7 for an expansion point e and a lane offset u), so it does
+ * not depend on how a kernel stages the splat.
+ *   KAPPA = 16: the project's budget for a float32 quadratic (blend.hip q_lower).  The fast
+ *     form spends 2 roundings on a pre-scaled coefficient, 1 on the centre offset (twice in a
+ *     product), 5 on k0 / the linear coefficients, 1 on k0 + log2 o and 5 FMAs whose partial
+ *     sums are <= M log2(e) + |log2 o|: about 13 u M; upstream's order spends 5.
+ *   C0 = 8, by counting the roundings that are not proportional to M.  On |ln o| (fast form):
+ *     v_log_f32 1 ulp = 2 u, k0 + log2 o 1 u, the 5 FMAs' partial sums 5 u: 8 u |ln o|.
+ *     Constant: v_exp_f32 1 ulp = 2 u (fast); expf 1 ulp = 2 u and o * exp 1 u (upstream's
+ *     order): at most 3 u.  C0 = max(8, 3).
+ * r = expm1(dp) + 2 ulp is the relative error of alpha (2 ulp: the alpha product and slack for
+ * the constants 0.99f, 1/255f, 0.0001f, which are used here as the float32 values); r = 0 where
+ * the 0.99 cap binds in every evaluation (alpha_raw (1 - r) > 0.99f).
+ *
+ * T.  relT, the relative error of T, grows per contributing splat by alpha r / (1 - alpha)
+ * (the error of 1 - alpha) + 4 ulp (1 - alpha and the product rounded, or the one FMA of the
+ * fast form, with slack).
+ *
+ * A pixel is unstable if for any splat evaluated before it is done: |power| <= dp (the
+ * power > 0 skip); |alpha_raw / (1/255f) - 1| <= r (the alpha threshold); the splat is not
+ * skipped and |test_T - 0.0001f| <= 0.0001f relT' (termination; relT' includes this step); or
+ * dp >= 1/4 (first order no longer holds).  A splat of opacity < 2^-10 with KAPPA u M < 1 is
+ * skipped decidably (alpha_raw < 1/255 by a factor 4 wherever power <= 0), which also keeps
+ * opacity 0 (ln o = -inf) out of dp.
+ *
+ * bound = sum_k max|rgb_k| (w_k (r_k + relT_k + 6 ulp) + u T_k) + u sum_k max|C_k|
+ *         + T relT max(1, max|bg|) + 4 ulp max(1, max|C|),   w_k = alpha_k T_k.
+ * 6 ulp: the two products and the add of one accumulation with slack.  u T_k: the fast form
+ * takes the weight as T - fl(T - alpha T), which carries the rounding of the new T (<= u T),
+ * not of alpha T.  u max|C_k|: the add into the running colour rounds relative to the sum.
+ * (The last two are roundings that the first-order formula alone misses for long lists of
+ * faint splats.)
+ *
+ * flags: 1 a splat skipped by power > 0, 2 the 0.99 cap bound, 4 terminated by T < 1e-4,
+ * 8 the tile's list is longer than 64. */
+#define F64_SKIP_POWER 1
+#define F64_CAP 2
+#define F64_TERM 4
+#define F64_LONG 8
+void oracle_render_f64(int W, int H, const float *bg, const uint32_t *ranges,
+                       const uint32_t *point_list, const float *means2D, const float *features,
+                       const float *conic_opacity, double *out_color, double *final_T,
+                       uint32_t *n_contrib, uint8_t *stable, double *bound, uint8_t *flags) {
+    const double U = 0x1p-24, ULP = 0x1p-23, KAPPA = 16.0, C0 = 8.0;
+    const double A_MIN = (double)(1.0f / 255.0f), CAP = (double)0.99f, T_MIN = (double)0.0001f;
+    const uint32_t gx = (uint32_t)((W + BLOCK_X - 1) / BLOCK_X);
+    const uint32_t gy = (uint32_t)((H + BLOCK_Y - 1) / BLOCK_Y);
+    const double bgmax = fmax(fmax(fabs((double)bg[0]), fabs((double)bg[1])), fabs((double)bg[2]));
+#pragma omp parallel for collapse(2) schedule(dynamic, 4)
+    for (uint32_t ty = 0; ty < gy; ++ty)
+        for (uint32_t tx = 0; tx < gx; ++tx) {
+            const uint32_t r0 = ranges[2 * (ty * gx + tx)], r1 = ranges[2 * (ty * gx + tx) + 1];
+            for (uint32_t ly = 0; ly < BLOCK_Y; ++ly)
+                for (uint32_t lx = 0; lx < BLOCK_X; ++lx) {
+                    const uint32_t px = tx * BLOCK_X + lx, py = ty * BLOCK_Y + ly;
+                    if (px >= (uint32_t)W || py >= (uint32_t)H) continue;
+                    double T = 1.0, C[3] = {0.0, 0.0, 0.0}, relT = 0.0, bnd = 0.0;
+                    uint32_t contributor = 0, last_contributor = 0;
+                    int unstable = 0;
+                    uint8_t fl = (r1 - r0 > 64u) ? F64_LONG : 0;
+                    for (uint32_t j = r0; j < r1; ++j) {
+                        contributor++;
+                        const uint32_t id = point_list[j];
+                        const double dx = (double)means2D[2 * id] - (double)px;
+                        const double dy = (double)means2D[2 * id + 1] - (double)py;
+                        const float *co = conic_opacity + 4 * id;
+                        const double a = co[0], b = co[1], c = co[2], o = co[3];
+                        const double power = -0.5 * (a * dx * dx + c * dy * dy) - b * dx * dy;
+                        const double Dx = fabs(dx) + 7.0, Dy = fabs(dy) + 7.0;
+                        const double M =
+                            0.5 * (fabs(a) * Dx * Dx + fabs(c) * Dy * Dy) + fabs(b) * Dx * Dy;
+                        const double dpM = KAPPA * U * M;
+                        if (o < 0x1p-10 && dpM < 1.0) { /* never reaches 1/255 */
+                            if (power > dpM) fl |= F64_SKIP_POWER;
+                            continue;
+                        }
+                        const double dp = dpM + C0 * U * (1.0 + fabs(log(o)));
+                        if (!(dp < 0.25) || fabs(power) <= dp) unstable = 1;
+                        if (power > 0.0) { fl |= F64_SKIP_POWER; continue; }
+                        const double araw = o * exp(power);
+                        const double r = expm1(dp) + 2.0 * ULP;
+                        if (fabs(araw / A_MIN - 1.0) <= r) unstable = 1;
+                        if (araw < A_MIN) continue;
+                        const double alpha = fmin(CAP, araw);
+                        if (araw >= CAP) fl |= F64_CAP;
+                        const double ra = (araw * (1.0 - r) > CAP) ? 0.0 : r;
+                        const double test_T = T * (1.0 - alpha);
+                        const double relT_next = relT + alpha * ra / (1.0 - alpha) + 4.0 * ULP;
+                        if (fabs(test_T - T_MIN) <= T_MIN * relT_next) unstable = 1;
+                        if (test_T < T_MIN) { fl |= F64_TERM; break; }
+                        const float *f = features + 3 * id;
+                        const double mx = fmax(fmax(fabs((double)f[0]), fabs((double)f[1])),
+                                               fabs((double)f[2]));
+                        const double w = alpha * T;
+                        bnd += mx * (w * (ra + relT + 6.0 * ULP) + U * T);
+                        for (int ch = 0; ch < 3; ++ch) C[ch] += (double)f[ch] * w;
+                        bnd += U * fmax(fmax(fabs(C[0]), fabs(C[1])), fabs(C[2]));
+                        T = test_T;
+                        relT = relT_next;
+                        last_contributor = contributor;
+                    }
+                    const size_t pid = (size_t)W * py + px;
+                    double cmax = 0.0;
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const double v = C[ch] + T * (double)bg[ch];
+                        out_color[(size_t)ch * H * W + pid] = v;
+                        cmax = fmax(cmax, fabs(v));
+                    }
+                    final_T[pid] = T;
+                    n_contrib[pid] = last_contributor;
+                    stable[pid] = (uint8_t)!unstable;
+                    bound[pid] = bnd + T * relT * fmax(1.0, bgmax) + 4.0 * ULP * fmax(1.0, cmax);
+                    flags[pid] = fl;
+                }
+        }
+}
+
 /* forward.cu computeColorFromSH over P Gaussians (every one, not only the visible): rgb[3P]
  * the clamped colour, clamped[3P] (optional) its clamp flags -- so the pre-clamp value is rgb
  * where the flag is 0.  For the GLSL-twin check (tests/test_oracle_glsl_twins.py). */

@@ -9,7 +9,10 @@ Contents:
                              SortPairs -> identifyTileRanges -> renderCUDA).  PARITY UNPINNED:
                              no output of the real upstream CUDA forward exists to check it
                              against (see gsr_oracle.c header and DESIGN.md).
-  view_depth / argsort    -- the reference's own sort backend (renderer_ogl.py:10-19),
+  render_f64(...)         -- upstream's per-pixel blend in float64 on the float32 records and
+                             lists, with a per-pixel verdict (stable, error bound, event flags):
+                             the reference of tests/gpu_helpers.py assert_blend_exact.
+  view_depth / argsort    --the reference's own sort backend (renderer_ogl.py:10-19),
                              PINNED against tests/golden/ vectors captured from the reference.
   sort_gaussian_cpu(...)  -- numpy restatement of renderer_ogl.py:10-19 (the CPU baseline).
 """
@@ -60,6 +63,8 @@ def lib() -> ctypes.CDLL:
         L.oracle_bin.argtypes = [ctypes.POINTER(_OracleIn), vp, vp, vp, vp, i64, vp, vp, vp]
         L.oracle_render.restype = None
         L.oracle_render.argtypes = [ctypes.POINTER(_OracleIn)] + [vp] * 8
+        L.oracle_render_f64.restype = None
+        L.oracle_render_f64.argtypes = [ctypes.c_int, ctypes.c_int] + [vp] * 12
         L.oracle_view_depth.restype = None
         L.oracle_view_depth.argtypes = [vp, i64, vp, vp]
         L.oracle_argsort_f32.restype = ctypes.c_int
@@ -155,6 +160,36 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy
                         _p(conic), _p(color), _p(final_T), _p(n_contrib))
     out.update(color=color, final_T=final_T, n_contrib=n_contrib)
     return out
+
+
+F64_SKIP_POWER, F64_CAP, F64_TERM, F64_LONG = 1, 2, 4, 8  # render_f64 "flags" bits
+
+
+def render_f64(ranges, point_list, means2D, conic_opacity, features, bg, W, H) -> dict:
+    """Upstream's per-pixel blend in float64 on float32 records and lists (oracle_render's
+    inputs), with the per-pixel verdict of gsr_oracle.c oracle_render_f64: color [3,H,W],
+    final_T, n_contrib, stable (bool: every skip / termination decision is clear of float32
+    rounding), bound (absolute error allowed to a float32 blend on a stable pixel) and flags
+    (F64_* bits: events that occurred at the pixel)."""
+    rg = _c(ranges, np.uint32).reshape(-1)
+    assert len(rg) == 2 * ((W + 15) // 16) * ((H + 15) // 16)
+    pl = _c(point_list, np.uint32).reshape(-1)
+    m2 = _c(means2D).reshape(-1)
+    co = _c(conic_opacity).reshape(-1)
+    ft = _c(features).reshape(-1)
+    assert len(co) == 2 * len(m2) and 3 * len(m2) == 2 * len(ft)
+    bgc = _c(bg).reshape(3)
+    color = np.zeros((3, H, W), np.float64)
+    final_T = np.zeros((H, W), np.float64)
+    n_contrib = np.zeros((H, W), np.uint32)
+    stable = np.zeros((H, W), np.uint8)
+    bound = np.zeros((H, W), np.float64)
+    flags = np.zeros((H, W), np.uint8)
+    lib().oracle_render_f64(int(W), int(H), _p(bgc), _p(rg), _p(pl) if len(pl) else None,
+                            _p(m2), _p(ft), _p(co), _p(color), _p(final_T), _p(n_contrib),
+                            _p(stable), _p(bound), _p(flags))
+    return dict(color=color, final_T=final_T, n_contrib=n_contrib, stable=stable.astype(bool),
+                bound=bound, flags=flags)
 
 
 _TIGHT_KEYS = ("not_subsequence", "kept", "dropped", "dropped_reaching", "first_tile",

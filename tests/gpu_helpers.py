@@ -96,10 +96,14 @@ def ulp_diff(a, b):
 # where the oracle rounds every product.  Both shift values by a few ulp and can flip the
 # alpha >= 1/255 or T < 1e-4 threshold of a rare pixel (one such flip moves it by <= alpha * rgb
 # ~ 1/255).  Bar: >= 99.99 % of values within 1e-5, every value within 4e-3, PSNR (peak 1)
-# >= 80 dB.  Measured on MI355X with the final round-3 build, lib 726b24d0
-# (profiles/r03n_blend_error_vs_oracle.jsonl, both modes, C2, C3, c3r, C4 full frame, C5 frames
-# 0/250/500/750): max abs 2.3e-3 (C3, exact) / 1.8e-3 (C4, fast), at least 99.9992 % of values
-# within 1e-5 (c3r, fast), PSNR >= 118.6 dB, n_contrib mismatch <= 4.8e-6.
+# >= 80 dB.  This statistical bar is what the large frames are held to, and what a pixel with a
+# decision inside its rounding (an "unstable" pixel) is held to everywhere.  On the frames small
+# enough for it, assert_blend_exact below holds every other pixel to its own bound against a
+# float64 evaluation of upstream's formula; the evidence behind both -- per arithmetic mode,
+# the error as a share of the bound, the largest absolute error and the unstable share, measured
+# on an MI355X -- is DESIGN.md section 4, "Blend error against float64" (it replaces the
+# round-3 distances between two float32 evaluations, profiles/r03n_blend_error_vs_oracle.jsonl:
+# max abs 2.3e-3 exact / 1.8e-3 fast on C2 .. C5, which still stand behind IMG_MAX).
 IMG_ATOL = 1e-5
 IMG_FRAC = 0.9999
 IMG_MAX = 4e-3
@@ -120,6 +124,52 @@ def assert_image_close(got, want, what="color"):
     assert (d.max() if d.size else 0.0) <= IMG_MAX, f"{what}: max abs diff {d.max()}"
     p = psnr_db(got, want)
     assert p >= IMG_PSNR_DB, f"{what}: PSNR {p:.1f} dB < {IMG_PSNR_DB} dB"
+
+
+UNSTABLE_CAP = 0.05  # a condition on the scene, met by the oracle alone (test_blend_reference.py)
+
+
+def blend_reference(oracle, orc, bg, features=None):
+    """The float64 blend (oracle.render_f64) of an oracle result's records and lists, computed
+    once per oracle result and kept in it."""
+    if "_f64" not in orc:
+        W, H = orc["color"].shape[2], orc["color"].shape[1]
+        orc["_f64"] = oracle.render_f64(orc["ranges"], orc["point_list"], orc["means2D"],
+                                        orc["conic_opacity"],
+                                        orc["rgb"] if features is None else features, bg, W, H)
+    return orc["_f64"]
+
+
+def assert_blend_exact(oracle, got, orc, bg, features=None, parity=True, what="blend"):
+    """The blend per pixel against the float64 reference of the same records and lists (which
+    `got`, rendered with all extras, shares bit for bit with the oracle result `orc`: asserted
+    first unless parity=False, for a result that has no lists of its own).  On the reference's
+    stable pixels: n_contrib equal, final_T and every colour channel within the pixel's bound.
+    On the others (a decision within rounding of its threshold) today's IMG_MAX.  features: the
+    colours_precomp of the call (default: the oracle's SH colours).  Returns max err / bound
+    over the stable pixels."""
+    if parity:
+        assert_parity(got, orc, image=False)
+    ref = blend_reference(oracle, orc, bg, features)
+    st = ref["stable"]
+    share = 1.0 - float(st.mean()) if st.size else 0.0
+    assert share <= UNSTABLE_CAP, f"{what}: {share:.4f} of pixels unstable"
+    e_T = np.abs(got["final_T"].astype(np.float64) - ref["final_T"])
+    e_C = np.abs(got["color"].astype(np.float64) - ref["color"]).max(axis=0)
+    err = np.maximum(e_T, e_C)
+    ratio = float((err[st] / ref["bound"][st]).max()) if st.any() else 0.0
+    print(f"{what}: unstable {share:.5f}, stable max err {err[st].max() if st.any() else 0.0:.3e}"
+          f" = {ratio:.3f} of bound (max bound {ref['bound'][st].max() if st.any() else 0.0:.3e})")
+    bad_n = st & (got["n_contrib"] != ref["n_contrib"])
+    assert not bad_n.any(), (f"{what}: n_contrib differs at {int(bad_n.sum())} stable pixels, "
+                             f"first (y, x) {tuple(np.argwhere(bad_n)[0])}")
+    bad = st & ~(err <= ref["bound"])
+    assert not bad.any(), (f"{what}: {int(bad.sum())} stable pixels beyond their bound, worst "
+                           f"{ratio:.2f} x bound at (y, x) "
+                           f"{tuple(np.argwhere(st & (err / ref['bound'] >= ratio))[0])}")
+    worst_unstable = float(err[~st].max()) if (~st).any() else 0.0
+    assert worst_unstable <= IMG_MAX, f"{what}: unstable pixel off by {worst_unstable}"
+    return ratio
 
 
 def assert_parity(hip, orc, image=True):

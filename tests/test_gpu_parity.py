@@ -16,7 +16,8 @@ from gaussiansplattingviewer_amd.camera import Camera, static_camera
 from gaussiansplattingviewer_amd.gaussian_data import (GaussianData, naive_gaussian,
                                                        synthetic_gaussians)
 
-from gpu_helpers import (assert_image_close, assert_parity, run_hip, run_oracle, scene_inputs)
+from gpu_helpers import (assert_blend_exact, assert_image_close, assert_parity, run_hip,
+                         run_oracle, scene_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,6 +54,12 @@ CASES = {
 }
 
 
+# the cases small enough for the per-pixel float64 check (gpu_helpers.assert_blend_exact)
+BLEND_EXACT_CASES = ("C1_10k_640x480_sh3", "oblique_30k_800x600_sh3",
+                     "inside_cloud_20k_1160x522_sh3", "one_tile_5k_16x16_sh3",
+                     "one_row_8k_1000x12_sh3", "narrow_10k_33x700_sh3")
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_forward_parity(gpu, oracle_mod, name):
     P, W, H, deg, seed, eye = CASES[name]
@@ -61,6 +68,8 @@ def test_forward_parity(gpu, oracle_mod, name):
     hip = run_hip(s, gpu)
     assert orc["num_rendered"] > 0
     assert_parity(hip, orc)
+    if name in BLEND_EXACT_CASES:
+        assert_blend_exact(oracle_mod, hip, orc, s["bg"], what=name)
     _assert_plain_call_identical(gpu, s, hip)
 
 
@@ -177,7 +186,11 @@ def test_blend_mode_parity(gpu, oracle_mod, name, mode):
         hip = run_hip(s, gpu)
     finally:
         _set_option(gpu, _lib.GSR_OPT_BLEND_FAST, 1)
-    assert_parity(hip, run_oracle(oracle_mod, s))
+    orc = run_oracle(oracle_mod, s)
+    assert_parity(hip, orc)
+    if name == "C1_10k_640x480_sh3":
+        assert_blend_exact(oracle_mod, hip, orc, s["bg"],
+                           what=f"{name} {'fast' if mode else 'exact'}")
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
