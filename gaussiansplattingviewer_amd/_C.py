@@ -14,6 +14,9 @@ reaches through renderer_cuda.py:211-224):
 
     visible = _C.mark_visible(means3D, viewmatrix, projmatrix)
 
+`_C.rasterize_gaussians_shaded(<the same 19 arguments>, shading)` is this package's own: the
+same forward under one of the GL backend's shadings (`gsr_forward_shaded`, include/gsr.h).
+
 Same arguments, order and return arity; absent optional inputs are empty tensors, as upstream
 passes them.  The work is `gsr_forward` / `gsr_mark_visible` in libgsr.so, on torch's current
 HIP stream, with one `gsr_context` per device held by the extension.  The three buffers are
@@ -27,7 +30,8 @@ No fallback: importing this module fails when `_native.so` is not built
 from __future__ import annotations
 
 try:
-    from ._native import abi_version, mark_visible, rasterize_gaussians  # noqa: F401
+    from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
+                          rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

@@ -14,7 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB: another build of the library (A/B builds in tools/ab.sh); default the in-tree libgsr.so
 LIB_PATH = os.environ.get("GSR_LIB") or os.path.join(_HERE, "libgsr.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 GSR_OPT_BLEND_CULL = 1
 GSR_OPT_BLEND_FAST = 2
@@ -23,6 +23,12 @@ GSR_OPT_TIGHT_BINNING = 13
 GSR_OPT_FRAME_GRAPHS = 14
 GSR_OPT_SECOND_STREAM = 15
 
+# gsr_forward_shaded's `shading` (the GL backend's shading combo, include/gsr.h)
+GSR_SHADE_SPLAT = 0
+GSR_SHADE_BILLBOARD = 1
+GSR_SHADE_FLAT_BALL = 2
+GSR_SHADE_GAUSS_BALL = 3
+
 # Symbols include/gsr.h declares (checked by the CPU test suite).
 EXPORTED_SYMBOLS = (
     "gsr_abi_version", "gsr_last_error", "gsr_create", "gsr_destroy", "gsr_reserve",
@@ -30,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "gsr_set_timing", "gsr_stage_times", "gsr_stage_name", "gsr_set_option",
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
+    "gsr_forward_shaded",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -92,6 +99,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gsr_reserve.argtypes = [vp, i64, i64]
     lib.gsr_forward.argtypes = [vp, ctypes.POINTER(GsrGaussians),
                                 ctypes.POINTER(GsrRasterSettings), ctypes.POINTER(GsrOutputs), vp]
+    lib.gsr_forward_shaded.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                       ctypes.POINTER(GsrRasterSettings),
+                                       ctypes.POINTER(GsrOutputs), ctypes.c_int32, vp]
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -114,7 +124,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     for name in ("gsr_disparity_colors", "gsr_pack_image", "gsr_create", "gsr_reserve", "gsr_forward", "gsr_get_binning",
                  "gsr_mark_visible", "gsr_depth_argsort", "gsr_set_timing", "gsr_tile_row_pairs",
                  "gsr_stage_times", "gsr_set_option", "gsr_get_option", "gsr_ply_probe", "gsr_ply_load",
-                 "gsr_frame_graph_stats"):
+                 "gsr_frame_graph_stats", "gsr_forward_shaded"):
         getattr(lib, name).restype = i32
 
 

@@ -12,7 +12,7 @@
 //   4 column scatter    = tile-sort pass 1
 //   5 row pass          = tile-sort pass 2 (radix_sort.hip)
 //   6 join                                          <- join
-//   7 blend             (blend.hip)
+//   7 blend             (blend.hip)               gsr_forward_shaded: a GL shading's first-hit kernel
 //
 // Binning has two forms with identical results: the column-first form above (default), and the
 // per-pair form (offsets scan -> duplicate fused with the first tile-sort pass -> the remaining
@@ -101,6 +101,9 @@ constexpr int64_t kMinListCap = 1 << 16;
 
 // Everything the kernels of a frame's recorded graphs read besides the context's own
 // workspace (named by its generation): a forward whose key equals a recorded one replays it.
+// The shading (gsr_forward_shaded) reaches the recorded chains only through `tight` -- the
+// billboard's full lists -- and selects the blend's kernel, which is launched directly after
+// them: frames of different shadings and equal lists share their graphs.
 struct GraphKey {
     uint64_t ws_gen;
     int64_t cap, P;
@@ -323,6 +326,7 @@ struct Frame {
     bool wide_local;    // the MSD local sort's 8192-slot form (crowded buckets lately)
     GsrPreprocessArgs pa;
     bool tight;  // tight binning: pairs only over the span words (needs the column-first form)
+    int shading = GSR_SHADE_SPLAT;  // gsr_forward_shaded: the kernel of stage 7
     uint64_t K = 0;   // upstream's num_rendered
     uint64_t KL = 0;  // pairs in the list (K, or fewer with tight binning)
     // the pair list the blend reads and gsr_get_binning exports
@@ -344,7 +348,7 @@ int stage_end(gsr_context *ctx, const Frame &f, int i) {
 // Arguments -> Frame (upstream's argument checks and messages, rasterize_points.cu /
 // __init__.py), workspace for P.
 int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                gsr_outputs *out, hipStream_t s, Frame &f) {
+                gsr_outputs *out, hipStream_t s, int shading, Frame &f) {
     const int64_t P = g->P;
     const int W = st->image_width, H = st->image_height;
     if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, "gsr_forward: bad P");
@@ -377,6 +381,7 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
         return fail(GSR_E_INVALID, "gsr_forward: conic_opacity output must be 16-B aligned");
 
     f.s = s;
+    f.shading = shading;
     f.P = P;
     f.W = W;
     f.H = H;
@@ -476,7 +481,14 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     // frames only: on a strip the replicated preprocess writes a 16-B record for every Gaussian
     // to shorten one strip's lists (C4 3/8 strip: preprocess 97 -> 141 us, row pass 52 -> 42 us;
     // C3 3/8 strip 0.150 -> 0.157 ms per frame; DESIGN.md decision 11)
-    f.tight = ctx->tight && f.colpairs && !out->n_contrib && f.rows_tiles == f.gy;
+    // Never under the billboard shading: its quads reach beyond the alpha >= 1/255 ellipse the
+    // span words are cut to (they stay inside upstream's rect: radius = ceil(3 sqrt(lambda_max))
+    // >= 3 sqrt(max(cxx, cyy))), so it reads upstream's lists.  The other prunings hold for it
+    // as they are: the blend's quadrant cull has its own box test (blend.hip k_shade_q), and the
+    // strip ranks' footprint skip (preprocess.hip strip_reach) bounds upstream's rect, not the
+    // ellipse, and reads no opacity.
+    f.tight = ctx->tight && f.colpairs && !out->n_contrib && f.rows_tiles == f.gy &&
+              shading != GSR_SHADE_BILLBOARD;
     pa.strip_rc = f.tight ? static_cast<uint4 *>(ctx->strip_rc.p) : nullptr;
     pa.block_pairs = static_cast<uint64_t *>(ctx->pair_count.p);
     pa.host_K = ctx->d_hostK;
@@ -774,6 +786,10 @@ int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st
     if (f.graph) {  // the list length is on the device: a list over the capacity is not blended
         ba.list_n = static_cast<const uint32_t *>(ctx->frame_words.p) + 1;
         ba.list_cap = (uint32_t)ctx->list_cap;
+    }
+    if (f.shading != GSR_SHADE_SPLAT) {  // a GL shading's first-hit kernel instead
+        GSR_HIP(gsr_launch_shade(ba, f.shading, f.s), "shade launch");
+        return GSR_OK;
     }
     GSR_HIP(gsr_launch_blend(ba, f.s), "blend launch");
     return GSR_OK;
@@ -1083,10 +1099,10 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 }
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-            gsr_outputs *out, hipStream_t s) {
+            gsr_outputs *out, hipStream_t s, int shading) {
     Frame f;
     ctx->have_forward = false;
-    GSR_TRY(setup_frame(ctx, g, st, out, s, f));
+    GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
@@ -1106,7 +1122,7 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         ++ctx->graph_overflows;
         ctx->list_cap = list_capacity((int64_t)f.KL, ctx->list_cap);
         GSR_TRY(reserve_K(ctx, ctx->list_cap, s));
-        GSR_TRY(setup_frame(ctx, g, st, out, s, f));
+        GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
         f.graph = false;
     }
 
@@ -1375,12 +1391,20 @@ int gsr_stage_times(gsr_context *ctx, float *ms, int n) {
     return kAllStages;
 }
 
-int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                gsr_outputs *out, void *stream) {
+int gsr_forward_shaded(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                       gsr_outputs *out, int32_t shading, void *stream) {
     if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    if (shading < GSR_SHADE_SPLAT || shading > GSR_SHADE_GAUSS_BALL)
+        return fail(GSR_E_INVALID, "gsr_forward_shaded: unknown shading " +
+                                       std::to_string(shading) + " (GSR_SHADE_* 0..3)");
     std::lock_guard<std::mutex> lock(ctx->mu);
     GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream));
+    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), shading);
+}
+
+int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                gsr_outputs *out, void *stream) {
+    return gsr_forward_shaded(ctx, g, st, out, GSR_SHADE_SPLAT, stream);
 }
 
 int gsr_get_binning(gsr_context *ctx, uint32_t *point_list, uint32_t *point_tiles,

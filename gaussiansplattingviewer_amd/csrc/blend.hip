@@ -368,7 +368,157 @@ inline uint32_t xcd_grid(uint32_t n_tiles) {
     return (n_tiles + g - 1) / g * g;
 }
 
+// ---- the GL backend's geometry shadings (gsr_forward_shaded, include/gsr.h) -------------------
+// shaders/gau_frag.glsl:15-38 on the rasterizer's lists: a pixel takes the colour of the first
+// entry of its tile's list that hits it -- nothing is composited.  An entry hits
+//   billboard (1):        |dx| <= 3 sqrt(cxx) and |dy| <= 3 sqrt(cyy), the axis-aligned quad of
+//                         gau_vert.glsl:174 (cxx = c / det, cyy = a / det, det = a c - b^2: the 2D
+//                         covariance with its 0.3); the opacity plays no part;
+//   the ball modes (2, 3): power <= 0 and alpha = min(0.99, o exp(power)) > 0.22, tested without
+//                         a transcendental per pixel as power > ln(0.22 / o) (0.99 > 0.22),
+// with upstream's dx = mx - x, dy = my - y, power = -1/2 (a dx^2 + c dy^2) - b dx dy in upstream's
+// operation order.  One arithmetic (GSR_OPT_BLEND_FAST does not apply).  The colour is the
+// record's rgb, bit for bit (1, 2), or rgb exp(power) (3: the one exp of a pixel, at its hit).
+//
+// The staged splat, 40 B of LDS: g = {mx, my, ex, ey} (billboard) or {mx, my, a, b} (ball);
+// q = {c, threshold, r, g} (billboard: -, -, r, g); e = {b, list position + 1 (uint bits)}.
+//
+// What is dropped before the scan can never hit, so the cull changes no bit (tested):
+//   ball: an opacity not above 0.22f -- the threshold ln(0.22f / o) is then >= 0 while a hit
+//     needs power <= 0 -- and, with GSR_OPT_BLEND_CULL, may_touch: alpha > 0.22 lies inside the
+//     alpha >= 1/255 region it bounds;
+//   billboard: a NaN extent, and with the cull a quad whose box misses the quadrant's pixel-centre
+//     box.  The box test is the per-pixel test itself at the nearest column / row: fl(mx - x) is
+//     monotone in x, so if the quadrant's nearest pixel fails, all fail.
+constexpr int kShadeBillboard = 1, kShadeFlatBall = 2, kShadeGaussBall = 3;
+
+template <int kMode>
+__global__ __launch_bounds__(256, 8) void k_shade_q(const GsrBlendArgs a, uint32_t n_tiles) {
+    constexpr bool kBill = kMode == kShadeBillboard;
+    __shared__ float4 s_g_q[4][64], s_q_q[4][64];  // per quadrant wave
+    __shared__ float2 s_e_q[4][64];
+
+    const uint32_t tile = xcd_tile(blockIdx.x, a.order, (n_tiles + kGroupTiles - 1) / kGroupTiles);
+    if (tile >= n_tiles) return;
+    if (a.list_n && *a.list_n > a.list_cap) return;  // not binned (frame graphs: re-rendered)
+    const uint32_t quad = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    float4 *const s_g = s_g_q[quad], *const s_q = s_q_q[quad];
+    float2 *const s_e = s_e_q[quad];
+    const uint32_t tx = tile % a.grid_x, ty = a.row_begin + tile / a.grid_x;
+    const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
+    const int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
+    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
+    const bool inside = px < a.W && py < a.H;
+    const float pfx = (float)px, pfy = (float)py;
+    const float X0 = (float)qx0, Y0 = (float)qy0;
+
+    const uint2 range = a.ranges[tile];
+    bool done = !inside;  // hit, or outside the frame
+    float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, hit_power = 0.0f;
+    uint32_t hit_pos = 0;  // list position + 1 of the hit
+    if (__ballot(!done) == 0ull) return;
+
+    const uint32_t i0 = range.x + (uint32_t)lane;
+    uint32_t id_next = i0 < range.y ? (a.point_list[i0] & a.id_mask) : 0u;
+    for (uint32_t start = range.x; start < range.y; start += 64) {
+        const uint32_t idx = start + (uint32_t)lane;
+        const bool valid = idx < range.y;
+        SplatRecord r;
+        if (valid) r = a.records[id_next];
+        if (idx + 64u < range.y) id_next = (a.point_list[idx + 64u] & a.id_mask);
+
+        bool keep = valid;
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f), q = g;
+        if (valid) {
+            if (kBill) {
+                // the determinant in double: a c ~ b^2 for elongated splats would cancel in float
+                const float det = (float)((double)r.a.z * (double)r.b.x - (double)r.a.w * (double)r.a.w);
+                const float ex = 3.0f * sqrtf(r.b.x / det), ey = 3.0f * sqrtf(r.a.z / det);
+                keep = ex == ex && ey == ey;
+                if (keep && a.cull) {
+                    const float ulo = X0 - r.a.x, uhi = r.a.x - (X0 + 7.0f);
+                    const float vlo = Y0 - r.a.y, vhi = r.a.y - (Y0 + 7.0f);
+                    keep = !(ulo > 0.0f && ulo > ex) && !(uhi > 0.0f && uhi > ex) &&
+                           !(vlo > 0.0f && vlo > ey) && !(vhi > 0.0f && vhi > ey);
+                }
+                g = make_float4(r.a.x, r.a.y, ex, ey);
+                q = make_float4(0.0f, 0.0f, r.c.y, r.c.z);
+            } else {
+                keep = r.b.y > 0.22f;
+                if (keep && a.cull)
+                    keep = may_touch(r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.z, r.b.w, 2.0f * r.c.x,
+                                     X0, X0 + 7, Y0, Y0 + 7);
+                g = r.a;
+                q = make_float4(r.b.x, logf(0.22f / r.b.y), r.c.y, r.c.z);
+            }
+        }
+        const uint64_t bal = __ballot(keep);
+        if (keep) {
+            const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+            const int slot = __popcll(bal & lt);  // compacted in list order
+            s_g[slot] = g;
+            s_q[slot] = q;
+            s_e[slot] = make_float2(r.c.w, __uint_as_float(idx - range.x + 1u));
+        }
+        const int count = __popcll(bal);
+        // one wave: its LDS writes above complete before the reads below are served
+        for (int k = 0; k < count; ++k) {
+            const float4 sg = s_g[k], sq = s_q[k];
+            const float2 se = s_e[k];
+            const float dx = sg.x - pfx, dy = sg.y - pfy;
+            bool hit;
+            float power = 0.0f;
+            if (kBill) {
+                hit = fabsf(dx) <= sg.z && fabsf(dy) <= sg.w;
+            } else {
+                power = -0.5f * (sg.z * dx * dx + sq.x * dy * dy) - sg.w * dx * dy;
+                hit = !(power > 0.0f) && power > sq.y;
+            }
+            hit = hit && !done;
+            C0 = hit ? sq.z : C0;
+            C1 = hit ? sq.w : C1;
+            C2 = hit ? se.x : C2;
+            hit_pos = hit ? __float_as_uint(se.y) : hit_pos;
+            if (kMode == kShadeGaussBall) hit_power = hit ? power : hit_power;
+            done = done || hit;
+            if ((k & 3) == 3 && __ballot(!done) == 0ull) break;
+        }
+        if (__ballot(!done) == 0ull) break;
+    }
+
+    if (inside) {
+        const size_t pid = (size_t)(py - a.y0) * a.W + px;
+        const size_t plane = (size_t)a.rows_out * a.W;
+        const bool hit = hit_pos != 0u;
+        if (kMode == kShadeGaussBall) {
+            const float e = exp_core(hit_power);
+            C0 *= e, C1 *= e, C2 *= e;
+        }
+        if (a.final_T) a.final_T[pid] = hit ? 0.0f : 1.0f;
+        if (a.n_contrib) a.n_contrib[pid] = hit_pos;
+        a.out_color[pid] = hit ? C0 : a.bg[0];
+        a.out_color[plane + pid] = hit ? C1 : a.bg[1];
+        a.out_color[2 * plane + pid] = hit ? C2 : a.bg[2];
+    }
+}
+
 }  // namespace
+
+hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s) {
+    if (a.rows_tiles == 0 || a.grid_x == 0) return hipSuccess;
+    const uint32_t n_tiles = a.grid_x * a.rows_tiles;
+    const dim3 grid(xcd_grid(n_tiles));
+    if (shading == kShadeBillboard)
+        hipLaunchKernelGGL((k_shade_q<kShadeBillboard>), grid, dim3(256), 0, s, a, n_tiles);
+    else if (shading == kShadeFlatBall)
+        hipLaunchKernelGGL((k_shade_q<kShadeFlatBall>), grid, dim3(256), 0, s, a, n_tiles);
+    else if (shading == kShadeGaussBall)
+        hipLaunchKernelGGL((k_shade_q<kShadeGaussBall>), grid, dim3(256), 0, s, a, n_tiles);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 
 uint32_t gsr_blend_order_groups(uint32_t n_tiles) {
     return (n_tiles + kGroupTiles - 1) / kGroupTiles;

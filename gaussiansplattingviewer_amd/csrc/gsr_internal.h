@@ -505,6 +505,9 @@ struct GsrBlendArgs {
     uint32_t list_cap;
 };
 hipError_t gsr_launch_blend(const GsrBlendArgs &a, hipStream_t s);
+// The GL backend's geometry shadings in place of the composite (blend.hip k_shade_q): shading =
+// GSR_SHADE_BILLBOARD / FLAT_BALL / GAUSS_BALL.  Same arguments; a.fast is not read.
+hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);
 // The blend's dispatch order: the groups of 4 row-adjacent tiles (16 quadrant waves, one XCD)
 // by descending pair count, so the last waves to start are the short ones.
 uint32_t gsr_blend_order_groups(uint32_t n_tiles);

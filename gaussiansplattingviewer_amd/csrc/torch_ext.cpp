@@ -12,6 +12,8 @@
 //     (renderer_cuda.py:211-224) through _RasterizeGaussians.  The three buffers hold upstream's
 //     backward state; the forward-only viewer (renderer_cuda.py:214, torch.no_grad) never reads
 //     them, and here they are empty.
+//   _C.rasterize_gaussians_shaded(<the same 19 arguments>, shading) -> the same 6-tuple
+//     this package's own: the forward under a GL shading (gsr_forward_shaded, GSR_SHADE_*).
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -58,15 +60,17 @@ const float *opt_ptr(const torch::Tensor &t, const torch::Device &dev, const cha
     return c.data_ptr<float>();
 }
 
-std::tuple<int64_t, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
-rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3D,
-                    const torch::Tensor &colors, const torch::Tensor &opacity,
-                    const torch::Tensor &scales, const torch::Tensor &rotations,
-                    double scale_modifier, const torch::Tensor &cov3D_precomp,
-                    const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix,
-                    double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width,
-                    const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
-                    bool prefiltered, bool debug) {
+using Forward6 =
+    std::tuple<int64_t, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+
+// upstream's 19 arguments and the shading (GSR_SHADE_*, gsr_forward_shaded)
+Forward6 rasterize_gaussians_shaded(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
+    int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
+    bool prefiltered, bool debug, int64_t shading) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -119,12 +123,26 @@ rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3
         int rc;
         {  // the forward waits for K (pinned memory): other Python threads may run meanwhile
             pybind11::gil_scoped_release no_gil;
-            rc = gsr_forward(ctx, &g, &st, &out, s);
+            rc = gsr_forward_shaded(ctx, &g, &st, &out, (int32_t)shading, s);
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_forward failed (", rc, "): ", gsr_last_error());
         num_rendered = out.num_rendered;
     }
     return std::make_tuple(num_rendered, color, radii, geom, binning, img);
+}
+
+Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3D,
+                             const torch::Tensor &colors, const torch::Tensor &opacity,
+                             const torch::Tensor &scales, const torch::Tensor &rotations,
+                             double scale_modifier, const torch::Tensor &cov3D_precomp,
+                             const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix,
+                             double tan_fovx, double tan_fovy, int64_t image_height,
+                             int64_t image_width, const torch::Tensor &sh, int64_t degree,
+                             const torch::Tensor &campos, bool prefiltered, bool debug) {
+    return rasterize_gaussians_shaded(background, means3D, colors, opacity, scales, rotations,
+                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                      tan_fovx, tan_fovy, image_height, image_width, sh, degree,
+                                      campos, prefiltered, debug, GSR_SHADE_SPLAT);
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -163,6 +181,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians", &rasterize_gaussians,
           "upstream RasterizeGaussiansCUDA: (num_rendered, color, radii, geomBuffer, "
           "binningBuffer, imgBuffer)");
+    m.def("rasterize_gaussians_shaded", &rasterize_gaussians_shaded,
+          "rasterize_gaussians under a GL shading: its 19 arguments, then GSR_SHADE_* (0 splat, "
+          "1 billboard, 2 flat ball, 3 gaussian ball)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -35,6 +35,9 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+    # not upstream's: one of _lib.GSR_SHADE_* (the GL backend's billboard / ball shadings,
+    # include/gsr.h gsr_forward_shaded); last and defaulted, so upstream's constructions hold
+    shading: int = 0
 
 
 def _device_of(t: torch.Tensor) -> torch.device:
@@ -69,7 +72,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                                scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx,
                                tanfovy, image_height, image_width, sh, degree, campos, prefiltered,
                                debug, *, tile_rows=None, extras=(), stream=None, slot=0,
-                               out_color=None, radii=True) -> ForwardResult:
+                               out_color=None, radii=True, shading=0) -> ForwardResult:
     """Same arguments, order and validation as upstream `_C.rasterize_gaussians`.
 
     Extensions (keyword-only, for the strip partition and the parity tests):
@@ -81,7 +84,9 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
       out_color -- preallocated contiguous f32 (3, rows, W) output (e.g. a gather buffer);
       radii     -- False (strips only, no per-Gaussian extras): no radii output
                    (ForwardResult.radii is None); Gaussians whose footprint bound misses the
-                   strip skip the per-Gaussian work (a multi-GPU strip rank needs its image only).
+                   strip skip the per-Gaussian work (a multi-GPU strip rank needs its image only);
+      shading   -- _lib.GSR_SHADE_*: 0 the splat composite, 1 billboard, 2 flat ball, 3 gaussian
+                   ball (the GL backend's shadings, gsr_forward_shaded in include/gsr.h).
     """
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -167,8 +172,13 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     with torch.cuda.device(dev_index):
-        _lib.check(lib.gsr_forward(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
-                                   ctypes.c_void_p(stream)), "gsr_forward")
+        if shading == _lib.GSR_SHADE_SPLAT:
+            _lib.check(lib.gsr_forward(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
+                                       ctypes.c_void_p(stream)), "gsr_forward")
+        else:
+            _lib.check(lib.gsr_forward_shaded(ctx, ctypes.byref(g), ctypes.byref(st),
+                                              ctypes.byref(out), int(shading),
+                                              ctypes.c_void_p(stream)), "gsr_forward_shaded")
     return ForwardResult(int(out.num_rendered), color, radii, ext)
 
 
@@ -221,10 +231,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         # forward that raises leaves them in SNAPSHOT_FILE for replay_snapshot()
         cpu_args = _cpu_copy(args) if rs.debug else None
         try:
-            if _lib._native_shares_library():
+            if not _lib._native_shares_library():
+                # GSR_LIB (an A/B build): `_C` links the in-tree library, so render by ctypes
+                num_rendered, color, radii, _ = rasterize_gaussians_native(*args,
+                                                                           shading=rs.shading)
+            elif rs.shading:  # upstream's 19 arguments and the shading
+                num_rendered, color, radii, geom, binning, img = \
+                    _C.rasterize_gaussians_shaded(*args, int(rs.shading))
+            else:
                 num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(*args)
-            else:  # GSR_LIB (an A/B build): `_C` links the in-tree library, so render by ctypes
-                num_rendered, color, radii, _ = rasterize_gaussians_native(*args)
         except Exception:
             if cpu_args is not None:
                 torch.save(cpu_args, SNAPSHOT_FILE)

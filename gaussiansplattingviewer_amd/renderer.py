@@ -84,8 +84,13 @@ def gaus_hip_from_cpu(gau, device="cuda") -> GaussianDataHIP:
 class HIPRenderer(GaussianRenderBase):
     """CUDARenderer's behaviour on the MI355X rasterizer (no GL)."""
 
-    def __init__(self, w, h, device="cuda", tile_rows=None):
+    # GL render_mod -> gsr_forward_shaded's shading (gau_frag.glsl:15-38)
+    GL_SHADINGS = {-2: _lib.GSR_SHADE_BILLBOARD, -3: _lib.GSR_SHADE_FLAT_BALL,
+                   -4: _lib.GSR_SHADE_GAUSS_BALL}
+
+    def __init__(self, w, h, device="cuda", tile_rows=None, gl_shading=False):
         super().__init__()
+        self.gl_shading = bool(gl_shading)  # render the GL backend's ball / billboard modes
         self.device = torch.device(device)
         self.raster_settings = {
             "image_height": int(h),
@@ -128,9 +133,12 @@ class HIPRenderer(GaussianRenderBase):
         mod >= 0 caps the SH degree at mod ("SH:0~k", gau_vert.glsl:217-247) and mod == -1
         renders the disparity image (per-Gaussian disparity grey, Gaussians scaled by 1.2,
         gau_vert.glsl:152-156, 182-207).  The ball / billboard modes (-2, -3, -4) render as the
-        default mode, as in the CUDA backend, with a one-time warning."""
+        default mode, as in the CUDA backend, with a one-time warning -- unless the renderer was
+        constructed with gl_shading=True: then -2 / -3 / -4 render the billboard / flat ball /
+        gaussian ball shading of gau_frag.glsl:15-38 (gsr_forward_shaded) at SH degree 0 (GL adds
+        the higher bands only for render_mod >= 1, gau_vert.glsl:219)."""
         mod = int(mod)
-        if mod < -1 and not self._warned_mod:
+        if mod < -1 and not self._warned_mod and not (self.gl_shading and mod in self.GL_SHADINGS):
             import warnings
             warnings.warn(f"render mode {mod} (ball / billboard shading) is GL-only; "
                           "rendering the default SH colours", stacklevel=2)
@@ -184,6 +192,9 @@ class HIPRenderer(GaussianRenderBase):
             settings["scale_modifier"] = settings["scale_modifier"] * DISPARITY_SCALE
         elif self.render_mod >= 0:
             settings["sh_degree"] = min(settings["sh_degree"], self.render_mod)
+        elif self.gl_shading and self.render_mod in self.GL_SHADINGS:
+            settings["shading"] = self.GL_SHADINGS[self.render_mod]
+            settings["sh_degree"] = 0
         rs = GaussianRasterizationSettings(**settings)
         with torch.no_grad():
             if self.tile_rows is None:
@@ -195,7 +206,7 @@ class HIPRenderer(GaussianRenderBase):
                     rs.bg, g.xyz, colors, g.opacity, g.scale, g.rot, rs.scale_modifier, None,
                     rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
                     rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug,
-                    tile_rows=self.tile_rows)
+                    tile_rows=self.tile_rows, shading=rs.shading)
                 img, radii = res.color, res.radii
         self.image, self.radii = img, radii
         return img

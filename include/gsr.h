@@ -49,8 +49,9 @@ extern "C" {
 /* 2 (round 4): option ids renumbered (GSR_OPT_COLUMN_PAIRS retired, tight binning moved to 13,
  * ids 10 and 12 reserved), GSR_OPT_DEPTH_SORT (id 11, was COMPACT_SORT) gains the MSD form,
  * gsr_get_binning exports tight lists.
- * 3 (round 6): gsr_get_option; contexts are serialised by a mutex and ordered across streams. */
-#define GSR_ABI_VERSION 3
+ * 3 (round 6): gsr_get_option; contexts are serialised by a mutex and ordered across streams.
+ * 4: gsr_forward_shaded and the GSR_SHADE_* ids (additive). */
+#define GSR_ABI_VERSION 4
 
 enum {
     GSR_OK = 0,
@@ -129,6 +130,35 @@ int gsr_reserve(gsr_context *ctx, int64_t P, int64_t K);
  * tile binning (scan + duplicate + radix tile sort + ranges) -> per-tile blend. */
 int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                 gsr_outputs *out, void *stream);
+
+/* gsr_forward with one of the GL backend's shadings (the viewer's "shading" combo, main.py:98;
+ * the fragment rule of shaders/gau_frag.glsl:15-38) on the rasterizer's geometry: preprocess,
+ * culls, rects, lists and the pixel-centre convention are gsr_forward's, only the per-tile stage
+ * differs.  GSR_SHADE_SPLAT is gsr_forward itself.  Under the others a pixel takes the colour of
+ * the FIRST entry of its tile's list (depth order) that hits it, nothing is composited; with
+ * dx = mx - x, dy = my - y, power = -(a dx^2 + c dy^2) / 2 - b dx dy and
+ * alpha = min(0.99, o exp(power)) an entry hits when
+ *   GSR_SHADE_BILLBOARD  (GL render_mod -2): |dx| <= 3 sqrt(cxx) and |dy| <= 3 sqrt(cyy), with
+ *     cxx = c / (a c - b^2), cyy = a / (a c - b^2) -- the axis-aligned +-3 sigma quad
+ *     (quadwh_scr, gau_vert.glsl:174) of the 2D covariance with its 0.3.  The opacity is not
+ *     read (gau_frag.glsl:15-19 returns before any discard); a NaN extent never hits;
+ *   GSR_SHADE_FLAT_BALL  (GL -3, the combo's "Gaussian Ball"): power <= 0 and alpha > 0.22;
+ *   GSR_SHADE_GAUSS_BALL (GL -4): as FLAT_BALL,
+ * and the pixel is the entry's rgb (BILLBOARD, FLAT_BALL: the record's bits, no arithmetic) or
+ * rgb * exp(power) (GAUSS_BALL).  At a hit at list position k: final_T = 0, n_contrib = k + 1;
+ * without one: the pixel is bg (its bits), final_T = 1, n_contrib = 0.  GL draws back to front
+ * with alpha in {0, 1}, which is the same image.
+ * Lists: the billboard quad reaches beyond the alpha >= 1/255 ellipse but stays inside upstream's
+ * rect, so a BILLBOARD frame always bins upstream's lists (GSR_OPT_TIGHT_BINNING is ignored for
+ * it); the ball shadings keep tight lists under gsr_forward's conditions.  GSR_OPT_BLEND_CULL
+ * gives identical bits either way; GSR_OPT_BLEND_FAST does not apply (one arithmetic).  The
+ * shading kernel is timed as the "blend" stage.  `shading` is an argument of the call, not a
+ * context option: a shared context carries no renderer's mode into another's frame.  Any other
+ * value: GSR_E_INVALID. */
+enum { GSR_SHADE_SPLAT = 0, GSR_SHADE_BILLBOARD = 1, GSR_SHADE_FLAT_BALL = 2,
+       GSR_SHADE_GAUSS_BALL = 3 };
+int gsr_forward_shaded(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                       gsr_outputs *out, int32_t shading, void *stream);
 
 /* Binning state of the last gsr_forward on this context: the pair lists its blend read.  Writes
  * the sizes (list_entries = K, the entries of the lists; num_tiles = T, tiles of the whole
