@@ -54,9 +54,16 @@ int fail(int code, const std::string &msg) {
         if (rc_ != GSR_OK) return rc_; \
     } while (0)
 
+// A grow-only device buffer (grow) ...
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+};
+// ... of T, which enters itself in its context's list of buffers (gsr_destroy frees that list).
+template <typename T>
+struct Buf : DevBuf {
+    explicit Buf(std::vector<DevBuf *> &all) { all.push_back(this); }
+    T *get() const { return static_cast<T *>(p); }
 };
 
 constexpr int kStages = 7;        // the chain on the caller's stream
@@ -135,42 +142,54 @@ struct gsr_context {
     // waits for the device (the workspace is stream-ordered on one stream at a time).
     hipStream_t ws_stream = nullptr;
     bool ws_stream_set = false;
-    // per-Gaussian workspace
-    DevBuf records, strip_rect, sort_keys, partials, total, hist, digit_total, bin, chunk_first,
-        rect_sorted, pair_count;
-    DevBuf strip_rc, rc_sorted;  // tight binning: {rect, span word}, by id and in depth order
-    DevBuf ds_a, ds_b;   // depth sort: (key, id) pairs between passes (ping-pong)
-    DevBuf block_kept;   // depth sort compaction (strips): kept keys per 256-Gaussian block
-    DevBuf color_ids;    // compacted strips: the kept ids the colour pass walks (4 B x P)
-    DevBuf perm;         // the depth sort's result: Gaussian ids in depth order (kept ones)
-    DevBuf ds_ctl;       // depth sort control words: kept count, key bits, per-tile key stats
-    DevBuf col_hist;     // column-first binning: per-(Gaussian block, column) pair counts
+    // The workspace: every device buffer is declared once, here, with its element type, and
+    // enters itself in `bufs`.  Per-Gaussian workspace:
+    std::vector<DevBuf *> bufs;
+    Buf<gsr::SplatRecord> records{bufs};
+    Buf<uint2> strip_rect{bufs}, rect_sorted{bufs};
+    Buf<uint32_t> sort_keys{bufs}, partials{bufs}, hist{bufs}, digit_total{bufs};
+    Buf<uint64_t> total{bufs}, pair_count{bufs};
+    Buf<uint4> bin{bufs};
+    Buf<uint32_t> chunk_first{bufs};
+    // tight binning: {rect, span word}, by id and in depth order
+    Buf<uint4> strip_rc{bufs}, rc_sorted{bufs};
+    // depth sort: (key, id) pairs between passes (ping-pong); ds_b also as words, the compacted
+    // keys and from word P their ids
+    Buf<uint2> ds_a{bufs}, ds_b{bufs};
+    uint32_t *ds_b_words() const { return reinterpret_cast<uint32_t *>(ds_b.get()); }
+    Buf<uint32_t> block_kept{bufs};  // depth sort compaction (strips): kept keys per 256-key block
+    Buf<uint32_t> color_ids{bufs};   // compacted strips: the kept ids the colour pass walks
+    Buf<uint32_t> perm{bufs};        // the depth sort's result: kept Gaussian ids in depth order
+    Buf<uint32_t> ds_ctl{bufs};      // depth sort control: kept count, key bits, per-tile key stats
+    Buf<uint32_t> col_hist{bufs};    // column-first binning: per-(Gaussian block, column) counts
     // per-pair workspace
-    DevBuf tile_keys, tile_vals, tile_keys_alt, tile_vals_alt;
-    DevBuf ranges_local;
-    DevBuf tile_diff;  // difference-array partials of the second-stream tile ranges
-    DevBuf blend_order;  // the blend's tile groups, heaviest first (second stream)
-    // pinned host words the GPU stores into: [0] -, [1] -, [2] K (k_publish_K), [3] its depth-key
-    // bits D, [4] (frame tag << 32) | D from the depth sort's pass 0, [5] the pair count over the
-    // spans (k_publish_K), [6] the bits of the kept depth keys' range (k_publish_K), [7] K's tag
-    uint64_t *h_total = nullptr;
-    unsigned long long *d_hostK = nullptr;  // device view of h_total + 2
-    unsigned long long *d_hostD = nullptr;  // device view of h_total + 4
-    unsigned long long *d_hostCrowd = nullptr;  // device view of h_total + 1
+    Buf<uint32_t> tile_keys{bufs}, tile_vals{bufs}, tile_keys_alt{bufs}, tile_vals_alt{bufs};
+    // the strip's tile ranges; also as words (the per-pair form's range kernel)
+    Buf<uint2> ranges_local{bufs};
+    uint32_t *ranges_words() const { return reinterpret_cast<uint32_t *>(ranges_local.get()); }
+    Buf<uint32_t> tile_diff{bufs};    // difference-array partials of the second-stream tile ranges
+    Buf<uint32_t> blend_order{bufs};  // the blend's tile groups, heaviest first (second stream)
+    // frame graphs (64 B, from gsr_create): [0] tag, [1] list length, [4..6] campos
+    Buf<uint32_t> frame_words{bufs};
+    uint32_t *list_n() const { return frame_words.get() + 1; }
+    // pinned host words the GPU stores into, and their device view
+    GsrHostWords *host_words = nullptr, *d_host_words = nullptr;
     uint32_t sort_tag = 0;                  // frames rendered on this context (the pinned tags)
     // the bits of the last frame's kept depth keys' range and the bits in which they differ
-    // (wait_K); the first frame, with no history, takes the LSD sort, which any spread of depths
+    // (read_K); the first frame, with no history, takes the LSD sort, which any spread of depths
     // suits
     uint32_t last_Dr = UINT32_MAX, last_D = UINT32_MAX;
     // state of the last forward (gsr_get_binning, gsr_tile_row_pairs)
-    bool have_forward = false;
-    int64_t last_K = 0;        // upstream's num_rendered
-    int64_t last_list = 0;     // pairs in the list (tight binning: fewer than last_K)
-    bool last_tight = false;
-    uint32_t last_gx = 0, last_gy = 0, last_rb = 0, last_re = 0;
-    uint32_t *last_point_list = nullptr, *last_tiles_local = nullptr;
-    bool last_packed = false;             // column pairs: packed words, no tile-key array
-    uint32_t last_id_mask = 0xFFFFFFFFu;  // packed word -> Gaussian id
+    struct LastFrame {
+        bool valid = false;  // a forward has completed since the last one began
+        int64_t K = 0;       // upstream's num_rendered
+        int64_t list = 0;    // pairs in the list (tight binning: fewer than K)
+        bool tight = false;
+        uint32_t gx = 0, gy = 0, rb = 0, re = 0;
+        uint32_t *point_list = nullptr, *tiles_local = nullptr;
+        bool packed = false;             // column pairs: packed words, no tile-key array
+        uint32_t id_mask = 0xFFFFFFFFu;  // packed word -> Gaussian id
+    } last;
     // options (include/gsr.h)
     int cull = 1;
     int fast = 1;
@@ -199,7 +218,6 @@ struct gsr_context {
     // replayed while the key matches; the binning is sized by a capacity instead of the host
     // waiting for K in mid-frame
     int graphs = 0;
-    DevBuf frame_words;                  // [0] tag, [1] list length, [4..6] campos
     uint32_t ws_gen = 0;                 // bumped by every (re)allocation of a workspace buffer
     int64_t list_cap = 0;                // pair-list capacity of the graphs (0: none yet)
     std::vector<GraphEntry> graph_cache;
@@ -293,7 +311,7 @@ int bits_for(uint64_t max_value) {  // bits needed to represent every value <= m
 // kSpinLimit.  A sleeping event wait adds wake-up jitter to every frame (and its record a host
 // call); the spin keeps one host core busy for the frame's first ~20-50 us.
 template <typename Pred>
-bool spin_on(const uint64_t *word, Pred pred, uint64_t &value) {
+bool spin_on(const unsigned long long *word, Pred pred, uint64_t &value) {
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0;; ++spin) {
         value = __atomic_load_n(word, __ATOMIC_ACQUIRE);
@@ -301,6 +319,10 @@ bool spin_on(const uint64_t *word, Pred pred, uint64_t &value) {
         if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > kSpinLimit)
             return false;
     }
+}
+
+uint64_t host_word(const unsigned long long &word) {  // (GsrHostWords, on the host)
+    return __atomic_load_n(&word, __ATOMIC_ACQUIRE);
 }
 
 // Everything one forward derives from its arguments, shared by the stage functions.
@@ -456,11 +478,11 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     pa.rot_vec4 = (g->rotations && (reinterpret_cast<uintptr_t>(g->rotations) & 15) == 0) ? 1 : 0;
     pa.radii = out->radii;
     pa.strip_skip = out->radii == nullptr ? 1 : 0;
-    pa.records = static_cast<gsr::SplatRecord *>(ctx->records.p);
-    pa.sort_keys = static_cast<uint32_t *>(ctx->sort_keys.p);
+    pa.records = ctx->records.get();
+    pa.sort_keys = ctx->sort_keys.get();
     f.compact_sort = ctx->depth_sort < 0 ? (f.rows_tiles < f.gy && P >= kCompactP)
                                          : ctx->depth_sort == 1 || ctx->depth_sort == 3;
-    pa.block_kept = f.compact_sort ? static_cast<uint32_t *>(ctx->block_kept.p) : nullptr;
+    pa.block_kept = f.compact_sort ? ctx->block_kept.get() : nullptr;
     // the MSD sort wants buckets of a few thousand keys: its 4096 buckets split the top 12 bits of
     // the kept keys' range (key - min), which balances them while the depths span a few float
     // exponents (Dr <= 25: C2, C3, C5 -- whose near Gaussians cross depth 2.0, D = 31 but Dr =
@@ -475,7 +497,7 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     // (compacted strips keep the second stream's publish: on the C4 1/8 strip the main-stream
     // publish let the tile counts and colour start earlier, beside the depth sort, 80 -> 134 us)
     f.main_publish = f.msd_sort && !f.compact_sort;
-    pa.strip_rect = static_cast<uint2 *>(ctx->strip_rect.p);
+    pa.strip_rect = ctx->strip_rect.get();
     // tight binning: the column-first form, and no n_contrib (upstream's n_contrib counts list
     // positions of the full 3-sigma pairs); span words only then (NULL: every rect full).  Full
     // frames only: on a strip the replicated preprocess writes a 16-B record for every Gaussian
@@ -489,9 +511,9 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     // ellipse, and reads no opacity.
     f.tight = ctx->tight && f.colpairs && !out->n_contrib && f.rows_tiles == f.gy &&
               shading != GSR_SHADE_BILLBOARD;
-    pa.strip_rc = f.tight ? static_cast<uint4 *>(ctx->strip_rc.p) : nullptr;
-    pa.block_pairs = static_cast<uint64_t *>(ctx->pair_count.p);
-    pa.host_K = ctx->d_hostK;
+    pa.strip_rc = f.tight ? ctx->strip_rc.get() : nullptr;
+    pa.block_pairs = ctx->pair_count.get();
+    pa.host_words = ctx->d_host_words;
     pa.depths = out->depths;
     pa.means2D = out->means2D;
     pa.conic_opacity = out->conic_opacity;
@@ -509,7 +531,7 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     // of 513-1024 keys crowding a group past 4096 LDS slots (the flag of the frame before this
     // one may not have landed yet: the form is only a speed choice)
     {
-        const uint32_t crowd = (uint32_t)__atomic_load_n(&ctx->h_total[1], __ATOMIC_ACQUIRE);
+        const uint32_t crowd = (uint32_t)host_word(ctx->host_words->crowd);
         f.wide_local = crowd != 0u && f.tag - crowd <= kCrowdFrames;
     }
     return GSR_OK;
@@ -517,23 +539,20 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
 
 // ---- 2. the stable depth sort of the Gaussians (depth_sort.hip), passes [p0, p1) ------------
 int launch_depth_sort(gsr_context *ctx, const Frame &f, int p0, int p1) {
-    uint32_t *hist = static_cast<uint32_t *>(ctx->hist.p);
-    uint32_t *digit_total = static_cast<uint32_t *>(ctx->digit_total.p);
-    uint32_t *ctl = static_cast<uint32_t *>(ctx->ds_ctl.p);
-    uint32_t *perm = static_cast<uint32_t *>(ctx->perm.p);
-    uint2 *ds_a = static_cast<uint2 *>(ctx->ds_a.p), *ds_b = static_cast<uint2 *>(ctx->ds_b.p);
+    uint32_t *hist = ctx->hist.get(), *digit_total = ctx->digit_total.get();
+    uint32_t *ctl = ctx->ds_ctl.get(), *perm = ctx->perm.get();
+    uint2 *ds_a = ctx->ds_a.get(), *ds_b = ctx->ds_b.get();
+    unsigned long long *host_D = &ctx->d_host_words->sort_D;
     hipError_t e;
     const int64_t nb = gsr_preprocess_blocks(f.P);  // (their key OR / AND words)
     const uint2 *keybits = reinterpret_cast<const uint2 *>(f.pa.block_pairs + nb);
     if (f.compact_sort) {
         // the compacted keys / ids live in ds_b until pass 1 (or the MSD pass) has read them
         if (f.msd_sort && p0 != 0) return GSR_OK;  // (no later passes)
-        uint32_t *keys_c = reinterpret_cast<uint32_t *>(ds_b), *ids_c = keys_c + f.P;
+        uint32_t *keys_c = ctx->ds_b_words(), *ids_c = keys_c + f.P;
         e = gsr_depth_sort_compacted(f.pa.sort_keys, f.P, f.pa.block_kept, keys_c, ids_c, ds_a,
-                                     ds_b, perm, hist, digit_total, ctl, p0, p1, f.s,
-                                     ctx->d_hostD, f.tag,
-                                     f.color_ids ? static_cast<uint32_t *>(ctx->color_ids.p)
-                                                 : nullptr,
+                                     ds_b, perm, hist, digit_total, ctl, p0, p1, f.s, host_D,
+                                     f.tag, f.color_ids ? ctx->color_ids.get() : nullptr,
                                      f.color_ids ? ctx->compacted : nullptr, f.msd_sort ? 1 : 0,
                                      f.msd_sort && !f.main_publish ? keybits : nullptr, nb);
     } else if (f.msd_sort) {
@@ -541,11 +560,12 @@ int launch_depth_sort(gsr_context *ctx, const Frame &f, int p0, int p1) {
         if (p0 != 0) return GSR_OK;  // (no later passes)
         e = gsr_depth_sort_msd(f.pa.sort_keys, f.P, f.main_publish ? nullptr : keybits, nb,
                                ds_a, ds_b, perm, hist, digit_total, ctl, f.s,
-                               f.graph ? nullptr : ctx->d_hostD, f.tag,
-                               f.graph ? nullptr : ctx->d_hostCrowd, f.graph ? 0 : f.wide_local);
+                               f.graph ? nullptr : host_D, f.tag,
+                               f.graph ? nullptr : &ctx->d_host_words->crowd,
+                               f.graph ? 0 : f.wide_local);
     } else {  // (frame graphs queue every pass; the host reads no D)
         e = gsr_depth_sort(f.pa.sort_keys, f.P, 1, ds_a, ds_b, perm, hist, digit_total, ctl, p0,
-                           p1, f.s, f.graph ? nullptr : ctx->d_hostD, f.tag);
+                           p1, f.s, f.graph ? nullptr : host_D, f.tag);
     }
     GSR_HIP(e, "depth sort launch");
     return GSR_OK;
@@ -579,20 +599,17 @@ int aux_chain(gsr_context *ctx, const Frame &f, hipStream_t as, const uint32_t *
     // (column pairs: the ranges, then the blend's heaviest-first order of the tile groups)
     if (f.colpairs) {
         GSR_HIP(gsr_launch_tile_ranges_aux(f.pa.strip_rect, f.pa.strip_rc, f.P, f.gx,
-                                           f.rows_tiles,
-                                           static_cast<uint32_t *>(ctx->tile_diff.p),
-                                           static_cast<uint2 *>(ctx->ranges_local.p), as),
+                                           f.rows_tiles, ctx->tile_diff.get(),
+                                           ctx->ranges_local.get(), as),
                 "tile ranges launch");
-        GSR_HIP(gsr_launch_blend_order(static_cast<const uint2 *>(ctx->ranges_local.p),
-                                       (uint32_t)f.T_strip,
-                                       static_cast<uint32_t *>(ctx->blend_order.p), as),
+        GSR_HIP(gsr_launch_blend_order(ctx->ranges_local.get(), (uint32_t)f.T_strip,
+                                       ctx->blend_order.get(), as),
                 "blend order launch");
     }
     const int color_waves = color_waves_of(f);
     if (f.color_ids) {
         GSR_HIP(hipStreamWaitEvent(as, ctx->compacted, 0), "hipStreamWaitEvent(compacted)");
-        GSR_HIP(gsr_launch_color_ids(f.pa, static_cast<const uint32_t *>(ctx->color_ids.p),
-                                     static_cast<const uint32_t *>(ctx->ds_ctl.p), color_waves,
+        GSR_HIP(gsr_launch_color_ids(f.pa, ctx->color_ids.get(), ctx->ds_ctl.get(), color_waves,
                                      as),
                 "color launch");
     } else {
@@ -615,24 +632,19 @@ int launch_second_stream(gsr_context *ctx, const Frame &f) {
 // ---- 3. the scan: per-column pair counts of the depth-sorted Gaussians (column pairs), or the
 // offsets scan over their strip tile counts (per-pair form) --------------------------------------
 int launch_scan(gsr_context *ctx, const Frame &f) {
-    const uint32_t *perm = static_cast<const uint32_t *>(ctx->perm.p);
-    const uint32_t *d_valid = static_cast<const uint32_t *>(ctx->ds_ctl.p);
-    uint2 *rect_sorted = static_cast<uint2 *>(ctx->rect_sorted.p);
+    const uint32_t *perm = ctx->perm.get(), *d_valid = ctx->ds_ctl.get();
+    uint2 *rect_sorted = ctx->rect_sorted.get();
     if (f.colpairs) {
         GSR_HIP(gsr_launch_col_pairs_count(perm, f.pa.strip_rect, f.pa.strip_rc, f.P, d_valid,
-                                           rect_sorted,
-                                           f.tight ? static_cast<uint4 *>(ctx->rc_sorted.p)
-                                                   : nullptr,
-                                           static_cast<uint32_t *>(ctx->col_hist.p),
-                                           static_cast<uint32_t *>(ctx->digit_total.p), f.s),
+                                           rect_sorted, f.tight ? ctx->rc_sorted.get() : nullptr,
+                                           ctx->col_hist.get(), ctx->digit_total.get(), f.s),
                 "column count launch");
     } else {
-        uint32_t *partials = static_cast<uint32_t *>(ctx->partials.p);
+        uint32_t *partials = ctx->partials.get();
         GSR_HIP(gsr_launch_scan_reduce(perm, f.pa.strip_rect, f.P, d_valid, partials,
                                        rect_sorted, f.s),
                 "scan launch");
-        GSR_HIP(gsr_launch_scan_partials(partials, gsr_scan_blocks(f.P),
-                                         static_cast<uint64_t *>(ctx->total.p), f.s),
+        GSR_HIP(gsr_launch_scan_partials(partials, gsr_scan_blocks(f.P), ctx->total.get(), f.s),
                 "scan launch");
     }
     return GSR_OK;
@@ -646,38 +658,48 @@ int64_t list_capacity(int64_t n, int64_t cap) {
     return std::min<int64_t>(c, (int64_t)UINT32_MAX - 4096);
 }
 
+// The frame's K, list length, D and Dr from the pinned words k_publish_K stores: the host spins
+// on the frame's tag and, past the spin limit, waits for the stream that publishes.
+hipStream_t publish_stream(const gsr_context *ctx, const Frame &f) {
+    return f.main_publish || !ctx->second_stream ? f.s : ctx->aux;
+}
+int read_K(gsr_context *ctx, Frame &f, hipStream_t publisher) {
+    const GsrHostWords *w = ctx->host_words;
+    uint64_t tagv = 0;
+    if (!spin_on(&w->K_tag, [&](uint64_t v) { return v == f.tag; }, tagv))
+        GSR_HIP(hipStreamSynchronize(publisher), "hipStreamSynchronize(pair count)");
+    f.K = host_word(w->K);
+    ctx->last_Dr = (uint32_t)host_word(w->Dr);
+    ctx->last_D = (uint32_t)host_word(w->D);
+    f.KL = f.tight ? host_word(w->K_spans) : f.K;
+    if (f.K > (uint64_t)UINT32_MAX - 4096)
+        return fail(GSR_E_INVALID, "gsr_forward: more than 2^32-4097 (Gaussian, tile) pairs");
+    return GSR_OK;
+}
+
 // K (the pair count, which sizes the binning) from k_publish_K on the second stream, published
 // in pinned memory ~20 us after the preprocess.  Debug mode also checks it against the depth
 // sort's own key bits and, in the per-pair form, against the offsets scan's total.
 int wait_K(gsr_context *ctx, Frame &f) {
-    uint64_t tagv = 0;
-    if (!spin_on(&ctx->h_total[7], [&](uint64_t v) { return v == f.tag; }, tagv))
-        GSR_HIP(hipStreamSynchronize(f.main_publish || !ctx->second_stream ? f.s : ctx->aux),
-                "hipStreamSynchronize(pair count)");
-    f.K = __atomic_load_n(&ctx->h_total[2], __ATOMIC_ACQUIRE);
-    ctx->last_Dr = (uint32_t)__atomic_load_n(&ctx->h_total[6], __ATOMIC_ACQUIRE);
-    ctx->last_D = (uint32_t)__atomic_load_n(&ctx->h_total[3], __ATOMIC_ACQUIRE);
-    f.KL = f.tight ? __atomic_load_n(&ctx->h_total[5], __ATOMIC_ACQUIRE) : f.K;
+    GSR_TRY(read_K(ctx, f, publish_stream(ctx, f)));
     if (f.dbg) {
         uint32_t ctl2[2];
         uint64_t scan_K[2] = {0, 0};
-        GSR_HIP(hipMemcpyAsync(ctl2, ctx->ds_ctl.p, 8, hipMemcpyDeviceToHost, f.s),
+        GSR_HIP(hipMemcpyAsync(ctl2, ctx->ds_ctl.get(), 8, hipMemcpyDeviceToHost, f.s),
                 "hipMemcpyAsync(ctl)");
         if (!f.colpairs)
-            GSR_HIP(hipMemcpyAsync(scan_K, ctx->total.p, 16, hipMemcpyDeviceToHost, f.s),
+            GSR_HIP(hipMemcpyAsync(scan_K, ctx->total.get(), 16, hipMemcpyDeviceToHost, f.s),
                     "hipMemcpyAsync(num_rendered)");
         GSR_HIP(hipStreamSynchronize(f.s), "hipStreamSynchronize(ctl)");
-        if (ctl2[1] != (uint32_t)ctx->h_total[3])
+        if (ctl2[1] != ctx->last_D)
             return fail(GSR_E_HIP, "gsr_forward: depth key bits mismatch (pair count " +
-                                       std::to_string(ctx->h_total[3]) + ", sort " +
+                                       std::to_string(ctx->last_D) + ", sort " +
                                        std::to_string(ctl2[1]) + ")");
         if (!f.colpairs && scan_K[0] != f.K)
             return fail(GSR_E_HIP, "gsr_forward: pair count mismatch (preprocess " +
                                        std::to_string(f.K) + ", scan " +
                                        std::to_string(scan_K[0]) + ")");
     }
-    if (f.K > (uint64_t)UINT32_MAX - 4096)
-        return fail(GSR_E_INVALID, "gsr_forward: more than 2^32-4097 (Gaussian, tile) pairs");
     // column-first frames also size the frame graphs' list capacity (before the binning, so
     // this frame's list is not reallocated under it)
     int64_t want = (int64_t)f.KL;
@@ -688,57 +710,58 @@ int wait_K(gsr_context *ctx, Frame &f) {
     return reserve_K(ctx, want, f.s);
 }
 
+// The packed pair word's Gaussian id bits (column-first binning: strip row << col_shift | id).
+uint32_t id_mask_of(int col_shift) {
+    return col_shift < 32 ? (1u << col_shift) - 1u : 0xFFFFFFFFu;
+}
+
+// ---- 4 + 5, column-first form: pass 1 by column on (Gaussian, column) segments, then pass 2 on
+// the packed words' row bits, keys only; on f.s, the list it ends in and its id mask into f.
+// n: the list's length, known to the host, or with list_n (deferred-K frames) the capacity the
+// list is binned into, its length stored to and read from that device word.
+int launch_col_binning(gsr_context *ctx, Frame &f, int64_t n, uint32_t *list_n) {
+    uint32_t *tv = ctx->tile_vals.get(), *tv_alt = ctx->tile_vals_alt.get();
+    if (n > 0)
+        GSR_HIP(gsr_launch_col_pairs_scatter(ctx->perm.get(), ctx->rect_sorted.get(),
+                                             f.tight ? ctx->rc_sorted.get() : nullptr, f.P,
+                                             ctx->ds_ctl.get(), ctx->col_hist.get(),
+                                             ctx->digit_total.get(), f.col_shift, tv_alt, f.s,
+                                             list_n ? (uint32_t)n : 0xFFFFFFFFu, list_n),
+                "column scatter launch");
+    std::swap(tv, tv_alt);
+    GSR_TRY(stage_end(ctx, f, 3));
+    if (n > 0 && f.col_shift < 32)  // (hist: after reserve_K)
+        GSR_HIP(gsr_radix_sort_keys(&tv, &tv_alt, n, f.col_shift, 32, ctx->hist.get(),
+                                    ctx->digit_total.get(), f.s, list_n),
+                "tile sort launch");
+    GSR_TRY(stage_end(ctx, f, 4));
+    f.point_list = tv;
+    f.tiles_local = nullptr;
+    f.id_mask = id_mask_of(f.col_shift);
+    return GSR_OK;
+}
+
 // ---- 4 + 5. the pairs, stably sorted by strip tile ------------------------------------------
 int launch_binning(gsr_context *ctx, Frame &f) {
-    const uint32_t *perm = static_cast<const uint32_t *>(ctx->perm.p);
-    const uint32_t *d_valid = static_cast<const uint32_t *>(ctx->ds_ctl.p);
-    const uint2 *rect_sorted = static_cast<const uint2 *>(ctx->rect_sorted.p);
-    uint32_t *hist = static_cast<uint32_t *>(ctx->hist.p);  // (after reserve_K)
-    uint32_t *digit_total = static_cast<uint32_t *>(ctx->digit_total.p);
-    uint32_t *tk = static_cast<uint32_t *>(ctx->tile_keys.p);
-    uint32_t *tv = static_cast<uint32_t *>(ctx->tile_vals.p);
-    uint32_t *tk_alt = static_cast<uint32_t *>(ctx->tile_keys_alt.p);
-    uint32_t *tv_alt = static_cast<uint32_t *>(ctx->tile_vals_alt.p);
     const int64_t K = (int64_t)f.KL;
-    if (f.colpairs) {
-        // pass 1 by column on (Gaussian, column) segments, then pass 2 on the packed words'
-        // row bits, keys only
-        if (K > 0)
-            GSR_HIP(gsr_launch_col_pairs_scatter(perm, rect_sorted,
-                                                 f.tight ? static_cast<const uint4 *>(ctx->rc_sorted.p)
-                                                         : nullptr,
-                                                 f.P, d_valid,
-                                                 static_cast<const uint32_t *>(ctx->col_hist.p),
-                                                 digit_total, f.col_shift, tv_alt, f.s),
-                    "column scatter launch");
-        std::swap(tv, tv_alt);
-        GSR_TRY(stage_end(ctx, f, 3));
-        if (K > 0 && f.col_shift < 32)
-            GSR_HIP(gsr_radix_sort_keys(&tv, &tv_alt, K, f.col_shift, 32, hist, digit_total, f.s),
-                    "tile sort launch");
-        GSR_TRY(stage_end(ctx, f, 4));
-        f.point_list = tv;
-        f.tiles_local = nullptr;
-        f.id_mask = f.col_shift < 32 ? (1u << f.col_shift) - 1u : 0xFFFFFFFFu;
-        return GSR_OK;
-    }
+    if (f.colpairs) return launch_col_binning(ctx, f, K, nullptr);
+    const uint32_t *perm = ctx->perm.get(), *d_valid = ctx->ds_ctl.get();
+    uint32_t *hist = ctx->hist.get(), *digit_total = ctx->digit_total.get();  // (after reserve_K)
+    uint32_t *tk = ctx->tile_keys.get(), *tv = ctx->tile_vals.get();
+    uint32_t *tk_alt = ctx->tile_keys_alt.get(), *tv_alt = ctx->tile_vals_alt.get();
     // per-pair form: offsets, then the duplication fused with the first tile-sort pass (which
     // also zeroes the ranges), then the remaining passes and the ranges over the sorted keys
     const int tbits = f.T_strip > 1 ? bits_for(f.T_strip - 1) : 0;
     const GsrRadixPlan plan = gsr_radix_plan(0, tbits);
     if (K > 0) {
-        GSR_HIP(gsr_launch_scan_down(perm, rect_sorted,
-                                     static_cast<const uint32_t *>(ctx->partials.p), f.P, d_valid,
-                                     static_cast<const uint64_t *>(ctx->total.p),
-                                     static_cast<uint4 *>(ctx->bin.p),
-                                     static_cast<uint32_t *>(ctx->chunk_first.p), f.s),
+        GSR_HIP(gsr_launch_scan_down(perm, ctx->rect_sorted.get(), ctx->partials.get(), f.P,
+                                     d_valid, ctx->total.get(), ctx->bin.get(),
+                                     ctx->chunk_first.get(), f.s),
                 "scan_down launch");
-        GSR_HIP(gsr_launch_dup_sort_pass(static_cast<const uint4 *>(ctx->bin.p),
-                                         static_cast<const uint32_t *>(ctx->chunk_first.p), K,
-                                         f.gx, plan.n ? plan.shift[0] : 0,
-                                         plan.n ? plan.nbits[0] : 0, hist, digit_total, tk_alt,
-                                         tv_alt, static_cast<uint2 *>(ctx->ranges_local.p),
-                                         (uint32_t)f.T_strip, f.s),
+        GSR_HIP(gsr_launch_dup_sort_pass(ctx->bin.get(), ctx->chunk_first.get(), K, f.gx,
+                                         plan.n ? plan.shift[0] : 0, plan.n ? plan.nbits[0] : 0,
+                                         hist, digit_total, tk_alt, tv_alt,
+                                         ctx->ranges_local.get(), (uint32_t)f.T_strip, f.s),
                 "duplicate launch");
         std::swap(tk, tk_alt);
         std::swap(tv, tv_alt);
@@ -750,10 +773,9 @@ int launch_binning(gsr_context *ctx, Frame &f) {
                 "tile sort launch");
     GSR_TRY(stage_end(ctx, f, 4));
     if (K == 0)
-        GSR_HIP(hipMemsetAsync(ctx->ranges_local.p, 0, f.T_strip * 8, f.s),
+        GSR_HIP(hipMemsetAsync(ctx->ranges_words(), 0, f.T_strip * 8, f.s),
                 "hipMemsetAsync(ranges)");
-    GSR_HIP(gsr_launch_ranges(tk, K, static_cast<uint32_t *>(ctx->ranges_local.p), f.s),
-            "ranges launch");
+    GSR_HIP(gsr_launch_ranges(tk, K, ctx->ranges_words(), f.s), "ranges launch");
     f.point_list = tv;
     f.tiles_local = tk;
     f.id_mask = 0xFFFFFFFFu;
@@ -764,7 +786,7 @@ int launch_binning(gsr_context *ctx, Frame &f) {
 int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st,
                  gsr_outputs *out) {
     GsrBlendArgs ba{};
-    ba.ranges = static_cast<const uint2 *>(ctx->ranges_local.p);
+    ba.ranges = ctx->ranges_local.get();
     ba.point_list = f.point_list;
     ba.records = f.pa.records;
     ba.W = f.W;
@@ -781,10 +803,9 @@ int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st
     ba.cull = ctx->cull;
     ba.fast = ctx->fast;
     ba.id_mask = f.id_mask;
-    ba.order = f.colpairs ? static_cast<const uint32_t *>(ctx->blend_order.p)
-                          : nullptr;  // (per-pair form: row-major)
+    ba.order = f.colpairs ? ctx->blend_order.get() : nullptr;  // (per-pair form: row-major)
     if (f.graph) {  // the list length is on the device: a list over the capacity is not blended
-        ba.list_n = static_cast<const uint32_t *>(ctx->frame_words.p) + 1;
+        ba.list_n = ctx->list_n();
         ba.list_cap = (uint32_t)ctx->list_cap;
     }
     if (f.shading != GSR_SHADE_SPLAT) {  // a GL shading's first-hit kernel instead
@@ -809,16 +830,36 @@ struct JoinGuard {
 // The state gsr_get_binning / gsr_tile_row_pairs read, after a rendered frame.
 void finish_frame(gsr_context *ctx, const Frame &f, gsr_outputs *out) {
     out->num_rendered = (int64_t)f.K;
-    ctx->last_K = (int64_t)f.K;
-    ctx->last_list = (int64_t)f.KL;
-    ctx->last_tight = f.tight;
-    ctx->last_gx = f.gx, ctx->last_gy = f.gy, ctx->last_rb = f.rb, ctx->last_re = f.re;
-    ctx->last_point_list = f.point_list;
-    ctx->last_tiles_local = f.tiles_local;
-    ctx->last_id_mask = f.id_mask;
-    ctx->last_packed = f.colpairs && f.KL > 0;
-    ctx->have_forward = true;
+    gsr_context::LastFrame &l = ctx->last;
+    l.K = (int64_t)f.K;
+    l.list = (int64_t)f.KL;
+    l.tight = f.tight;
+    l.gx = f.gx, l.gy = f.gy, l.rb = f.rb, l.re = f.re;
+    l.point_list = f.point_list;
+    l.tiles_local = f.tiles_local;
+    l.id_mask = f.id_mask;
+    l.packed = f.colpairs && f.KL > 0;
+    l.valid = true;
     if (f.tmode) ++ctx->timed_frames;
+}
+
+// The head of a rendered frame: ---- 1. preprocess, and the fork the second stream waits for.
+int frame_head(gsr_context *ctx, const Frame &f) {
+    if (f.tmode == 1) GSR_HIP(hipEventRecord(f.ev[0], f.s), "hipEventRecord");
+    GSR_HIP(gsr_launch_preprocess(f.pa, f.s), "preprocess launch");
+    GSR_HIP(hipEventRecord(ctx->fork, f.s), "hipEventRecord(fork)");
+    return stage_end(ctx, f, 0);
+}
+
+// ... and its tail, once the list is binned: ---- 6. join: the blend reads the colours and the
+// second-stream ranges; ---- 7. blend
+int frame_tail(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st,
+               gsr_outputs *out) {
+    if (ctx->second_stream)
+        GSR_HIP(hipStreamWaitEvent(f.s, ctx->join, 0), "hipStreamWaitEvent(join)");
+    GSR_TRY(stage_end(ctx, f, 5));
+    GSR_TRY(launch_blend(ctx, f, st, out));
+    return stage_end(ctx, f, 6);
 }
 
 // ---- frame graphs (DESIGN.md decision 12) -----------------------------------------------------
@@ -876,8 +917,7 @@ GraphKey graph_key(const gsr_context *ctx, const Frame &f) {
 // words, and none of the per-frame pointers (camera matrices, outputs), which they do not read.
 GsrPreprocessArgs graph_args(const gsr_context *ctx, const GsrPreprocessArgs &a) {
     GsrPreprocessArgs g = a;
-    uint32_t *fw = static_cast<uint32_t *>(ctx->frame_words.p);
-    g.campos = a.campos ? reinterpret_cast<const float *>(fw + 4) : nullptr;
+    g.campos = a.campos ? reinterpret_cast<const float *>(ctx->frame_words.get() + 4) : nullptr;
     g.viewmatrix = g.projmatrix = nullptr;
     g.scales = g.rotations = g.opacities = g.cov3D_precomp = nullptr;
     g.radii = nullptr;
@@ -961,47 +1001,26 @@ Frame graph_frame(const gsr_context *ctx, const Frame &f) {
 int chain_sort(gsr_context *ctx, Frame &g, hipStream_t cs) {
     g.s = cs;
     if (g.main_publish)
-        GSR_HIP(gsr_launch_count_pairs(g.pa, cs, static_cast<uint32_t *>(ctx->ds_ctl.p),
-                                       static_cast<const uint32_t *>(ctx->frame_words.p)),
+        GSR_HIP(gsr_launch_count_pairs(g.pa, cs, ctx->ds_ctl.get(), ctx->frame_words.get()),
                 "pair count launch");
     return launch_depth_sort(ctx, g, 0, gsr_depth_sort_passes(32));
 }
 
 // The column counts, the column scatter and the row pass over the capacity, the list length
-// read on the device; *point_list: the buffer the sorted list ends in.
-int chain_bin(gsr_context *ctx, Frame &g, hipStream_t cs, uint32_t **point_list) {
+// read on the device; g.point_list: the buffer the sorted list ends in.
+int chain_bin(gsr_context *ctx, Frame &g, hipStream_t cs) {
     g.s = cs;
     GSR_TRY(launch_scan(ctx, g));
-    const int64_t cap = ctx->list_cap;
-    uint32_t *list_n = static_cast<uint32_t *>(ctx->frame_words.p) + 1;
-    uint32_t *tv = static_cast<uint32_t *>(ctx->tile_vals.p);
-    uint32_t *tv_alt = static_cast<uint32_t *>(ctx->tile_vals_alt.p);
-    GSR_HIP(gsr_launch_col_pairs_scatter(
-                static_cast<const uint32_t *>(ctx->perm.p),
-                static_cast<const uint2 *>(ctx->rect_sorted.p),
-                g.tight ? static_cast<const uint4 *>(ctx->rc_sorted.p) : nullptr, g.P,
-                static_cast<const uint32_t *>(ctx->ds_ctl.p),
-                static_cast<const uint32_t *>(ctx->col_hist.p),
-                static_cast<uint32_t *>(ctx->digit_total.p), g.col_shift, tv_alt, cs,
-                (uint32_t)cap, list_n),
-            "column scatter launch");
-    std::swap(tv, tv_alt);
-    if (g.col_shift < 32)
-        GSR_HIP(gsr_radix_sort_keys(&tv, &tv_alt, cap, g.col_shift, 32,
-                                    static_cast<uint32_t *>(ctx->hist.p),
-                                    static_cast<uint32_t *>(ctx->digit_total.p), cs, list_n),
-                "tile sort launch");
-    *point_list = tv;
-    return GSR_OK;
+    return launch_col_binning(ctx, g, ctx->list_cap, ctx->list_n());
 }
 
 // Records the frame's three chains (the key's) into e.
 int record_frame_graphs(gsr_context *ctx, const Frame &f, GraphEntry &e) {
     Frame g = graph_frame(ctx, f);
-    const uint32_t *fw = static_cast<const uint32_t *>(ctx->frame_words.p);
+    const uint32_t *fw = ctx->frame_words.get();
     GSR_TRY(record_chain(ctx, [&](hipStream_t cs) { return chain_sort(ctx, g, cs); }, &e.sort));
-    GSR_TRY(record_chain(ctx, [&](hipStream_t cs) { return chain_bin(ctx, g, cs, &e.point_list); },
-                         &e.bin));
+    GSR_TRY(record_chain(ctx, [&](hipStream_t cs) { return chain_bin(ctx, g, cs); }, &e.bin));
+    e.point_list = g.point_list;
     GSR_TRY(record_chain(ctx, [&](hipStream_t cs) { return aux_chain(ctx, g, cs, fw); }, &e.aux));
     ++ctx->graph_records;
     return GSR_OK;
@@ -1053,12 +1072,10 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
     // a chain that cannot be recorded or instantiated leaves the frame to the direct path
     if (replay && find_graphs(ctx, f, &e) != GSR_OK) return kNoGraphs;
     Frame g = graph_frame(ctx, f);
-    const uint32_t *fw = static_cast<const uint32_t *>(ctx->frame_words.p);
+    uint32_t *fw = ctx->frame_words.get();
     hipStream_t s = f.s;
-    if (f.tmode == 1) GSR_HIP(hipEventRecord(f.ev[0], s), "hipEventRecord");
-    f.pa.frame_words = static_cast<uint32_t *>(ctx->frame_words.p);
-    GSR_HIP(gsr_launch_preprocess(f.pa, s), "preprocess launch");
-    GSR_HIP(hipEventRecord(ctx->fork, s), "hipEventRecord(fork)");
+    f.pa.frame_words = fw;
+    GSR_TRY(frame_head(ctx, f));
     if (replay) GSR_HIP(hipGraphLaunch(e->sort, s), "hipGraphLaunch(depth sort)");
     else GSR_TRY(chain_sort(ctx, g, s));
     const bool two = ctx->second_stream != 0;  // (else mode 2 on one stream: in order on s)
@@ -1066,33 +1083,16 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
     if (replay) GSR_HIP(hipGraphLaunch(e->aux, two ? ctx->aux : s), "hipGraphLaunch(aux chain)");
     else GSR_TRY(aux_chain(ctx, g, two ? ctx->aux : s, fw));
     if (two) GSR_HIP(hipEventRecord(ctx->join, ctx->aux), "hipEventRecord(join)");
-    uint32_t *point_list = nullptr;
-    if (replay) {
-        GSR_HIP(hipGraphLaunch(e->bin, s), "hipGraphLaunch(binning)");
-        point_list = e->point_list;
-    } else {
-        GSR_TRY(chain_bin(ctx, g, s, &point_list));
-    }
-    if (two) GSR_HIP(hipStreamWaitEvent(s, ctx->join, 0), "hipStreamWaitEvent(join)");
-    GSR_TRY(stage_end(ctx, f, 5));
-    f.point_list = point_list;
+    if (replay) GSR_HIP(hipGraphLaunch(e->bin, s), "hipGraphLaunch(binning)");
+    else GSR_TRY(chain_bin(ctx, g, s));
+    f.point_list = replay ? e->point_list : g.point_list;
     f.tiles_local = nullptr;
-    f.id_mask = f.col_shift < 32 ? (1u << f.col_shift) - 1u : 0xFFFFFFFFu;
-    GSR_TRY(launch_blend(ctx, f, st, out));
-    GSR_TRY(stage_end(ctx, f, 6));
+    f.id_mask = id_mask_of(f.col_shift);
+    GSR_TRY(frame_tail(ctx, f, st, out));
     ++ctx->graph_frames;
     // K for num_rendered: published by the first kernel after the preprocess, long before the
     // host has queued the rest of the frame
-    uint64_t tagv = 0;
-    if (!spin_on(&ctx->h_total[7], [&](uint64_t v) { return v == f.tag; }, tagv))
-        GSR_HIP(hipStreamSynchronize(f.main_publish || !two ? s : ctx->aux),
-                "hipStreamSynchronize(pair count)");
-    f.K = __atomic_load_n(&ctx->h_total[2], __ATOMIC_ACQUIRE);
-    ctx->last_Dr = (uint32_t)__atomic_load_n(&ctx->h_total[6], __ATOMIC_ACQUIRE);
-    ctx->last_D = (uint32_t)__atomic_load_n(&ctx->h_total[3], __ATOMIC_ACQUIRE);
-    f.KL = f.tight ? __atomic_load_n(&ctx->h_total[5], __ATOMIC_ACQUIRE) : f.K;
-    if (f.K > (uint64_t)UINT32_MAX - 4096)
-        return fail(GSR_E_INVALID, "gsr_forward: more than 2^32-4097 (Gaussian, tile) pairs");
+    GSR_TRY(read_K(ctx, f, publish_stream(ctx, f)));
     if ((int64_t)f.KL > ctx->list_cap) return kOverflow;
     finish_frame(ctx, f, out);
     return GSR_OK;
@@ -1101,12 +1101,12 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
             gsr_outputs *out, hipStream_t s, int shading) {
     Frame f;
-    ctx->have_forward = false;
+    ctx->last.valid = false;
     GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
-    f.graph = f.P > 0 && graph_eligible(ctx, f, out);
+    f.graph = graph_eligible(ctx, f, out);
     if (f.graph) {
         GSR_TRY(drain_retired(ctx, s, false));
         int rc = forward_graph(ctx, f, st, out);
@@ -1129,30 +1129,23 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
     if (f.P == 0) {  // upstream returns the zero-initialised image without rendering
         GSR_HIP(hipMemsetAsync(out->color, 0, (size_t)3 * f.rows_out * f.W * sizeof(float), s),
                 "hipMemsetAsync(color)");
-        GSR_HIP(hipMemsetAsync(ctx->ranges_local.p, 0, f.T_strip * 8, s), "hipMemsetAsync");
-        out->num_rendered = 0;
-        ctx->last_K = 0;
-        ctx->last_list = 0;
-        ctx->last_tight = false;
-        ctx->last_gx = f.gx, ctx->last_gy = f.gy, ctx->last_rb = f.rb, ctx->last_re = f.re;
-        ctx->last_point_list = static_cast<uint32_t *>(ctx->tile_vals.p);
-        ctx->last_tiles_local = static_cast<uint32_t *>(ctx->tile_keys.p);
-        ctx->last_id_mask = 0xFFFFFFFFu;
-        ctx->last_packed = false;
-        ctx->have_forward = true;
+        GSR_HIP(hipMemsetAsync(ctx->ranges_words(), 0, f.T_strip * 8, s), "hipMemsetAsync");
+        // an empty list in the per-pair form's buffers; no stage ran, so no timed frame
+        f.K = f.KL = 0;
+        f.tight = false;
+        f.point_list = ctx->tile_vals.get();
+        f.tiles_local = ctx->tile_keys.get();
+        f.id_mask = 0xFFFFFFFFu;
+        f.tmode = 0;
+        finish_frame(ctx, f, out);
         return GSR_OK;
     }
 
-    if (f.tmode == 1) GSR_HIP(hipEventRecord(f.ev[0], s), "hipEventRecord");
-    // ---- 1. preprocess
-    GSR_HIP(gsr_launch_preprocess(f.pa, s), "preprocess launch");
-    GSR_HIP(hipEventRecord(ctx->fork, s), "hipEventRecord(fork)");
-    GSR_TRY(stage_end(ctx, f, 0));
+    GSR_TRY(frame_head(ctx, f));
     // MSD frames: K for the host and D for the sort from one kernel on the main stream (one
     // launch fewer than the second stream's publish plus the sort's own key-bit reduction)
     if (f.main_publish)
-        GSR_HIP(gsr_launch_count_pairs(f.pa, s, static_cast<uint32_t *>(ctx->ds_ctl.p)),
-                "pair count launch");
+        GSR_HIP(gsr_launch_count_pairs(f.pa, s, ctx->ds_ctl.get()), "pair count launch");
 
     // ---- 2. depth sort: pass 0 first, then the second stream's work (the host hands the
     // critical chain to the GPU first: queueing the ~10 second-stream commands before it left
@@ -1167,9 +1160,9 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
     if (!f.msd_sort) {  // the LSD sort: the passes D needs
         int depth_passes = gsr_depth_sort_passes(32);  // all
         uint64_t dv = 0;
-        if (ctx->last_K >= kWaitDPairs && ctx->last_D <= 2u * 12u &&
-            spin_on(&ctx->h_total[4], [&](uint64_t v) { return (uint32_t)(v >> 32) == f.tag; },
-                    dv))
+        if (ctx->last.K >= kWaitDPairs && ctx->last_D <= 2u * 12u &&
+            spin_on(&ctx->host_words->sort_D,
+                    [&](uint64_t v) { return (uint32_t)(v >> 32) == f.tag; }, dv))
             depth_passes = gsr_depth_sort_passes((uint32_t)dv);
         GSR_TRY(launch_depth_sort(ctx, f, 1, depth_passes));
     }
@@ -1183,15 +1176,9 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
     // ---- 4, 5. duplicate + tile sort (+ the per-pair form's ranges)
     GSR_TRY(launch_binning(ctx, f));
 
-    // ---- 6. join: the blend reads the colours and the second-stream ranges
+    // ---- 6, 7. join + blend
     guard.armed = false;
-    if (ctx->second_stream)
-        GSR_HIP(hipStreamWaitEvent(s, ctx->join, 0), "hipStreamWaitEvent(join)");
-    GSR_TRY(stage_end(ctx, f, 5));
-
-    // ---- 7. blend
-    GSR_TRY(launch_blend(ctx, f, st, out));
-    GSR_TRY(stage_end(ctx, f, 6));
+    GSR_TRY(frame_tail(ctx, f, st, out));
     finish_frame(ctx, f, out);
     return GSR_OK;
 }
@@ -1216,19 +1203,15 @@ int gsr_create(gsr_context **out) {
         delete ctx;
         return fail(GSR_E_HIP, "gsr_create: no HIP device");
     }
-    if (hipHostMalloc(reinterpret_cast<void **>(&ctx->h_total), 8 * sizeof(uint64_t),
+    if (hipHostMalloc(reinterpret_cast<void **>(&ctx->host_words), sizeof(GsrHostWords),
                       hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_hostK), ctx->h_total + 2, 0) !=
-            hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_hostD), ctx->h_total + 4, 0) !=
-            hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_hostCrowd), ctx->h_total + 1,
+        hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_host_words), ctx->host_words,
                                 0) != hipSuccess) {
         (void)hipGetLastError();
         delete ctx;
         return fail(GSR_E_HIP, "gsr_create: hipHostMalloc failed");
     }
-    std::memset(ctx->h_total, 0, 8 * sizeof(uint64_t));  // tag 0 never matches a frame
+    std::memset(ctx->host_words, 0, sizeof(GsrHostWords));  // tag 0 never matches a frame
     bool ok = hipMalloc(&ctx->frame_words.p, 64) == hipSuccess &&
               hipMemset(ctx->frame_words.p, 0, 64) == hipSuccess &&
               // stream-to-stream hand-offs on one device: a device-scope release suffices
@@ -1258,15 +1241,7 @@ void gsr_destroy(gsr_context *ctx) {
     (void)hipDeviceSynchronize();
     for (GraphEntry &e : ctx->graph_cache) retire_graph(ctx, e);
     for (hipGraphExec_t ge : ctx->graph_retired) (void)hipGraphExecDestroy(ge);
-    DevBuf *bufs[] = {&ctx->records,     &ctx->strip_rect,    &ctx->sort_keys,  &ctx->ds_a,
-                      &ctx->ds_b,        &ctx->block_kept,    &ctx->partials,   &ctx->total,
-                      &ctx->hist,        &ctx->digit_total,   &ctx->bin,        &ctx->chunk_first,
-                      &ctx->rect_sorted, &ctx->pair_count,    &ctx->perm,       &ctx->ds_ctl,
-                      &ctx->tile_keys,   &ctx->tile_vals,     &ctx->tile_keys_alt,
-                      &ctx->tile_vals_alt, &ctx->ranges_local, &ctx->tile_diff, &ctx->col_hist,
-                      &ctx->color_ids, &ctx->blend_order, &ctx->strip_rc, &ctx->rc_sorted,
-                      &ctx->frame_words};
-    for (DevBuf *b : bufs)
+    for (DevBuf *b : ctx->bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &set : ctx->ev)
         for (auto &e : set)
@@ -1278,7 +1253,7 @@ void gsr_destroy(gsr_context *ctx) {
     if (ctx->join) (void)hipEventDestroy(ctx->join);
     if (ctx->compacted) (void)hipEventDestroy(ctx->compacted);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-    if (ctx->h_total) (void)hipHostFree(ctx->h_total);
+    if (ctx->host_words) (void)hipHostFree(ctx->host_words);
     delete ctx;
 }
 
@@ -1411,38 +1386,37 @@ int gsr_get_binning(gsr_context *ctx, uint32_t *point_list, uint32_t *point_tile
                     uint32_t *ranges, int64_t *list_entries, int32_t *num_tiles, void *stream) {
     if (!ctx) return fail(GSR_E_INVALID, "gsr_get_binning: NULL context");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->have_forward) return fail(GSR_E_STATE, "gsr_get_binning: no forward yet");
+    const gsr_context::LastFrame &l = ctx->last;
+    if (!l.valid) return fail(GSR_E_STATE, "gsr_get_binning: no forward yet");
     hipStream_t s = static_cast<hipStream_t>(stream);
     GSR_TRY(order_stream(ctx, s));
-    const int64_t K = ctx->last_list;
-    const uint64_t T = (uint64_t)ctx->last_gx * ctx->last_gy;
-    const uint64_t off = (uint64_t)ctx->last_rb * ctx->last_gx;
-    const uint64_t T_strip = (uint64_t)ctx->last_gx * (ctx->last_re - ctx->last_rb);
+    const int64_t K = l.list;
+    const uint64_t T = (uint64_t)l.gx * l.gy;
+    const uint64_t off = (uint64_t)l.rb * l.gx;
+    const uint64_t T_strip = (uint64_t)l.gx * (l.re - l.rb);
     if (list_entries) *list_entries = K;  // (tight lists: fewer than the forward's num_rendered)
     if (num_tiles) *num_tiles = (int32_t)T;
     if (point_list && K > 0) {
-        if (ctx->last_id_mask != 0xFFFFFFFFu)
-            GSR_HIP(gsr_launch_unpack_ids(ctx->last_point_list, K, ctx->last_id_mask, point_list,
-                                          s),
+        if (l.id_mask != 0xFFFFFFFFu)
+            GSR_HIP(gsr_launch_unpack_ids(l.point_list, K, l.id_mask, point_list, s),
                     "unpack launch");
         else
-            GSR_HIP(hipMemcpyAsync(point_list, ctx->last_point_list, (size_t)K * 4,
+            GSR_HIP(hipMemcpyAsync(point_list, l.point_list, (size_t)K * 4,
                                    hipMemcpyDeviceToDevice, s),
                     "hipMemcpyAsync(point_list)");
     }
     if (point_tiles && K > 0) {
-        if (!ctx->last_packed)
-            GSR_HIP(gsr_launch_globalize_tiles(ctx->last_tiles_local, K, (uint32_t)off,
-                                               point_tiles, s),
+        if (!l.packed)
+            GSR_HIP(gsr_launch_globalize_tiles(l.tiles_local, K, (uint32_t)off, point_tiles, s),
                     "globalize launch");
         else  // packed list (no key array): the tile of every pair from the ranges
-            GSR_HIP(gsr_launch_fill_tiles(static_cast<const uint2 *>(ctx->ranges_local.p),
-                                          (uint32_t)T_strip, (uint32_t)off, point_tiles, s),
+            GSR_HIP(gsr_launch_fill_tiles(ctx->ranges_local.get(), (uint32_t)T_strip,
+                                          (uint32_t)off, point_tiles, s),
                     "fill_tiles launch");
     }
     if (ranges) {
         GSR_HIP(hipMemsetAsync(ranges, 0, T * 8, s), "hipMemsetAsync(ranges)");
-        GSR_HIP(hipMemcpyAsync(reinterpret_cast<char *>(ranges) + off * 8, ctx->ranges_local.p,
+        GSR_HIP(hipMemcpyAsync(reinterpret_cast<char *>(ranges) + off * 8, ctx->ranges_local.get(),
                                T_strip * 8, hipMemcpyDeviceToDevice, s),
                 "hipMemcpyAsync(ranges)");
     }
@@ -1453,14 +1427,14 @@ int gsr_get_binning(gsr_context *ctx, uint32_t *point_list, uint32_t *point_tile
 int gsr_tile_row_pairs(gsr_context *ctx, uint32_t *row_pairs, int32_t n_rows, void *stream) {
     if (!ctx) return fail(GSR_E_INVALID, "gsr_tile_row_pairs: NULL context");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->have_forward) return fail(GSR_E_STATE, "gsr_tile_row_pairs: no forward yet");
-    const uint32_t rows = ctx->last_re - ctx->last_rb;
+    if (!ctx->last.valid) return fail(GSR_E_STATE, "gsr_tile_row_pairs: no forward yet");
+    const uint32_t rows = ctx->last.re - ctx->last.rb;
     if (n_rows != (int32_t)rows || (rows > 0 && !row_pairs))
         return fail(GSR_E_INVALID, "gsr_tile_row_pairs: n_rows must be the strip's " +
                                        std::to_string(rows) + " tile rows");
     GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    GSR_HIP(gsr_launch_row_pairs(static_cast<const uint2 *>(ctx->ranges_local.p), ctx->last_gx,
-                                 rows, row_pairs, static_cast<hipStream_t>(stream)),
+    GSR_HIP(gsr_launch_row_pairs(ctx->ranges_local.get(), ctx->last.gx, rows, row_pairs,
+                                 static_cast<hipStream_t>(stream)),
             "row pairs launch");
     return GSR_OK;
 }
@@ -1486,16 +1460,15 @@ int gsr_depth_argsort(gsr_context *ctx, const float *xyz, int64_t P, const float
     if (P == 0) return GSR_OK;
     GSR_TRY(order_stream(ctx, s));
     GSR_TRY(reserve_P(ctx, P, s));
-    uint32_t *k = static_cast<uint32_t *>(ctx->sort_keys.p);
+    uint32_t *k = ctx->sort_keys.get();
     GSR_HIP(gsr_launch_view_depth_keys(xyz, P, view_host16[8], view_host16[9], view_host16[10],
                                        view_host16[11], k, out_depth, s),
             "view depth launch");
     // every key is kept (no sentinel); the indices land in out_index directly (< 2^31)
-    GSR_HIP(gsr_depth_sort(k, P, 0, static_cast<uint2 *>(ctx->ds_a.p),
-                           static_cast<uint2 *>(ctx->ds_b.p), reinterpret_cast<uint32_t *>(out_index),
-                           static_cast<uint32_t *>(ctx->hist.p),
-                           static_cast<uint32_t *>(ctx->digit_total.p),
-                           static_cast<uint32_t *>(ctx->ds_ctl.p), 0, gsr_depth_sort_passes(32), s),
+    GSR_HIP(gsr_depth_sort(k, P, 0, ctx->ds_a.get(), ctx->ds_b.get(),
+                           reinterpret_cast<uint32_t *>(out_index), ctx->hist.get(),
+                           ctx->digit_total.get(), ctx->ds_ctl.get(), 0, gsr_depth_sort_passes(32),
+                           s),
             "depth argsort launch");
     return GSR_OK;
 }

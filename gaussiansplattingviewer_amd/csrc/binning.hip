@@ -669,7 +669,7 @@ hipError_t gsr_launch_scan_down(const uint32_t *perm, const uint2 *rect_sorted,
 
 int64_t gsr_duplicate_chunks(int64_t K) { return (K + kChunk - 1) / kChunk; }
 
-int64_t gsr_fused_chunks(int64_t K) { return (K + kFChunk - 1) / kFChunk; }
+static int64_t gsr_fused_chunks(int64_t K) { return (K + kFChunk - 1) / kFChunk; }
 
 hipError_t gsr_launch_dup_sort_pass(const uint4 *bin, const uint32_t *chunk_first, int64_t K,
                                     uint32_t gx, int shift, int nbits, uint32_t *hist,

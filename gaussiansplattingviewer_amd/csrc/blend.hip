@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
     const float puu = pu * pu, puv = pu * pv, pvv = pv * pv;
 
     const uint2 range = a.ranges[tile];
-    // done carried in the sign of T, as in k_blend
+    // done carried in the sign of T (T <= 0: the lane composites no more)
     float T = inside ? 1.0f : -1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
     uint32_t last_contributor = 0;
     auto live_any = [&]() { return __ballot(!(T <= 0.0f)) != 0ull; };

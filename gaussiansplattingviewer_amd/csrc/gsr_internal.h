@@ -13,7 +13,6 @@
 
 #define GSR_TILE_X 16
 #define GSR_TILE_Y 16
-#define GSR_WAVE 64
 
 namespace gsr {
 
@@ -263,6 +262,24 @@ inline uint32_t xcd_run_grid(int64_t nb) {
 
 }  // namespace gsr
 
+// The words a context's kernels store for its host: pinned host memory, device-mapped, eight
+// 64-bit words, zero at first (tag 0 never matches a frame; a frame's tag is nonzero).  The
+// stores are system-scope atomics and the host reads with acquire loads.  k_publish_K
+// (preprocess.hip) stores D, Dr, K_spans and K, then K_tag with release order, which the host
+// spins on; the depth sort's pass 0 stores sort_D for the host to count the LSD passes, and the
+// MSD local sort stores crowd (depth_sort.hip: both take the address of their one word).
+struct GsrHostWords {
+    unsigned long long unused;
+    unsigned long long crowd;    // the tag of the last frame whose MSD buckets crowded the LDS
+    unsigned long long K;        // (Gaussian, strip tile) pairs: upstream's num_rendered
+    unsigned long long D;        // the bits in which the kept depth keys differ
+    unsigned long long sort_D;   // (frame tag << 32) | D, from the depth sort's pass 0
+    unsigned long long K_spans;  // the pair count over the spans (tight binning's list length)
+    unsigned long long Dr;       // the bits of the kept depth keys' range (gsr::key_bits)
+    unsigned long long K_tag;    // the tag of the frame whose K, D, Dr and K_spans are above
+};
+static_assert(sizeof(GsrHostWords) == 8 * sizeof(unsigned long long), "eight pinned words");
+
 // ---- host-side launchers (defined in the .hip files, called by api.hip) ------------------
 struct GsrPreprocessArgs {
     int64_t P;
@@ -291,9 +308,8 @@ struct GsrPreprocessArgs {
     // bits) and its pair count over the spans (high 32 bits: the same without tight binning),
     // then as many uint2 of the OR / AND of its kept depth keys
     uint64_t *block_pairs;
-    // pinned host memory (device-mapped): [K, D, -, K over the spans, -, K tag]
-    unsigned long long *host_K;
-    uint32_t k_tag;              // nonzero: stored to host_K[5] after K (the host spins on it)
+    GsrHostWords *host_words;    // (the device view)
+    uint32_t k_tag;              // nonzero: stored to host_words->K_tag after K
     // frame graphs (api.hip): device words of the context -- [0] the frame's tag, [4..6] the
     // camera position -- which k_preprocess's block 0 stores (k_tag, *campos) for the kernels of
     // a recorded graph, whose arguments cannot change per frame; NULL otherwise
@@ -318,7 +334,7 @@ bool gsr_color_ids_ok(const GsrPreprocessArgs &a);
 hipError_t gsr_launch_color_ids(const GsrPreprocessArgs &a, const uint32_t *ids,
                                 const uint32_t *d_n, int waves_per_simd, hipStream_t s);
 // K of the frame (sum of the preprocess blocks' pair counts), the pair count over the spans and
-// D -> a.host_K (pinned host memory), after the preprocess.  ds_ctl (optional): also the MSD
+// D -> a.host_words (pinned host memory), after the preprocess.  ds_ctl (optional): also the MSD
 // depth sort's control words, ctl[1] = D and ctl[2] = its pass's shift (gsr_depth_sort_msd
 // with keybits NULL), so the publish runs on the main stream in place of the sort's own
 // key-bit reduction.
@@ -430,7 +446,6 @@ int64_t gsr_duplicate_chunks(int64_t K);
 // Fused duplicate + first tile-sort radix pass (digit (key >> shift) & (2^nbits - 1)):
 // writes the K pairs, stably ordered by that digit, to keys_out / vals_out.  Uses
 // chunk_first as written by gsr_launch_scan_down; hist needs gsr_radix_hist_words(K) words.
-int64_t gsr_fused_chunks(int64_t K);
 hipError_t gsr_launch_dup_sort_pass(const uint4 *bin, const uint32_t *chunk_first, int64_t K,
                                     uint32_t gx, int shift, int nbits, uint32_t *hist,
                                     uint32_t *digit_total, uint32_t *keys_out, uint32_t *vals_out,

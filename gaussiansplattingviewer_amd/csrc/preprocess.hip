@@ -513,12 +513,12 @@ __global__ __launch_bounds__(256) void k_preprocess(const GsrPreprocessArgs a) {
 // visible): K = sum of the per-block pair counts and D = the bits in which the kept depth keys
 // differ (bits of OR ^ AND: the depth sort's pass count), stored straight into pinned host
 // memory (system scope) so the host can read them as soon as this kernel's completion event
-// fires -- no copy, and nothing added to the main stream.  host_K[0] = K, host_K[1] = D,
-// host_K[3] = the pair count over the spans (the high halves of the block counts).
+// fires -- no copy, and nothing added to the main stream (GsrHostWords; the pair count over the
+// spans is the sum of the high halves of the block counts).
 constexpr int kPubThreads = 1024, kPubWaves = kPubThreads / 64;
 __global__ __launch_bounds__(kPubThreads) void k_publish_K(const unsigned long long *__restrict__ cnt,
                                                            const uint2 *__restrict__ keybits,
-                                                           int64_t n, unsigned long long *host_K,
+                                                           int64_t n, GsrHostWords *host,
                                                            uint32_t k_tag, uint32_t *ds_ctl,
                                                            const uint32_t *d_tag) {
     __shared__ unsigned long long s_w[kPubWaves], s_wt[kPubWaves];
@@ -573,17 +573,17 @@ __global__ __launch_bounds__(kPubThreads) void k_publish_K(const unsigned long l
         // differ is the highest bit any two kept keys differ in); Dr: the bits of their range
         const KeyBits kb = key_bits(mx, mn);
         if (ds_ctl) gsr_msd_ctl(kb, ds_ctl);  // the MSD depth sort's control words
-        __hip_atomic_store(host_K + 1, (unsigned long long)kb.D, __ATOMIC_RELAXED,
+        __hip_atomic_store(&host->D, (unsigned long long)kb.D, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_K + 4, (unsigned long long)kb.Dr, __ATOMIC_RELAXED,
+        __hip_atomic_store(&host->Dr, (unsigned long long)kb.Dr, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_K + 3, tt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_K, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->K_spans, tt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->K, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         // the host spins on this tag instead of sleeping in an event wait (release: K and D are
         // visible first)
         if (d_tag) k_tag = *d_tag;
         if (k_tag)
-            __hip_atomic_store(host_K + 5, (unsigned long long)k_tag, __ATOMIC_RELEASE,
+            __hip_atomic_store(&host->K_tag, (unsigned long long)k_tag, __ATOMIC_RELEASE,
                                __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -766,7 +766,7 @@ hipError_t gsr_launch_count_pairs(const GsrPreprocessArgs &a, hipStream_t s, uin
     const uint2 *keybits = reinterpret_cast<const uint2 *>(a.block_pairs + g);
     hipLaunchKernelGGL(k_publish_K, dim3(1), dim3(kPubThreads), 0, s,
                        reinterpret_cast<const unsigned long long *>(a.block_pairs), keybits,
-                       (int64_t)g, a.host_K, d_tag ? 0u : a.k_tag, ds_ctl, d_tag);
+                       (int64_t)g, a.host_words, d_tag ? 0u : a.k_tag, ds_ctl, d_tag);
     return hipGetLastError();
 }
 

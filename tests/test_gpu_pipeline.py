@@ -225,3 +225,89 @@ def test_threads_and_streams_share_one_context(gpu):
     for (t, rep, i), (k, color) in out.items():
         assert k == ref[i][0]
         assert torch.equal(color.view(torch.int32), ref[i][1].view(torch.int32)), (t, rep, i)
+
+
+def _bits_equal(a, b):
+    assert a.num_rendered == b.num_rendered
+    assert torch.equal(a.radii, b.radii)
+    assert torch.equal(a.color.view(torch.int32), b.color.view(torch.int32))
+
+
+def test_empty_frame_state_then_normal_frame(gpu):
+    """An empty frame (P = 0) leaves an exported state of its own -- no list entries, all-zero
+    ranges and row counts -- and the next frame on that context equals a fresh context's."""
+    from gaussiansplattingviewer_amd.rasterizer import binning_state, tile_row_pairs
+    used, fresh = 200, 201
+    W, H = 64, 48
+    view, proj, campos, tx, ty = cuda_camera_inputs(static_camera(W, H))
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(gpu)  # noqa: E731
+    r = rasterize_gaussians_native(
+        torch.full((3,), 0.3, device=gpu), torch.zeros((0, 3), device=gpu), None,
+        torch.zeros((0, 1), device=gpu), torch.zeros((0, 3), device=gpu),
+        torch.zeros((0, 4), device=gpu), 1.0, None, up(view), up(proj), tx, ty, H, W,
+        torch.zeros((0, 1, 3), device=gpu), 0, up(campos), False, False, slot=used)
+    assert r.num_rendered == 0 and r.radii.shape == (0,)
+    assert torch.all(r.color == 0)
+    pl, pt, rg = binning_state(0, used)
+    assert pl.numel() == 0 and pt.numel() == 0
+    assert tuple(rg.shape) == (4 * 3, 2) and not rg.any()
+    assert not tile_row_pairs(3, 0, used).any()
+
+    P, W, H = 2_000, 320, 240
+    _, dg, cams = _scene(gpu, P, W, H, 1, seed=29)
+    a = _render(dg, cams[0], W, H, gpu, slot=used)
+    sa = binning_state(0, used)
+    b = _render(dg, cams[0], W, H, gpu, slot=fresh)
+    sb = binning_state(0, fresh)
+    _bits_equal(a, b)
+    assert a.num_rendered > 0 and sa[0].numel() > 0
+    for x, y in zip(sa, sb):
+        assert torch.equal(x, y)
+
+
+def test_stage_timing_leaves_the_frame_alone(gpu):
+    """gsr_set_timing 1 (every stage) and 2 (the blend of every 8th forward) change no output
+    bit, with and without frame graphs, and gsr_stage_times reports finite, non-negative means
+    with the stages that always run above zero; with no timed forward it is a state error."""
+    import ctypes
+    from gaussiansplattingviewer_amd import _lib
+    from gpu_helpers import set_option
+    P, W, H, n = 10_000, 320, 240, 9
+    _, dg, cams = _scene(gpu, P, W, H, n, seed=31)
+    lib = _lib.load_library()
+    names = _lib.stage_names()
+    i_pre, i_blend = names.index("preprocess"), names.index("blend")
+
+    def times(ctx):
+        buf = (ctypes.c_float * 8)(*([float("nan")] * 8))
+        rc = lib.gsr_stage_times(ctx, buf, 8)
+        return rc, np.array(buf[:], np.float32)
+
+    for slot, graphs in ((202, 0), (203, 1)):
+        set_option(gpu, _lib.GSR_OPT_FRAME_GRAPHS, graphs, slot)
+        ctx = _lib.context(0, slot)
+        _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
+        ref = [_render(dg, cam, W, H, gpu, slot=slot) for cam in cams]
+        torch.cuda.synchronize()
+
+        _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
+        for cam, want in zip(cams[:3], ref):
+            _bits_equal(_render(dg, cam, W, H, gpu, slot=slot), want)
+        rc, ms = times(ctx)
+        assert rc == 8
+        assert np.all(np.isfinite(ms)) and np.all(ms >= 0), ms
+        assert ms[i_pre] > 0 and ms[i_blend] > 0, ms
+
+        _lib.check(lib.gsr_set_timing(ctx, 2), "gsr_set_timing")
+        for cam, want in zip(cams, ref):  # the 1st and the 9th forward are sampled
+            _bits_equal(_render(dg, cam, W, H, gpu, slot=slot), want)
+        rc, ms = times(ctx)
+        assert rc == 8 and ms[i_blend] > 0, (rc, ms)
+
+        _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
+        for cam, want in zip(cams[:2], ref):
+            _bits_equal(_render(dg, cam, W, H, gpu, slot=slot), want)
+        rc, _ = times(ctx)
+        assert rc == -4  # GSR_E_STATE: no timed forward since gsr_set_timing
+        if graphs:
+            assert _lib.frame_graph_stats(0, slot)["graph_frames"] > 0

@@ -14,7 +14,7 @@ import json
 import sys
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
-d, kern = args[0], (args[1] if len(args) > 1 else "k_blend")
+d, kern = args[0], (args[1] if len(args) > 1 else "k_blend_q")
 out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
 if out_json in args:
     args.remove(out_json)
