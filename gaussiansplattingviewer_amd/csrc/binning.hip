@@ -918,11 +918,13 @@ hipError_t gsr_launch_fill_tiles(const uint2 *ranges, uint32_t n_tiles, uint32_t
     return hipGetLastError();
 }
 
-// Rows of 256 words the column-first binning needs: per block its sub-block offsets, per group
-// its column totals.
+// Rows of 256 words the column-first binning needs: per group its column totals, and per
+// sub-block its offsets -- for every sub-block of every group, since k_col_count writes all
+// kCGroup offset rows of a group whether or not the last ones hold Gaussians (with nb rows, a
+// block count that is no multiple of kCGroup put up to three rows past the buffer).
 int64_t gsr_col_blocks(int64_t n) {
     const int64_t nb = (n + kCG - 1) / kCG, ng = (nb + kCGroup - 1) / kCGroup;
-    return nb + ng;
+    return ng * kCGroup + ng;
 }
 
 hipError_t gsr_launch_col_pairs_count(const uint32_t *perm, const uint2 *strip_rect,

@@ -268,10 +268,27 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
                 // exponent log2(e) * (-q/2) = a dx^2 + b dx dy + c dy^2 with dx = ex - u,
                 // dy = ey - v, expanded in (u, v)
                 const float kL2e = 1.4426950408889634f;
-                const float ca = r.a.z * (-0.5f * kL2e), cb = r.a.w * (-kL2e),
-                            cc = r.b.x * (-0.5f * kL2e);
+                float ca = r.a.z * (-0.5f * kL2e), cb = r.a.w * (-kL2e),
+                      cc = r.b.x * (-0.5f * kL2e);
                 const float ex = r.a.x - (X0 + 3.5f), ey = r.a.y - (Y0 + 3.5f);
-                const float lo = __builtin_amdgcn_logf(r.b.y);  // log2(opacity)
+                float lo = __builtin_amdgcn_logf(r.b.y);  // log2(opacity)
+                // the conic as upstream reads it (before the rescaling below)
+                const bool pd = ca < 0.0f && cc < 0.0f && 4.0f * ca * cc > cb * cb;
+                bool neg_inf = false;
+                if (r.b.y < 0.0f) {
+                    // a negative opacity has no logarithm.  Upstream's alpha = o exp(power) is
+                    // negative (skipped): exponent -inf.  Except for o = -inf where exp(power)
+                    // underflows to 0 (power log2(e) < -150): -inf * 0 = NaN and min(0.99, NaN) =
+                    // 0.99.  There the exponent becomes -2^20 (power log2(e) + 150), by exact
+                    // scaling of the conic: >= 0 (alpha 0.99) where upstream's exp is 0, and
+                    // below -8 (alpha < 1/255) within 8e-6 above that threshold, power > 0 included
+                    neg_inf = r.b.y == -__builtin_huge_valf();
+                    lo = -__builtin_huge_valf();
+                    if (neg_inf) {
+                        ca *= -0x1p20f, cb *= -0x1p20f, cc *= -0x1p20f;
+                        lo = -150.0f * 0x1p20f;
+                    }
+                }
                 const float k0 = __builtin_fmaf(ex, __builtin_fmaf(ca, ex, cb * ey), cc * ey * ey);
                 st.g = make_float4(k0 + lo, __builtin_fmaf(-2.0f * ca, ex, -cb * ey),
                                    __builtin_fmaf(-cb, ex, -2.0f * cc * ey), ca);
@@ -279,10 +296,9 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
                 // upstream skips power > 0, which a positive-definite conic reaches only through
                 // rounding; the expanded form rounds differently (at a centre that falls on a
                 // pixel it can land just above 0), so the test is kept for the other conics only
-                const bool pd = ca < 0.0f && cc < 0.0f && 4.0f * ca * cc > cb * cb;
-                npd = !pd;
+                npd = !pd && !neg_inf;
                 st.e = make_float4(r.c.w, __uint_as_float(idx - range.x + 1u),
-                                   pd ? __builtin_huge_valf() : lo, 0.0f);
+                                   (pd || neg_inf) ? __builtin_huge_valf() : lo, 0.0f);
             } else {
                 st.g = r.a;
                 st.q = make_float4(r.b.x, r.b.y, r.c.y, r.c.z);

@@ -452,7 +452,7 @@ hipError_t gsr_launch_dup_sort_pass(const uint4 *bin, const uint32_t *chunk_firs
                                     uint2 *ranges_zero, uint32_t n_ranges, hipStream_t s);
 // Column-first pair generation (binning.hip): pass 1 of the tile sort on (Gaussian, column)
 // segments of the depth-sorted Gaussians.  hist: gsr_col_blocks(n_max) * 256 words (per group of
-// 4 blocks its column totals, per block its offsets within the group).
+// 4 blocks its column totals, per sub-block of every group its offsets within the group).
 int64_t gsr_col_blocks(int64_t n);
 // Tight binning: strip_rc (GsrPreprocessArgs) instead of strip_rect, and the depth-ordered copy
 // goes to rc_sorted instead of rect_sorted (NULL: full rects).

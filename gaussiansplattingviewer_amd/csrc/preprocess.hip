@@ -175,7 +175,9 @@ __device__ __forceinline__ float3 eval_sh3_stream(float3 pos, const float *campo
 __device__ __forceinline__ float3 cull_data(float A, float B, float C, float o) {
     const float kInf = __builtin_huge_valf();
     const double det_d = (double)A * (double)C - (double)B * (double)B;
-    if (!(det_d > 0.0) || !(A > 0.0f) || !(C > 0.0f) || !(o == o))
+    // (an opacity that is not finite is never culled: NaN, and -inf, whose alpha upstream
+    // takes as min(0.99, -inf * 0) = 0.99 where exp(power) underflows, far outside any L)
+    if (!(det_d > 0.0) || !(A > 0.0f) || !(C > 0.0f) || !(fabsf(o) < kInf))
         return make_float3(kInf, kInf, kInf);
     const float det = (float)det_d;  // > 0, or 0 / denormal -> infinite extents below
     float L = __logf(255.0f * o);
@@ -361,7 +363,11 @@ __device__ __forceinline__ uint32_t back_one(const GsrPreprocessArgs &a, int64_t
             const int r_int = f2i_sat(my_radius);
             const Rect rc = get_rect(px, py, r_int, a.grid_x, a.grid_y);
             all_tiles = (rc.x1 - rc.x0) * (rc.y1 - rc.y0);
-            if (all_tiles != 0) {
+            // a saturated radius <= 0 (my_radius NaN: a non-finite covariance, or lambda < 0
+            // under the square root) is culled like an empty rect -- the only behaviour upstream
+            // defines, its duplicateWithKeys skips radii <= 0 -- although get_rect of radius 0
+            // still covers a tile; so a Gaussian with pairs always has a positive radius
+            if (r_int > 0 && all_tiles != 0) {
                 const float opacity = f.opacity;
                 radius_out = r_int;
                 const uint32_t sy0 = max(rc.y0, a.row_begin), sy1 = min(rc.y1, a.row_end);
@@ -588,10 +594,18 @@ __global__ __launch_bounds__(kPubThreads) void k_publish_K(const unsigned long l
     }
 }
 
+// Colour needed: Gaussians with pairs in this strip (the blend reads them), or every visible
+// one when the caller asked for the rgb output (upstream semantics).  back_one gives pairs only
+// to a Gaussian with a positive radius, so the second set holds the first: whatever the blend
+// reads has its record colour written, with and without the rgb output.
+__device__ __forceinline__ bool needs_color(const GsrPreprocessArgs &a, int64_t idx) {
+    return a.rgb ? a.radii[idx] > 0 : a.strip_rect[idx].x != 0u;
+}
+
 // Colour of the Gaussians k_preprocess kept (radii > 0, as upstream computes colour only for
 // those): upstream computeColorFromSH, or colors_precomp copied.
 __device__ __forceinline__ void color_one(const GsrPreprocessArgs &a, int64_t idx) {
-    if (a.rgb ? a.radii[idx] == 0 : a.strip_rect[idx].x == 0u) return;
+    if (!needs_color(a, idx)) return;
     float3 col;
     if (a.colors_precomp) {
         col = make_float3(a.colors_precomp[3 * idx], a.colors_precomp[3 * idx + 1],
@@ -650,9 +664,7 @@ __global__ __launch_bounds__(256) void k_color(const GsrPreprocessArgs a) {
     const int64_t wave_stride = (int64_t)gridDim.x * 4;
     for (int64_t wv = (int64_t)blockIdx.x * 4 + w; wv < n_waves; wv += wave_stride) {
         const int64_t idx = wv * 64 + lane;
-        // colour needed: Gaussians with pairs in this strip (the blend reads them), or every
-        // visible one when the caller asked for the rgb output (upstream semantics)
-        if (idx < a.P && (a.rgb ? a.radii[idx] != 0 : a.strip_rect[idx].x != 0u)) {
+        if (idx < a.P && needs_color(a, idx)) {
             const float3 p = make_float3(a.means3D[3 * idx], a.means3D[3 * idx + 1],
                                          a.means3D[3 * idx + 2]);
             store_color(a, idx, eval_sh3_stream(p, a.campos,

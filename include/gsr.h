@@ -101,7 +101,11 @@ typedef struct {
     /* [P] int32 (0 = culled).  Required for whole frames.  On a strip (tile_row_begin/end)
      * it may be NULL when no per-Gaussian intermediate below is requested either: Gaussians
      * whose conservative footprint bound misses the strip then skip the covariance, radius and
-     * record work (a multi-GPU strip rank needs only its image). */
+     * record work (a multi-GPU strip rank needs only its image).
+     * A Gaussian whose saturated radius is <= 0 (a NaN radius: a non-finite covariance, or a
+     * negative eigenvalue under the square root) is culled like one outside the frame: radius
+     * 0, no tiles, no pairs, not in num_rendered, no per-Gaussian output written.  A radius
+     * is > 0 exactly where the Gaussian touches a tile. */
     int32_t *radii;
     /* optional per-Gaussian intermediates (NULL = not written) */
     float *depths;        /* [P]   view-space z */

@@ -292,8 +292,14 @@ int64_t oracle_preprocess(const OracleIn *in, float *depths, int32_t *radii, flo
         const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
         const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
         const float pimg[2] = {ndc2pix(p_proj[0], in->W), ndc2pix(p_proj[1], in->H)};
+        /* A saturated radius <= 0 (my_radius NaN: a non-finite covariance, or lambda < 0 under
+         * the square root for an indefinite one with negative trace) is culled: upstream's
+         * duplicateWithKeys skips radii <= 0, so this is the only behaviour it defines, and
+         * get_rect of radius 0 would still cover a tile. */
+        const int r_int = f2i_sat(my_radius);
+        if (r_int <= 0) continue;
         uint32_t rmin[2], rmax[2];
-        get_rect(pimg[0], pimg[1], f2i_sat(my_radius), gx, gy, rmin, rmax);
+        get_rect(pimg[0], pimg[1], r_int, gx, gy, rmin, rmax);
         if ((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) == 0) continue;
 
         if (!in->colors_precomp) {
@@ -305,7 +311,7 @@ int64_t oracle_preprocess(const OracleIn *in, float *depths, int32_t *radii, flo
             rgb[3 * idx + 2] = col[2];
         }
         depths[idx] = p_view[2];
-        radii[idx] = f2i_sat(my_radius);
+        radii[idx] = r_int;
         means2D[2 * idx + 0] = pimg[0];
         means2D[2 * idx + 1] = pimg[1];
         conic_opacity[4 * idx + 0] = conic[0];

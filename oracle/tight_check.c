@@ -138,7 +138,7 @@ enum { kSpanCols = 8, kSpanRows = 15 };
 static float model_cull_Lm(float A, float B, float C, float o, float shrink) {
     const int bare = shrink > 0.0f;
     const double det_d = (double)A * (double)C - (double)B * (double)B;
-    if (!(det_d > 0.0) || !(A > 0.0f) || !(C > 0.0f) || !(o == o)) return INFINITY;
+    if (!(det_d > 0.0) || !(A > 0.0f) || !(C > 0.0f) || !(fabsf(o) < INFINITY)) return INFINITY;
     const float det = (float)det_d;
     float L = logf(255.0f * o);
     if (!(L > 0.0f)) L = 0.0f;

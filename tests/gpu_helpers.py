@@ -51,19 +51,32 @@ def to_dev(a, dev):
     return None if a is None else torch.as_tensor(np.ascontiguousarray(a)).to(dev)
 
 
+def to_dev_unaligned(a, dev):
+    """to_dev, as a contiguous view that starts one float into a larger buffer: the data
+    pointer is 4-byte aligned only."""
+    a = np.ascontiguousarray(a, np.float32)
+    buf = torch.empty(a.size + 1, dtype=torch.float32, device=dev)
+    view = buf[1:].view(a.shape)
+    view.copy_(torch.as_tensor(a))
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
 def run_hip(s, dev, tile_rows=None, colors_precomp=None, cov3D_precomp=None, extras=ALL_EXTRAS,
-            binning=True, debug=False, radii=True):
+            binning=True, debug=False, radii=True, slot=0, unaligned=False):
+    """unaligned: shs, rotations and means3D at pointers that are not 16-byte aligned."""
     g = s["g"]
     P = len(g.xyz)
-    sh = None if colors_precomp is not None else to_dev(g.sh.reshape(P, g.sh.shape[-1] // 3, 3), dev)
+    up = to_dev_unaligned if unaligned else to_dev
+    sh = None if colors_precomp is not None else up(g.sh.reshape(P, g.sh.shape[-1] // 3, 3), dev)
     use_sr = cov3D_precomp is None
     res = rasterize_gaussians_native(
-        to_dev(s["bg"], dev), to_dev(g.xyz, dev), to_dev(colors_precomp, dev),
+        to_dev(s["bg"], dev), up(g.xyz, dev), to_dev(colors_precomp, dev),
         to_dev(g.opacity, dev), to_dev(g.scale, dev) if use_sr else None,
-        to_dev(g.rot, dev) if use_sr else None, s["scale_modifier"], to_dev(cov3D_precomp, dev),
+        up(g.rot, dev) if use_sr else None, s["scale_modifier"], to_dev(cov3D_precomp, dev),
         to_dev(s["view"], dev), to_dev(s["proj"], dev), s["tx"], s["ty"], s["H"], s["W"], sh,
         s["sh_degree"], to_dev(s["campos"], dev), False, debug, tile_rows=tile_rows,
-        extras=extras, radii=radii)
+        extras=extras, radii=radii, slot=slot)
     out = {"num_rendered": res.num_rendered, "color": res.color.cpu().numpy(),
            "radii": None if res.radii is None else res.radii.cpu().numpy()}
     for k, v in res.extras.items():
@@ -73,7 +86,7 @@ def run_hip(s, dev, tile_rows=None, colors_precomp=None, cov3D_precomp=None, ext
     if "n_contrib" in out:
         out["n_contrib"] = out["n_contrib"].view(np.uint32)
     if binning:
-        pl, pt, rg = binning_state(dev.index or 0)
+        pl, pt, rg = binning_state(dev.index or 0, slot)
         out["point_list"] = pl.cpu().numpy().view(np.uint32)
         out["point_tiles"] = pt.cpu().numpy().view(np.uint32)
         out["ranges"] = rg.cpu().numpy().view(np.uint32)

@@ -43,13 +43,44 @@ def tp44(p, M):
 
 
 def f2i(v):
+    """CUDA's cvt.rzi.s32.f32: truncate, saturate, NaN -> 0."""
+    v = float(v)
     if math.isnan(v):
         return 0
-    return int(max(min(math.trunc(float(v)), 2**31 - 1), -2**31))
+    if v >= 2147483648.0:
+        return 2**31 - 1
+    if v <= -2147483648.0:
+        return -2**31
+    return math.trunc(v)
 
 
-def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D):
-    M_ = 16 if g.sh.shape[1] == 48 else 1
+def fmax(a, b):
+    """C fmaxf: the other operand where one is NaN."""
+    if a != a:
+        return b
+    return a if (b != b or a >= b) else b
+
+
+def fmin(a, b):
+    if a != a:
+        return b
+    return a if (b != b or a <= b) else b
+
+
+def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D, scale_modifier=1.0,
+                  cov3D_precomp=None, colors_precomp=None):
+    """One Gaussian through upstream's preprocessCUDA in float32, operation by operation; None
+    where it is culled.  A saturated radius <= 0 (NaN radius) is culled: upstream's
+    duplicateWithKeys skips it.  cov3D_precomp (P, 6) replaces scale / rotation; with
+    colors_precomp no colour is computed (rgb None).  M = g.sh.shape[1] / 3 coefficients."""
+    with np.errstate(all="ignore"):
+        return _py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D, scale_modifier,
+                              cov3D_precomp, colors_precomp)
+
+
+def _py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D, scale_modifier, cov3D_precomp,
+                   colors_precomp):
+    M_ = g.sh.shape[1] // 3
     p = [f32(v) for v in g.xyz[i]]
     pv = tp43(p, view)
     if not pv[2] > f32(0.2):
@@ -57,24 +88,30 @@ def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D):
     ph = tp44(p, proj)
     pw = f32(f32(1) / f32(ph[3] + f32(1e-7)))
     pp = [f32(ph[0] * pw), f32(ph[1] * pw)]
-    s = g.scale[i]
-    S = mat3_cols(1, 0, 0, 0, 1, 0, 0, 0, 1)
-    S[0][0], S[1][1], S[2][2] = f32(f32(1) * s[0]), f32(f32(1) * s[1]), f32(f32(1) * s[2])
-    r, x, y, z = [f32(v) for v in g.rot[i]]
-    two, one = f32(2), f32(1)
-    R = mat3_cols(one - two * f32(y * y + z * z), two * f32(x * y - r * z), two * f32(x * z + r * y),
-                  two * f32(x * y + r * z), one - two * f32(x * x + z * z), two * f32(y * z - r * x),
-                  two * f32(x * z - r * y), two * f32(y * z + r * x), one - two * f32(x * x + y * y))
-    Mm = mat3_mul(S, R)
-    Sig = mat3_mul(transpose(Mm), Mm)
-    c = [Sig[0][0], Sig[0][1], Sig[0][2], Sig[1][1], Sig[1][2], Sig[2][2]]
+    if cov3D_precomp is not None:
+        c = [f32(v) for v in cov3D_precomp[i]]
+    else:
+        s = g.scale[i]
+        mod = f32(scale_modifier)
+        S = mat3_cols(1, 0, 0, 0, 1, 0, 0, 0, 1)
+        S[0][0], S[1][1], S[2][2] = f32(mod * s[0]), f32(mod * s[1]), f32(mod * s[2])
+        r, x, y, z = [f32(v) for v in g.rot[i]]
+        two, one = f32(2), f32(1)
+        R = mat3_cols(one - two * f32(y * y + z * z), two * f32(x * y - r * z),
+                      two * f32(x * z + r * y), two * f32(x * y + r * z),
+                      one - two * f32(x * x + z * z), two * f32(y * z - r * x),
+                      two * f32(x * z - r * y), two * f32(y * z + r * x),
+                      one - two * f32(x * x + y * y))
+        Mm = mat3_mul(S, R)
+        Sig = mat3_mul(transpose(Mm), Mm)
+        c = [Sig[0][0], Sig[0][1], Sig[0][2], Sig[1][1], Sig[1][2], Sig[2][2]]
     fy = f32(f32(H) / f32(f32(2) * f32(ty)))
     fx = f32(f32(W) / f32(f32(2) * f32(tx)))
     t = list(pv)
     limx, limy = f32(f32(1.3) * f32(tx)), f32(f32(1.3) * f32(ty))
     txtz, tytz = f32(t[0] / t[2]), f32(t[1] / t[2])
-    t[0] = f32(min(limx, max(-limx, txtz)) * t[2])
-    t[1] = f32(min(limy, max(-limy, tytz)) * t[2])
+    t[0] = f32(fmin(limx, fmax(-limx, txtz)) * t[2])
+    t[1] = f32(fmin(limy, fmax(-limy, tytz)) * t[2])
     tz2 = f32(t[2] * t[2])
     J = mat3_cols(f32(fx / t[2]), 0, f32(-f32(fx * t[0]) / tz2), 0, f32(fy / t[2]),
                   f32(-f32(fy * t[1]) / tz2), 0, 0, 0)
@@ -89,12 +126,14 @@ def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D):
     di = f32(f32(1) / det)
     conic = (f32(cc * di), f32(-b * di), f32(a * di))
     mid = f32(f32(0.5) * f32(a + cc))
-    l1 = f32(mid + np.sqrt(max(f32(0.1), f32(f32(mid * mid) - det)), dtype=f32))
-    l2 = f32(mid - np.sqrt(max(f32(0.1), f32(f32(mid * mid) - det)), dtype=f32))
-    rad = f32(math.ceil(f32(f32(3) * np.sqrt(max(l1, l2), dtype=f32))))
+    l1 = f32(mid + np.sqrt(fmax(f32(0.1), f32(f32(mid * mid) - det)), dtype=f32))
+    l2 = f32(mid - np.sqrt(fmax(f32(0.1), f32(f32(mid * mid) - det)), dtype=f32))
+    rad = np.ceil(f32(f32(3) * np.sqrt(fmax(l1, l2), dtype=f32)))
     px = f32(((float(pp[0]) + 1.0) * W - 1.0) * 0.5)
     py = f32(((float(pp[1]) + 1.0) * H - 1.0) * 0.5)
     ri = f2i(rad)
+    if ri <= 0:
+        return None
     gx, gy = (W + 15) // 16, (H + 15) // 16
     rect = (min(gx, max(0, f2i(f32(f32(px - f32(ri)) / f32(16))))),
             min(gy, max(0, f2i(f32(f32(py - f32(ri)) / f32(16))))),
@@ -102,6 +141,10 @@ def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D):
             min(gy, max(0, f2i(f32(f32(f32(f32(py + f32(ri)) + f32(16)) - f32(1)) / f32(16))))))
     if (rect[2] - rect[0]) * (rect[3] - rect[1]) == 0:
         return None
+    geom = dict(depth=pv[2], radius=ri, xy=(px, py), conic=conic, rect=rect, det=det,
+                tiles=(rect[2] - rect[0]) * (rect[3] - rect[1]))
+    if colors_precomp is not None:
+        return dict(geom, rgb=None)
     # SH (deg <= 3), upstream computeColorFromSH
     pos = [f32(v) for v in g.xyz[i]]
     d = [f32(pos[k] - f32(campos[k])) for k in range(3)]
@@ -143,9 +186,8 @@ def py_preprocess(i, g, view, proj, campos, tx, ty, W, H, D):
                     for m in range(7):
                         acc = f32(acc + f32(e[m] * sh[9 + m][k]))
                     res[k] = acc
-    rgb = [max(f32(v + f32(0.5)), f32(0)) for v in res]
-    return dict(depth=pv[2], radius=ri, xy=(px, py), conic=conic, rgb=rgb,
-                tiles=(rect[2] - rect[0]) * (rect[3] - rect[1]))
+    rgb = [fmax(f32(v + f32(0.5)), f32(0)) for v in res]
+    return dict(geom, rgb=rgb)
 
 
 @pytest.mark.parametrize("sh_degree,seed", [(3, 5), (0, 6)])
