@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "gsr_set_timing", "gsr_stage_times", "gsr_stage_name", "gsr_set_option",
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
-    "gsr_forward_shaded",
+    "gsr_forward_shaded", "gsr_forward_depth",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -76,6 +76,11 @@ class GsrOutputs(ctypes.Structure):
     ]
 
 
+class GsrDepthOutputs(ctypes.Structure):
+    """gsr_depth_outputs: gsr_forward_depth's optional per-pixel planes."""
+    _fields_ = [("depth_map", ctypes.c_void_p), ("inv_depth_map", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -102,6 +107,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gsr_forward_shaded.argtypes = [vp, ctypes.POINTER(GsrGaussians),
                                        ctypes.POINTER(GsrRasterSettings),
                                        ctypes.POINTER(GsrOutputs), ctypes.c_int32, vp]
+    # (an older build of ABI 4 loaded through GSR_LIB lacks it: forward_depth() says so)
+    if hasattr(lib, "gsr_forward_depth"):
+        lib.gsr_forward_depth.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                          ctypes.POINTER(GsrRasterSettings),
+                                          ctypes.POINTER(GsrOutputs),
+                                          ctypes.POINTER(GsrDepthOutputs), vp]
+        lib.gsr_forward_depth.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -146,6 +158,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             raise RuntimeError(f"libgsr.so ABI version {ver} != expected {ABI_VERSION}")
         _lib = lib
         return lib
+
+
+def forward_depth_fn(lib: ctypes.CDLL):
+    """gsr_forward_depth of a loaded library; RuntimeError if that build does not have it."""
+    fn = getattr(lib, "gsr_forward_depth", None)
+    if fn is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_forward_depth: the depth_map / inv_depth_map outputs need a "
+            "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
+    return fn
 
 
 def check(rc: int, what: str) -> int:

@@ -13,6 +13,7 @@
 //   5 row pass          = tile-sort pass 2 (radix_sort.hip)
 //   6 join                                          <- join
 //   7 blend             (blend.hip)               gsr_forward_shaded: a GL shading's first-hit kernel
+//                                                  gsr_forward_depth: the depth-accumulating composite
 //
 // Binning has two forms with identical results: the column-first form above (default), and the
 // per-pair form (offsets scan -> duplicate fused with the first tile-sort pass -> the remaining
@@ -110,7 +111,9 @@ constexpr int64_t kMinListCap = 1 << 16;
 // workspace (named by its generation): a forward whose key equals a recorded one replays it.
 // The shading (gsr_forward_shaded) reaches the recorded chains only through `tight` -- the
 // billboard's full lists -- and selects the blend's kernel, which is launched directly after
-// them: frames of different shadings and equal lists share their graphs.
+// them: frames of different shadings and equal lists share their graphs.  So do depth frames
+// (gsr_forward_depth) and plain ones: the planes are arguments of that direct launch alone, and the
+// depth keys it reads are written by the preprocess, which is a direct launch too.
 struct GraphKey {
     uint64_t ws_gen;
     int64_t cap, P;
@@ -349,6 +352,8 @@ struct Frame {
     GsrPreprocessArgs pa;
     bool tight;  // tight binning: pairs only over the span words (needs the column-first form)
     int shading = GSR_SHADE_SPLAT;  // gsr_forward_shaded: the kernel of stage 7
+    // gsr_forward_depth: the planes stage 7 also fills (both NULL: the plain composite)
+    float *depth_map = nullptr, *inv_depth_map = nullptr;
     uint64_t K = 0;   // upstream's num_rendered
     uint64_t KL = 0;  // pairs in the list (K, or fewer with tight binning)
     // the pair list the blend reads and gsr_get_binning exports
@@ -812,6 +817,14 @@ int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st
         GSR_HIP(gsr_launch_shade(ba, f.shading, f.s), "shade launch");
         return GSR_OK;
     }
+    if (f.depth_map || f.inv_depth_map) {
+        // z by Gaussian id from the depth keys: written by this frame's preprocess on f.s and only
+        // read since (the depth sort takes them const); the next writer is the next call's
+        // preprocess or gsr_depth_argsort, queued behind this blend (order_stream)
+        const GsrDepthArgs da{f.pa.sort_keys, f.depth_map, f.inv_depth_map};
+        GSR_HIP(gsr_launch_blend_depth(ba, da, f.s), "depth blend launch");
+        return GSR_OK;
+    }
     GSR_HIP(gsr_launch_blend(ba, f.s), "blend launch");
     return GSR_OK;
 }
@@ -1099,10 +1112,11 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 }
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-            gsr_outputs *out, hipStream_t s, int shading) {
+            gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth) {
     Frame f;
     ctx->last.valid = false;
     GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
+    if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
@@ -1123,12 +1137,17 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         ctx->list_cap = list_capacity((int64_t)f.KL, ctx->list_cap);
         GSR_TRY(reserve_K(ctx, ctx->list_cap, s));
         GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
+        if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
         f.graph = false;
     }
 
     if (f.P == 0) {  // upstream returns the zero-initialised image without rendering
         GSR_HIP(hipMemsetAsync(out->color, 0, (size_t)3 * f.rows_out * f.W * sizeof(float), s),
                 "hipMemsetAsync(color)");
+        for (float *plane : {f.depth_map, f.inv_depth_map})
+            if (plane)
+                GSR_HIP(hipMemsetAsync(plane, 0, (size_t)f.rows_out * f.W * sizeof(float), s),
+                        "hipMemsetAsync(depth plane)");
         GSR_HIP(hipMemsetAsync(ctx->ranges_words(), 0, f.T_strip * 8, s), "hipMemsetAsync");
         // an empty list in the per-pair form's buffers; no stage ran, so no timed frame
         f.K = f.KL = 0;
@@ -1374,7 +1393,15 @@ int gsr_forward_shaded(gsr_context *ctx, const gsr_gaussians *g, const gsr_raste
                                        std::to_string(shading) + " (GSR_SHADE_* 0..3)");
     std::lock_guard<std::mutex> lock(ctx->mu);
     GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), shading);
+    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), shading, nullptr);
+}
+
+int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                      gsr_outputs *out, const gsr_depth_outputs *depth, void *stream) {
+    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
+    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth);
 }
 
 int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,

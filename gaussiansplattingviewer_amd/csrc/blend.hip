@@ -168,8 +168,18 @@ struct StagedSplat {
 // blend's VALU; the extra pass over the lists cost more than it saved).
 // kContrib: track the last contributor (the n_contrib output); off (no n_contrib requested),
 // the composite step loses one v_cndmask.
-template <bool kFast, bool kContrib>
-__global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32_t n_tiles) {
+//
+// kDepth (k_blend_depth_q, gsr_forward_depth): two more accumulators per pixel, the expected
+// view-space depth and inverse depth sum z w and sum (1/z) w over the very splats and with the very
+// weight w of the colour channels (a colour channel with the feature in place of the colour: the
+// twin property).  z is gathered by Gaussian id from the depth keys (its bits,
+// preprocess.hip back_one), 1/z is one IEEE division per staged splat, and the pair {z0, 1/z0,
+// z1, 1/z1} lies in 16 B of LDS of its own (the paired-slot layout has no spare word in e): one
+// more LDS read per composited pair.  The pad slot of an odd count holds 0, 0 (weight 0 times a
+// finite feature).  Without kDepth none of it is compiled: k_blend_q is the kernel it was.
+template <bool kFast, bool kContrib, bool kDepth>
+__device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
+                                        const GsrDepthArgs &d) {
     __shared__ StagedSplat s_spl_q[4][64];  // per quadrant wave
     constexpr bool kPair = kFast && !kContrib;  // paired colour / bound words (see staging)
 
@@ -179,6 +189,11 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
     const uint32_t quad = threadIdx.x >> 6;  // this wave's quadrant
     const int lane = threadIdx.x & 63;
     StagedSplat *const s_spl = s_spl_q[quad];
+    float2 *s_zf = nullptr;  // kDepth: {z, 1 / z} of the staged splats, slot for slot
+    if constexpr (kDepth) {
+        __shared__ alignas(16) float2 s_zf_q[4][64];  // (a pair: one 16-B read)
+        s_zf = s_zf_q[quad];
+    }
     const uint32_t tx = tile % a.grid_x, ty_local = tile / a.grid_x, ty = a.row_begin + ty_local;
     const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
     const int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
@@ -192,13 +207,14 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
     const uint2 range = a.ranges[tile];
     // done carried in the sign of T (T <= 0: the lane composites no more)
     float T = inside ? 1.0f : -1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+    float D0 = 0.0f, D1 = 0.0f;  // kDepth: sum z w, sum (1 / z) w
     uint32_t last_contributor = 0;
     auto live_any = [&]() { return __ballot(!(T <= 0.0f)) != 0ull; };
     if (!live_any()) return;
 
     // kBound (fast form): test upstream's power > 0 skip as p > bound -- only chunks holding a
     // conic that is not positive definite need it (staging below)
-    auto composite = [&](const StagedSplat &sp, auto bound_tag) {
+    auto composite = [&](const StagedSplat &sp, float fz, float fiz, auto bound_tag) {
         constexpr bool kBound = decltype(bound_tag)::value;
         bool vis, acc, term;
         float test_T;
@@ -224,6 +240,10 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
             C0 = __builtin_fmaf(sp.q.z, wgt, C0);
             C1 = __builtin_fmaf(sp.q.w, wgt, C1);
             C2 = __builtin_fmaf(sp.e.x, wgt, C2);
+            if constexpr (kDepth) {
+                D0 = __builtin_fmaf(fz, wgt, D0);
+                D1 = __builtin_fmaf(fiz, wgt, D1);
+            }
             if (kContrib)
                 last_contributor = (vis && !lo) ? __float_as_uint(sp.e.y) : last_contributor;
             T = T_next;
@@ -240,6 +260,10 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
             C0 = acc ? C0 + sp.q.z * alpha * T : C0;
             C1 = acc ? C1 + sp.q.w * alpha * T : C1;
             C2 = acc ? C2 + sp.e.x * alpha * T : C2;
+            if constexpr (kDepth) {
+                D0 = acc ? D0 + fz * alpha * T : D0;
+                D1 = acc ? D1 + fiz * alpha * T : D1;
+            }
         }
         T = acc ? test_T : (term ? -fabsf(T) : T);
         if (kContrib) last_contributor = acc ? __float_as_uint(sp.e.y) : last_contributor;
@@ -254,6 +278,9 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
         const bool valid = idx < range.y;
         SplatRecord r;
         if (valid) r = a.records[id_next];
+        float z = 1.0f;  // kDepth: by Gaussian id, as the record
+        if constexpr (kDepth)
+            if (valid) z = __uint_as_float(d.z_bits[id_next]);
         if (idx + 64u < range.y) id_next = (a.point_list[idx + 64u] & a.id_mask);
 
         bool keep = valid;
@@ -317,6 +344,7 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
             } else {
                 s_spl[slot] = st;
             }
+            if constexpr (kDepth) s_zf[slot] = make_float2(z, 1.0f / z);
         }
         int count = __popcll(bal);
         if (count == 0) continue;
@@ -334,6 +362,8 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
                 reinterpret_cast<float *>(&s_spl[count])[lane] =
                     (kFast && (lane == 0 || lane == 10)) ? -__builtin_huge_valf() : 0.0f;
             }
+            if constexpr (kDepth)
+                if (lane == 12) s_zf[count] = make_float2(0.0f, 0.0f);
             ++count;
         }
         // one wave: its LDS writes above complete before the reads below are served
@@ -342,17 +372,19 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
         // during this pair) spilled past 64 VGPRs and was slower
         auto composite_all = [&](auto bound_tag) {
             for (int k = 0; k < count; k += 2) {
+                float4 zf = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pair's {z, 1 / z}
+                if constexpr (kDepth) zf = *reinterpret_cast<const float4 *>(&s_zf[k]);
                 if (kPair) {
                     const float4 e = s_spl[k].e;
                     composite(StagedSplat{s_spl[k].g, s_spl[k].q, make_float4(e.x, 0.0f, e.z, 0.0f)},
-                              bound_tag);
+                              zf.x, zf.y, bound_tag);
                     composite(StagedSplat{s_spl[k + 1].g, s_spl[k + 1].q,
                                           make_float4(e.y, 0.0f, e.w, 0.0f)},
-                              bound_tag);
+                              zf.z, zf.w, bound_tag);
                 } else {
                     const StagedSplat a0 = s_spl[k], a1 = s_spl[k + 1];
-                    composite(a0, bound_tag);
-                    composite(a1, bound_tag);
+                    composite(a0, zf.x, zf.y, bound_tag);
+                    composite(a1, zf.z, zf.w, bound_tag);
                 }
             }
         };
@@ -374,7 +406,26 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
         a.out_color[pid] = C0 + Tf * a.bg[0];
         a.out_color[plane + pid] = C1 + Tf * a.bg[1];
         a.out_color[2 * plane + pid] = C2 + Tf * a.bg[2];
+        if constexpr (kDepth) {  // premultiplied, no background term
+            if (d.depth_map) d.depth_map[pid] = D0;
+            if (d.inv_depth_map) d.inv_depth_map[pid] = D1;
+        }
     }
+}
+
+template <bool kFast, bool kContrib>
+__global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32_t n_tiles) {
+    blend_q<kFast, kContrib, false>(a, n_tiles, GsrDepthArgs{});
+}
+
+// The depth-accumulating form: 14 KiB of LDS per block; kDepthWaves waves per SIMD leave it the
+// registers for the two accumulators and the pair's features without scratch.
+constexpr int kDepthWaves = 6;
+template <bool kFast, bool kContrib>
+__global__ __launch_bounds__(256, kDepthWaves) void k_blend_depth_q(const GsrBlendArgs a,
+                                                                    uint32_t n_tiles,
+                                                                    const GsrDepthArgs d) {
+    blend_q<kFast, kContrib, true>(a, n_tiles, d);
 }
 
 // Grid of whole XCD groups: one block per tile, kGroupTiles per XCD round; blocks past the
@@ -558,5 +609,19 @@ hipError_t gsr_launch_blend(const GsrBlendArgs &a, hipStream_t s) {
         hipLaunchKernelGGL((k_blend_q<true, true>), grid, dim3(256), 0, s, a, n_tiles);
     else
         hipLaunchKernelGGL((k_blend_q<false, true>), grid, dim3(256), 0, s, a, n_tiles);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_blend_depth(const GsrBlendArgs &a, const GsrDepthArgs &d, hipStream_t s) {
+    if (!d.z_bits || (!d.depth_map && !d.inv_depth_map)) return hipErrorInvalidValue;
+    if (a.rows_tiles == 0 || a.grid_x == 0) return hipSuccess;
+    const uint32_t n_tiles = a.grid_x * a.rows_tiles;
+    const dim3 grid(xcd_grid(n_tiles));
+    if (a.fast && !a.n_contrib)
+        hipLaunchKernelGGL((k_blend_depth_q<true, false>), grid, dim3(256), 0, s, a, n_tiles, d);
+    else if (a.fast)
+        hipLaunchKernelGGL((k_blend_depth_q<true, true>), grid, dim3(256), 0, s, a, n_tiles, d);
+    else
+        hipLaunchKernelGGL((k_blend_depth_q<false, true>), grid, dim3(256), 0, s, a, n_tiles, d);
     return hipGetLastError();
 }

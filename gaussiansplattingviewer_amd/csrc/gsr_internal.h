@@ -520,6 +520,15 @@ struct GsrBlendArgs {
     uint32_t list_cap;
 };
 hipError_t gsr_launch_blend(const GsrBlendArgs &a, hipStream_t s);
+// gsr_forward_depth's planes (blend.hip k_blend_depth_q): the composite of gsr_launch_blend, which
+// also accumulates z and 1 / z under the colour's weights.  z_bits: per Gaussian, the bits of its
+// view-space z -- the depth keys (GsrPreprocessArgs.sort_keys), read by the ids of the list; either
+// plane may be NULL (not both), [rows_out, W] strip-local like final_T.
+struct GsrDepthArgs {
+    const uint32_t *z_bits;
+    float *depth_map, *inv_depth_map;
+};
+hipError_t gsr_launch_blend_depth(const GsrBlendArgs &a, const GsrDepthArgs &d, hipStream_t s);
 // The GL backend's geometry shadings in place of the composite (blend.hip k_shade_q): shading =
 // GSR_SHADE_BILLBOARD / FLAT_BALL / GAUSS_BALL.  Same arguments; a.fast is not read.
 hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);

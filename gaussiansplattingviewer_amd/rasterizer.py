@@ -78,7 +78,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     Extensions (keyword-only, for the strip partition and the parity tests):
       tile_rows -- (begin, end) 16-px tile rows to render; the image is then strip-local;
       extras    -- names of intermediates to return: depths, means2D, conic_opacity, rgb,
-                   tiles_touched, final_T, n_contrib;
+                   tiles_touched, final_T, n_contrib; and the per-pixel planes depth_map,
+                   inv_depth_map, (rows, W) float32: the sums of z and 1 / z under the colour's
+                   weights, premultiplied (gsr_forward_depth in include/gsr.h; `depths` stays the
+                   per-Gaussian view-space z).  Splat composite only: RuntimeError with a shading;
       stream    -- HIP stream handle (default: torch's current stream);
       slot      -- context slot (`_lib.context`): forwards in different slots may overlap;
       out_color -- preallocated contiguous f32 (3, rows, W) output (e.g. a gather buffer);
@@ -93,6 +96,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     if not radii and (tile_rows is None or any(
             n in extras for n in ("depths", "means2D", "conic_opacity", "rgb", "tiles_touched"))):
         raise RuntimeError("radii=False needs tile_rows and no per-Gaussian extras")
+    depth_planes = [n for n in ("depth_map", "inv_depth_map") if n in extras]
+    if depth_planes and shading != _lib.GSR_SHADE_SPLAT:
+        raise RuntimeError("depth_map / inv_depth_map come from the splat composite: not "
+                           f"available with shading {shading}")
     device = _device_of(means3D)
     dev_index = device.index if device.index is not None else torch.cuda.current_device()
     P = int(means3D.size(0))
@@ -146,7 +153,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
             ext[name] = torch.zeros((P, 3), **f32)
         elif name == "tiles_touched":
             ext[name] = torch.zeros((P,), dtype=torch.int32, device=device)
-        elif name == "final_T":
+        elif name in ("final_T", "depth_map", "inv_depth_map"):
             ext[name] = torch.zeros((rows, W), **f32)
         elif name == "n_contrib":
             ext[name] = torch.zeros((rows, W), dtype=torch.int32, device=device)
@@ -166,13 +173,19 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     out = _lib.GsrOutputs(color=color.data_ptr(),
                           radii=radii.data_ptr() if P and radii is not None else None)
     for name, t in ext.items():
-        setattr(out, name, t.data_ptr())
+        if name not in depth_planes:
+            setattr(out, name, t.data_ptr())
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     with torch.cuda.device(dev_index):
-        if shading == _lib.GSR_SHADE_SPLAT:
+        if depth_planes:
+            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
+            _lib.check(_lib.forward_depth_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st),
+                                                  ctypes.byref(out), ctypes.byref(planes),
+                                                  ctypes.c_void_p(stream)), "gsr_forward_depth")
+        elif shading == _lib.GSR_SHADE_SPLAT:
             _lib.check(lib.gsr_forward(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
                                        ctypes.c_void_p(stream)), "gsr_forward")
         else:

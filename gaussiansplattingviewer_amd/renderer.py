@@ -81,8 +81,25 @@ def gaus_hip_from_cpu(gau, device="cuda") -> GaussianDataHIP:
     return g
 
 
-class HIPRenderer(GaussianRenderBase):
-    """CUDARenderer's behaviour on the MI355X rasterizer (no GL)."""
+class _RendererOptions(type):
+    """HIPRenderer(w, h, ..., depth_maps=False): the keyword is taken at construction, here,
+    because `__init__`'s parameter list is pinned as it stands (tests/test_shading_reference.py
+    test_python_api_carries_the_shading compares it name for name)."""
+
+    def __call__(cls, *args, depth_maps=False, **kw):
+        r = super().__call__(*args, **kw)
+        r.depth_maps = bool(depth_maps)
+        return r
+
+
+class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
+    """CUDARenderer's behaviour on the MI355X rasterizer (no GL).
+
+    depth_maps (keyword, default False): draw() also leaves the blend pass's per-pixel planes
+    (gsr_forward_depth) in self.depth_map / self.inv_depth_map / self.final_T, (rows, W) float32
+    beside self.image; None under a GL shading (nothing is composited there).  It then renders
+    through rasterize_gaussians_native (ctypes) for full frames too: the `_C` entry points keep
+    upstream's signatures.  False: nothing changes."""
 
     # GL render_mod -> gsr_forward_shaded's shading (gau_frag.glsl:15-38)
     GL_SHADINGS = {-2: _lib.GSR_SHADE_BILLBOARD, -3: _lib.GSR_SHADE_FLAT_BALL,
@@ -91,6 +108,8 @@ class HIPRenderer(GaussianRenderBase):
     def __init__(self, w, h, device="cuda", tile_rows=None, gl_shading=False):
         super().__init__()
         self.gl_shading = bool(gl_shading)  # render the GL backend's ball / billboard modes
+        self.depth_maps = False  # (set by the constructor's depth_maps keyword)
+        self.depth_map = self.inv_depth_map = self.final_T = None
         self.device = torch.device(device)
         self.raster_settings = {
             "image_height": int(h),
@@ -196,8 +215,17 @@ class HIPRenderer(GaussianRenderBase):
             settings["shading"] = self.GL_SHADINGS[self.render_mod]
             settings["sh_degree"] = 0
         rs = GaussianRasterizationSettings(**settings)
+        planes = {}
         with torch.no_grad():
-            if self.tile_rows is None:
+            if self.depth_maps:
+                extras = () if rs.shading else ("depth_map", "inv_depth_map", "final_T")
+                res = rasterize_gaussians_native(
+                    rs.bg, g.xyz, colors, g.opacity, g.scale, g.rot, rs.scale_modifier, None,
+                    rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
+                    rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug,
+                    tile_rows=self.tile_rows, shading=rs.shading, extras=extras)
+                img, radii, planes = res.color, res.radii, res.extras
+            elif self.tile_rows is None:
                 img, radii = GaussianRasterizer(raster_settings=rs)(
                     means3D=g.xyz, means2D=None, shs=shs, colors_precomp=colors,
                     opacities=g.opacity, scales=g.scale, rotations=g.rot, cov3D_precomp=None)
@@ -209,6 +237,9 @@ class HIPRenderer(GaussianRenderBase):
                     tile_rows=self.tile_rows, shading=rs.shading)
                 img, radii = res.color, res.radii
         self.image, self.radii = img, radii
+        if self.depth_maps:
+            self.depth_map, self.inv_depth_map = planes.get("depth_map"), planes.get("inv_depth_map")
+            self.final_T = planes.get("final_T")
         return img
 
     def rgba(self) -> torch.Tensor:

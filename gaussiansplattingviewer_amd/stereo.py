@@ -11,6 +11,9 @@ FBO readbacks).  Here the same three images come from the HIP rasterizer:
 * `pack_image` -- the device packer (`gsr_pack_image`): RGB8 as glReadPixels(GL_RGB,
   GL_UNSIGNED_BYTE) converts, uint16 = disparity * 65535 truncated (main.py:873-874), or the
   HWC RGBA float of renderer_cuda.py:226-228;
+* `metric_disparity` -- the left view's disparity in pixels, fx |B| / z, from the inverse-depth
+  plane of the left image's own blend pass (`gsr_forward_depth`): metric, pixel-aligned with
+  the left image, and no third forward (`StereoCapture(disparity="metric")`);
 * `StereoCapture` -- the capture sequence of main.py:843-917 (left pose, disparity with the
   left pose still bound, right pose) on a `HIPRenderer`, returning device tensors; `save`
   writes the PNGs (PIL) the way the viewer names them.
@@ -94,44 +97,100 @@ def pack_image(image: torch.Tensor, fmt: str, flip_rows: bool = False,
     return out
 
 
+def metric_disparity(inv_depth_map: torch.Tensor, final_T: torch.Tensor, tanfovx: float,
+                     width: int, baseline: float = BASELINE, normalise: bool = True) -> torch.Tensor:
+    """Disparity in pixels, float32 (H, W), of a rectified pair whose right view is the left one
+    translated by `baseline` along view-space x (colmap.py load_camera_positions):
+    fx |baseline| / z with fx = width / (2 tanfovx), linear in inverse depth.  inv_depth_map and
+    final_T are the left frame's planes (premultiplied sum of w / z; transmittance).  normalise:
+    divided by the covered share 1 - final_T where that is > 0, else 0 (no surface); False
+    returns the premultiplied map.  Plain torch ops: device or host tensors."""
+    inv = inv_depth_map.to(torch.float32)
+    scale = float(width) / (2.0 * float(tanfovx)) * abs(float(baseline))
+    d = inv * scale
+    if not normalise:
+        return d
+    cover = 1.0 - final_T.to(torch.float32)
+    # (the quotient where cover <= 0 is discarded: five element-wise kernels in all)
+    return torch.where(cover > 0, d / cover, torch.zeros((), dtype=d.dtype, device=d.device))
+
+
+def disparity_u16(disparity: torch.Tensor) -> torch.Tensor:
+    """The KITTI disparity PNG's values: uint16 = min(65535, round(256 d)), 0 = no surface;
+    returned as int32 (H, W) (torch's uint16 has no rounding ops), cast at the save."""
+    return torch.clamp(torch.round(disparity.to(torch.float32) * 256.0), 0, 65535).to(torch.int32)
+
+
 class StereoCapture:
     """main.py:839-923 on a HIPRenderer: left RGB, disparity, right RGB for one pose.
 
-    `render_mode` is the viewer's g_render_mode - 3 (default 3: full SH, main.py:99)."""
+    `render_mode` is the viewer's g_render_mode - 3 (default 3: full SH, main.py:99).
+    `disparity`: "gl" (default) the GL backend's mode -1 image as "depth", a third forward;
+    "metric" the left frame's own inverse-depth plane as "disparity" (metric_disparity, float32
+    pixels), two forwards -- the renderer must be a HIPRenderer(depth_maps=True); "both" all
+    four from three forwards."""
 
-    def __init__(self, renderer, camera, render_mode: int = 3):
+    DISPARITIES = ("gl", "metric", "both")
+
+    def __init__(self, renderer, camera, render_mode: int = 3, disparity: str = "gl"):
+        if disparity not in self.DISPARITIES:
+            raise ValueError(f"disparity must be one of {self.DISPARITIES}, not {disparity!r}")
+        if disparity != "gl" and not getattr(renderer, "depth_maps", False):
+            raise RuntimeError(f'disparity="{disparity}" needs HIPRenderer(..., depth_maps=True)')
         self.renderer = renderer
         self.camera = camera
         self.render_mode = int(render_mode)
+        self.disparity = disparity
 
     def render(self, camera_pose) -> dict:
         """One images.txt entry -> {"left": u8 (H,W,3), "depth": u16 (H,W), "right": u8
-        (H,W,3)} device tensors, in the viewer's draw order (main.py:845-900)."""
+        (H,W,3)} device tensors, in the viewer's draw order (main.py:845-900); with
+        disparity="metric" {"left", "right", "disparity": f32 (H,W) pixels}, "both" all four."""
         r, cam = self.renderer, self.camera
         pose_left, pose_right = load_camera_positions(camera_pose)
         r.update_camera_intrin(cam)                       # main.py:826-827
         r.set_render_mod(self.render_mode)                 # main.py:845
         r.sort_and_update(cam, True, pose_left)
         r.update_camera_pose(cam, True, pose_left)
-        left = pack_image(r.draw(), "rgb8")
-        r.set_render_mod(-1)                               # main.py:867-868: left pose bound
-        depth = pack_image(r.draw(), "r16")
-        r.set_render_mod(self.render_mode)                 # main.py:885-889
-        r.sort_and_update(cam, True, pose_right)
-        r.update_camera_pose(cam, True, pose_right)
-        right = pack_image(r.draw(), "rgb8")
-        return {"left": left, "depth": depth, "right": right}
+        out = {"left": pack_image(r.draw(), "rgb8")}
+        if self.disparity != "gl":
+            if r.inv_depth_map is None:
+                raise RuntimeError("the metric disparity needs the splat composite (render_mode "
+                                   f"{self.render_mode} is a GL shading)")
+            rs = r.raster_settings
+            out["disparity"] = metric_disparity(r.inv_depth_map, r.final_T, rs["tanfovx"],
+                                                rs["image_width"])
+        # only the left frame needs its planes (they stay in the renderer, the left view's)
+        planes, r.depth_maps = r.depth_maps, r.depth_maps and self.disparity == "gl"
+        try:
+            if self.disparity != "metric":
+                r.set_render_mod(-1)                       # main.py:867-868: left pose bound
+                out["depth"] = pack_image(r.draw(), "r16")
+            r.set_render_mod(self.render_mode)             # main.py:885-889
+            r.sort_and_update(cam, True, pose_right)
+            r.update_camera_pose(cam, True, pose_right)
+            out["right"] = pack_image(r.draw(), "rgb8")
+        finally:
+            r.depth_maps = planes
+        return out
 
     @staticmethod
     def save(frames: dict, out_dir: str, scene: str, pose_index: int) -> list[str]:
         """Write left/right RGB PNGs and the 16-bit disparity PNG under
-        out_dir/scene/{left,right,depth}/{pose_index}.png (main.py:701-712, 879, 916-917)."""
+        out_dir/scene/{left,right,depth}/{pose_index}.png (main.py:701-712, 879, 916-917); a
+        metric "disparity" as disparity/{pose_index}.png, uint16 = min(65535, round(256 d)) with
+        0 = no surface (the KITTI convention)."""
         from PIL import Image
         paths = []
-        for kind in ("left", "depth", "right"):
+        for kind in ("left", "depth", "disparity", "right"):
+            if kind not in frames:
+                continue
             d = os.path.join(out_dir, scene, kind)
             os.makedirs(d, exist_ok=True)
-            a = frames[kind].cpu().numpy()
+            if kind == "disparity":
+                a = disparity_u16(frames[kind]).cpu().numpy().astype(np.uint16)
+            else:
+                a = frames[kind].cpu().numpy()
             path = os.path.join(d, f"{pose_index}.png")
             Image.fromarray(a).save(path)
             paths.append(path)

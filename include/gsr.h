@@ -164,6 +164,38 @@ enum { GSR_SHADE_SPLAT = 0, GSR_SHADE_BILLBOARD = 1, GSR_SHADE_FLAT_BALL = 2,
 int gsr_forward_shaded(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                        gsr_outputs *out, int32_t shading, void *stream);
 
+/* gsr_forward (the splat composite) that also fills two optional per-pixel planes, strip-local
+ * like final_T ([rows, W] float32), from the same blend pass as the image:
+ *   depth_map[y,x]     = sum_k z_k       w_k      (expected view-space depth, premultiplied)
+ *   inv_depth_map[y,x] = sum_k (1 / z_k) w_k      (expected inverse depth, premultiplied)
+ * over exactly the splats the colour composites at that pixel (the list order, the power > 0 and
+ * alpha < 1/255 skips, the 0.99 cap and the T < 1e-4 termination are the colour's), with w_k the
+ * very weight of the colour channels in the context's arithmetic (GSR_OPT_BLEND_FAST 0: alpha T in
+ * upstream's order; 1: |T| - |T_next|, accumulated with one FMA).  z_k is the Gaussian's
+ * view-space z -- the bits of the `depths` output and of its depth-sort key -- and 1 / z_k the
+ * correctly rounded float32 quotient, computed once per staged splat.  A listed Gaussian has a
+ * finite z > 0.2.  So each plane is, bit for bit, a colour channel of a gsr_forward of the same
+ * scene with colors_precomp = (z, 1 / z, 0) and bg = 0 (tests/test_gpu_depth_maps.py).  There is
+ * no background term: a pixel that composites nothing is 0, and the expected depth of the covered
+ * part is depth_map / (1 - final_T), a division left to the caller.  A rectified stereo pair of
+ * baseline B has the disparity fx |B| / z in pixels, linear in inverse depth: inv_depth_map is the
+ * left image's pixel-aligned ground-truth disparity (stereo.metric_disparity).
+ * Everything else is the same gsr_forward call's, bit for bit: every gsr_outputs member,
+ * num_rendered and the lists gsr_get_binning exports.  A NULL struct or two NULL planes is
+ * gsr_forward itself (today's kernels, today's arguments); one plane gives the bits it has when
+ * both are asked for.  Strips (radii NULL included), debug, every option and every context work
+ * as in gsr_forward; GSR_OPT_BLEND_CULL and GSR_OPT_TIGHT_BINNING leave the planes bit-identical
+ * (a dropped splat has weight exactly 0).  Frame graphs: the blend is launched directly after the
+ * recorded chains with this call's pointers, so depth and plain frames share their graphs and
+ * nothing of a plane is recorded; a frame whose list outgrew the capacity writes no plane before
+ * it is rendered again.  The kernel is timed as the "blend" stage.  (Additive to ABI 4.) */
+typedef struct {
+    float *depth_map;     /* [rows, W] or NULL */
+    float *inv_depth_map; /* [rows, W] or NULL */
+} gsr_depth_outputs;
+int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                      gsr_outputs *out, const gsr_depth_outputs *depth, void *stream);
+
 /* Binning state of the last gsr_forward on this context: the pair lists its blend read.  Writes
  * the sizes (list_entries = K, the entries of the lists; num_tiles = T, tiles of the whole
  * frame) and, for each non-NULL caller-owned

@@ -12,7 +12,12 @@ host side (PIL, `--png` only, thread pool), plus the live HIP-event time of the 
 pack kernels against HBM peak (algorithmic bytes: disparity 24 B per Gaussian, RGB8 pack 15 B
 per pixel, uint16 pack 6 B per pixel).
 
+--disparity metric captures the left view's disparity from its own blend pass instead
+(StereoCapture(disparity="metric"): the inverse-depth plane of gsr_forward_depth, float32 pixels):
+two forwards per pose instead of three, and no disparity-colour or uint16 pack kernel.
+
 Usage: python tools/stereo_bench.py [--P 1000000] [--poses 60] [--warmup 5] [--png]
+                                    [--disparity {gl,metric}]
 """
 import argparse
 import json
@@ -84,6 +89,7 @@ def main():
     ap.add_argument("--poses", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--png", action="store_true")
+    ap.add_argument("--disparity", choices=("gl", "metric"), default="gl")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     W, H = colmap.VIEWER_RESOLUTION
@@ -92,9 +98,10 @@ def main():
         poses = colmap.read_images_txt(d)
     g = synthetic_gaussians(a.P, 3, 2)
     cam = Camera(H, W)
-    r = HIPRenderer(W, H, device=dev)
+    metric = a.disparity == "metric"
+    r = HIPRenderer(W, H, device=dev, depth_maps=metric)
     r.update_gaussian_data(g)
-    cap = StereoCapture(r, cam)
+    cap = StereoCapture(r, cam, disparity=a.disparity)
     for i in range(a.warmup):
         cap.render(poses[i % len(poses)])
     torch.cuda.synchronize()
@@ -115,6 +122,7 @@ def main():
 
     out = {"workload": f"stereo capture, {a.P} Gaussians SH3 (synthetic C3), {W}x{H}, "
                        f"{len(poses)} COLMAP orbit poses, left+disparity+right per pose",
+           "disparity": a.disparity, "forwards_per_pose": 2 if metric else 3,
            "poses": len(poses), "device_poses_per_s": round(len(poses) / dev_s, 1),
            "device_ms_per_pose": round(1e3 * dev_s / len(poses), 3),
            "to_host_poses_per_s": round(len(poses) / host_s, 1)}
