@@ -21,8 +21,22 @@ Same arguments, order and return arity; absent optional inputs are empty tensors
 passes them.  The work is `gsr_forward` / `gsr_mark_visible` in libgsr.so, on torch's current
 HIP stream, with one `gsr_context` per device held by the extension.  The three buffers are
 upstream's scratch (geometry, binning and image state, kept for the backward pass); this
-rasterizer is forward only and keeps that state inside its context (reused across frames), so
-they are returned as empty uint8 device tensors.
+rasterizer keeps its state inside its context (reused across frames) and its backward rebuilds
+what it needs from the inputs, so they are returned as empty uint8 device tensors.
+
+The backward (rasterize_points.cu `RasterizeGaussiansBackwardCUDA`, called by
+`_RasterizeGaussians.backward`):
+
+    dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, \\
+        dL_drotations = _C.rasterize_gaussians_backward(
+            bg, means3D, radii, colors_precomp, scales, rotations, scale_modifier, cov3D_precomp,
+            viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh, sh_degree, campos,
+            geomBuffer, num_rendered, binningBuffer, imgBuffer, debug, opacities)
+
+Upstream's 21 arguments in upstream's order and upstream's 8-tuple, plus ONE MORE trailing
+argument, `opacities`: upstream reads them out of geomBuffer, here nothing of the forward is kept
+and `gsr_backward` (include/gsr.h, which states the semantics) rebuilds the state from the
+inputs.  `radii`, `num_rendered` and the three buffers are accepted and ignored.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -31,7 +45,7 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
-                          rasterize_gaussians_shaded)
+                          rasterize_gaussians_backward, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "gsr_set_timing", "gsr_stage_times", "gsr_stage_name", "gsr_set_option",
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
-    "gsr_forward_shaded", "gsr_forward_depth",
+    "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -81,6 +81,20 @@ class GsrDepthOutputs(ctypes.Structure):
     _fields_ = [("depth_map", ctypes.c_void_p), ("inv_depth_map", ctypes.c_void_p)]
 
 
+class GsrBackwardInputs(ctypes.Structure):
+    """gsr_backward_inputs."""
+    _fields_ = [("dL_dcolor", ctypes.c_void_p)]
+
+
+GRADIENT_NAMES = ("dL_dmeans3D", "dL_dmeans2D", "dL_dopacity", "dL_dcolors", "dL_dconic",
+                  "dL_dsh", "dL_dscales", "dL_drotations", "dL_dcov3D")
+
+
+class GsrGradients(ctypes.Structure):
+    """gsr_gradients: every member optional (None = not wanted)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in GRADIENT_NAMES]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -114,6 +128,15 @@ def _declare(lib: ctypes.CDLL) -> None:
                                           ctypes.POINTER(GsrOutputs),
                                           ctypes.POINTER(GsrDepthOutputs), vp]
         lib.gsr_forward_depth.restype = i32
+    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_fn() says so)
+    if hasattr(lib, "gsr_backward"):
+        lib.gsr_backward.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                     ctypes.POINTER(GsrRasterSettings),
+                                     ctypes.POINTER(GsrBackwardInputs),
+                                     ctypes.POINTER(GsrGradients), vp]
+        lib.gsr_backward.restype = i32
+        lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
+        lib.gsr_backward_times.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -167,6 +190,16 @@ def forward_depth_fn(lib: ctypes.CDLL):
         raise RuntimeError(
             f"{LIB_PATH} has no gsr_forward_depth: the depth_map / inv_depth_map outputs need a "
             "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
+    return fn
+
+
+def backward_fn(lib: ctypes.CDLL):
+    """gsr_backward of a loaded library; RuntimeError if that build does not have it."""
+    fn = getattr(lib, "gsr_backward", None)
+    if fn is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_backward: gradients need a libgsr.so built from this tree "
+            "(include/gsr.h declares it; ABI 4, additive)")
     return fn
 
 

@@ -172,6 +172,14 @@ struct gsr_context {
     uint32_t *ranges_words() const { return reinterpret_cast<uint32_t *>(ranges_local.get()); }
     Buf<uint32_t> tile_diff{bufs};    // difference-array partials of the second-stream tile ranges
     Buf<uint32_t> blend_order{bufs};  // the blend's tile groups, heaviest first (second stream)
+    // gsr_backward: the per-Gaussian 2D gradient rows (kGradRow floats each) the blend's backward
+    // sums into, and the radii of the per-Gaussian stage it rebuilds
+    Buf<float> grad2d{bufs};
+    Buf<int32_t> bwd_radii{bufs};
+    // ... and the events around its three stages (rebuild, blend backward, per-Gaussian backward)
+    // of the last backward run under gsr_set_timing (created by the first one; gsr_backward_times)
+    hipEvent_t ev_bwd[4] = {};
+    bool bwd_timed = false;
     // frame graphs (64 B, from gsr_create): [0] tag, [1] list length, [4..6] campos
     Buf<uint32_t> frame_words{bufs};
     uint32_t *list_n() const { return frame_words.get() + 1; }
@@ -354,6 +362,7 @@ struct Frame {
     int shading = GSR_SHADE_SPLAT;  // gsr_forward_shaded: the kernel of stage 7
     // gsr_forward_depth: the planes stage 7 also fills (both NULL: the plain composite)
     float *depth_map = nullptr, *inv_depth_map = nullptr;
+    bool no_blend = false;  // gsr_backward's rebuild: everything up to the lists, no stage 7
     uint64_t K = 0;   // upstream's num_rendered
     uint64_t KL = 0;  // pairs in the list (K, or fewer with tight binning)
     // the pair list the blend reads and gsr_get_binning exports
@@ -871,7 +880,7 @@ int frame_tail(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st,
     if (ctx->second_stream)
         GSR_HIP(hipStreamWaitEvent(f.s, ctx->join, 0), "hipStreamWaitEvent(join)");
     GSR_TRY(stage_end(ctx, f, 5));
-    GSR_TRY(launch_blend(ctx, f, st, out));
+    if (!f.no_blend) GSR_TRY(launch_blend(ctx, f, st, out));
     return stage_end(ctx, f, 6);
 }
 
@@ -1112,11 +1121,13 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 }
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-            gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth) {
+            gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth,
+            bool no_blend = false) {
     Frame f;
     ctx->last.valid = false;
     GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
     if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
+    f.no_blend = no_blend;
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
@@ -1138,6 +1149,7 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         GSR_TRY(reserve_K(ctx, ctx->list_cap, s));
         GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
         if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
+        f.no_blend = no_blend;
         f.graph = false;
     }
 
@@ -1268,6 +1280,8 @@ void gsr_destroy(gsr_context *ctx) {
     for (auto &set : ctx->ev_color)
         for (auto &e : set)
             if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->ev_bwd)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->fork) (void)hipEventDestroy(ctx->fork);
     if (ctx->join) (void)hipEventDestroy(ctx->join);
     if (ctx->compacted) (void)hipEventDestroy(ctx->compacted);
@@ -1407,6 +1421,132 @@ int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster
 int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                 gsr_outputs *out, void *stream) {
     return gsr_forward_shaded(ctx, g, st, out, GSR_SHADE_SPLAT, stream);
+}
+
+// The gradients of the splat composite.  Everything is rebuilt from the arguments -- the
+// per-Gaussian stage, the depth sort and upstream's (untight) lists, the direct way: no recorded
+// graph is replayed, none is invalidated beyond what a forward of the same shape would -- so
+// nothing of an earlier forward on this context is read; then backward.hip's two kernels.
+int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                 const gsr_backward_inputs *in, gsr_gradients *gr, void *stream) {
+    if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, "gsr_backward: NULL argument");
+    if (st->tile_row_begin != 0 || st->tile_row_end != 0)
+        return fail(GSR_E_INVALID, "gsr_backward: whole frames only (a tile row strip is set)");
+    const int64_t P = g->P;
+    if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, "gsr_backward: bad P");
+    if (st->image_width <= 0 || st->image_height <= 0)
+        return fail(GSR_E_INVALID, "gsr_backward: image size must be positive");
+    if (P > 0) {
+        if (!in->dL_dcolor) return fail(GSR_E_INVALID, "gsr_backward: dL_dcolor is required");
+        if ((g->shs == nullptr) == (g->colors_precomp == nullptr))
+            return fail(GSR_E_INVALID,
+                        "Please provide excatly one of either SHs or precomputed colors!");
+        if (((g->scales == nullptr || g->rotations == nullptr) && g->cov3D_precomp == nullptr) ||
+            ((g->scales != nullptr || g->rotations != nullptr) && g->cov3D_precomp != nullptr))
+            return fail(GSR_E_INVALID, "Please provide exactly one of either scale/rotation pair "
+                                       "or precomputed 3D covariance!");
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GSR_TRY(order_stream(ctx, s));
+    if (P == 0) return GSR_OK;  // no Gaussian, no gradient
+    GSR_TRY(grow(ctx, ctx->grad2d, (size_t)P * kGradRow * sizeof(float), s));
+    GSR_TRY(grow(ctx, ctx->bwd_radii, (size_t)P * sizeof(int32_t), s));
+
+    // the rebuild: a forward without its blend, with upstream's lists, launched directly and
+    // untimed; the context's options are the caller's again afterwards
+    gsr_outputs out{};
+    out.color = ctx->grad2d.get();  // (required by the argument check; never written: no_blend)
+    out.radii = ctx->bwd_radii.get();
+    const int tight = ctx->tight, graphs = ctx->graphs, timing = ctx->timing;
+    ctx->bwd_timed = false;
+    if (timing)
+        for (auto &e : ctx->ev_bwd)
+            if (!e) GSR_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence), "hipEventCreate");
+    auto mark = [&](int i) -> int {
+        if (timing) GSR_HIP(hipEventRecord(ctx->ev_bwd[i], s), "hipEventRecord");
+        return GSR_OK;
+    };
+    GSR_TRY(mark(0));
+    ctx->tight = ctx->graphs = ctx->timing = 0;
+    const int rc = forward(ctx, g, st, &out, s, GSR_SHADE_SPLAT, nullptr, true);
+    ctx->tight = tight, ctx->graphs = graphs, ctx->timing = timing;
+    GSR_TRY(rc);
+
+    const bool dbg = st->debug != 0;
+    auto stage_check = [&](const char *what) -> int {
+        if (!dbg) return GSR_OK;
+        GSR_HIP(hipStreamSynchronize(s), what);
+        GSR_HIP(hipGetLastError(), what);
+        return GSR_OK;
+    };
+    GSR_TRY(mark(1));
+    GSR_HIP(hipMemsetAsync(ctx->grad2d.get(), 0, (size_t)P * kGradRow * sizeof(float), s),
+            "hipMemsetAsync(grad2d)");
+    const gsr_context::LastFrame &l = ctx->last;
+    GsrBlendBwdArgs ba{};
+    ba.ranges = ctx->ranges_local.get();
+    ba.point_list = l.point_list;
+    ba.records = ctx->records.get();
+    ba.W = st->image_width;
+    ba.H = st->image_height;
+    ba.grid_x = l.gx;
+    ba.n_tiles = l.gx * l.gy;
+    ba.bg = st->bg;
+    ba.dL_dcolor = in->dL_dcolor;
+    ba.id_mask = l.id_mask;
+    ba.cull = ctx->cull;
+    ba.grad2d = ctx->grad2d.get();
+    if (l.list > 0) GSR_HIP(gsr_launch_blend_bwd(ba, s), "blend backward launch");
+    GSR_TRY(mark(2));
+    GSR_TRY(stage_check("stage blend backward"));
+
+    GsrPreprocessBwdArgs pb{};
+    pb.P = P;
+    pb.D = g->D;
+    pb.M = g->M;
+    pb.scale_modifier = g->scale_modifier;
+    pb.means3D = g->means3D;
+    pb.scales = g->scales;
+    pb.rotations = g->rotations;
+    pb.shs = g->shs;
+    pb.colors_precomp = g->colors_precomp;
+    pb.cov3D_precomp = g->cov3D_precomp;
+    pb.viewmatrix = st->viewmatrix;
+    pb.projmatrix = st->projmatrix;
+    pb.campos = st->campos;
+    pb.tanfovx = st->tanfovx;
+    pb.tanfovy = st->tanfovy;
+    pb.focal_y = (float)st->image_height / (2.0f * st->tanfovy);
+    pb.focal_x = (float)st->image_width / (2.0f * st->tanfovx);
+    pb.W = st->image_width;
+    pb.H = st->image_height;
+    pb.radii = ctx->bwd_radii.get();
+    pb.grad2d = ctx->grad2d.get();
+    pb.dL_dmeans3D = gr->dL_dmeans3D;
+    pb.dL_dmeans2D = gr->dL_dmeans2D;
+    pb.dL_dopacity = gr->dL_dopacity;
+    pb.dL_dcolors = gr->dL_dcolors;
+    pb.dL_dconic = gr->dL_dconic;
+    pb.dL_dsh = gr->dL_dsh;
+    pb.dL_dscales = gr->dL_dscales;
+    pb.dL_drotations = gr->dL_drotations;
+    pb.dL_dcov3D = gr->dL_dcov3D;
+    GSR_HIP(gsr_launch_preprocess_bwd(pb, s), "per-Gaussian backward launch");
+    GSR_TRY(mark(3));
+    ctx->bwd_timed = timing != 0;
+    return stage_check("stage per-Gaussian backward");
+}
+
+int gsr_backward_times(gsr_context *ctx, float *ms, int n) {
+    if (!ctx || (!ms && n > 0)) return fail(GSR_E_INVALID, "gsr_backward_times: bad arguments");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->bwd_timed) return fail(GSR_E_STATE, "gsr_backward_times: no timed backward yet");
+    GSR_HIP(hipEventSynchronize(ctx->ev_bwd[3]), "hipEventSynchronize");
+    for (int i = 0; i < 3 && i < n; ++i)
+        GSR_HIP(hipEventElapsedTime(&ms[i], ctx->ev_bwd[i], ctx->ev_bwd[i + 1]),
+                "hipEventElapsedTime");
+    return 3;
 }
 
 int gsr_get_binning(gsr_context *ctx, uint32_t *point_list, uint32_t *point_tiles,

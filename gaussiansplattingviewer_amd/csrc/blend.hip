@@ -30,51 +30,6 @@ using namespace gsr;
 
 namespace {
 
-// ocml __ocml_exp_f32 (non-DAZ path) without the final range selects: identical results for
-// every finite argument (below about -104 both give 0, above 88.7 both give +inf).
-__device__ __forceinline__ float exp_core(float x) {
-    const float kLog2eHi = 0x1.715476p+0f;   // 1.44269502
-    const float kLog2eLo = 0x1.4ae0bep-26f;  // 1.92596299e-08
-    const float ph = x * kLog2eHi;
-    const float n = __builtin_rintf(ph);
-    const float hi = ph - n;
-    float lo = __builtin_fmaf(x, kLog2eHi, -ph);
-    lo = __builtin_fmaf(x, kLog2eLo, lo);
-    const float e = __builtin_amdgcn_exp2f(hi + lo);
-    return __builtin_ldexpf(e, (int)n);
-}
-
-// Lower bound of q(u, v) = A u^2 + 2B uv + C v^2 evaluated in float: q minus a bound on its
-// rounding error.
-__device__ __forceinline__ float q_lower(float A, float B, float C, float u, float v) {
-    const float uu = A * u * u, uv = 2.0f * B * u * v, vv = C * v * v;
-    return (uu + uv + vv) - 16.0f * 5.96e-8f * (uu + fabsf(uv) + vv);
-}
-
-// May the splat reach alpha >= 1/255 at some pixel centre of the box [bx0,bx1] x [by0,by1]?
-// False only when provably not (NaN / inf data always answer true).
-__device__ __forceinline__ bool may_touch(float x, float y, float A, float B, float C, float ex,
-                                          float ey, float twoL, float bx0, float bx1, float by0,
-                                          float by1) {
-    const float ulo = bx0 - x, uhi = bx1 - x, vlo = by0 - y, vhi = by1 - y;
-    if (fmaxf(fmaxf(ulo, -uhi), 0.0f) > ex || fmaxf(fmaxf(vlo, -vhi), 0.0f) > ey) return false;
-    if (ulo <= 0.0f && uhi >= 0.0f && vlo <= 0.0f && vhi >= 0.0f) return true;
-    // centre outside the box: q is convex, so its minimum over the box lies on an edge whose
-    // constraint the centre violates (at the minimiser, the direction to the centre leaves the
-    // box through an active face), where it is the 1-D minimum clamped to the edge: at most one
-    // vertical and one horizontal edge.  The minimiser's slope -B/C (-B/A) comes from
-    // v_rcp_f32 (1 ulp) instead of an IEEE division (~10 VALU): a minimiser a few ulp off
-    // raises q there by C * dv^2 ~ 1e-13 * q, far inside q_lower's 16-ulp rounding margin.
-    const float su = -B * __builtin_amdgcn_rcpf(C), sv = -B * __builtin_amdgcn_rcpf(A);
-    const float ue = ulo > 0.0f ? ulo : uhi, ve = vlo > 0.0f ? vlo : vhi;
-    const float lu = q_lower(A, B, C, ue, fminf(fmaxf(su * ue, vlo), vhi));
-    const float lv = q_lower(A, B, C, fminf(fmaxf(sv * ve, ulo), uhi), ve);
-    const float inf = __builtin_huge_valf();
-    const float lb = fminf((ulo > 0.0f || uhi < 0.0f) ? lu : inf,
-                           (vlo > 0.0f || vhi < 0.0f) ? lv : inf);
-    return !(lb > twoL);
-}
-
 // Block -> tile, XCD-aware: the hardware deals block b to XCD b % 8 (speed only, never
 // correctness); groups of kGroupTiles consecutive tiles (four row-adjacent tiles, 16 quadrant
 // waves) go round-robin over the XCDs, so each group shares one L2 while the image's heavy and

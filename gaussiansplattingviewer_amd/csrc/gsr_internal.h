@@ -209,6 +209,53 @@ __device__ __forceinline__ void gsr_msd_ctl(const KeyBits &k, uint32_t *ctl) {
     ctl[3] = k.min;
 }
 
+// --- the blend's exp and its quadrant cull (blend.hip, backward.hip: one arithmetic for the
+// composite and its derivative, so both take the same skip decisions) -----------------------
+// ocml __ocml_exp_f32 (non-DAZ path) without the final range selects: identical results for
+// every finite argument (below about -104 both give 0, above 88.7 both give +inf).
+__device__ __forceinline__ float exp_core(float x) {
+    const float kLog2eHi = 0x1.715476p+0f;   // 1.44269502
+    const float kLog2eLo = 0x1.4ae0bep-26f;  // 1.92596299e-08
+    const float ph = x * kLog2eHi;
+    const float n = __builtin_rintf(ph);
+    const float hi = ph - n;
+    float lo = __builtin_fmaf(x, kLog2eHi, -ph);
+    lo = __builtin_fmaf(x, kLog2eLo, lo);
+    const float e = __builtin_amdgcn_exp2f(hi + lo);
+    return __builtin_ldexpf(e, (int)n);
+}
+
+// Lower bound of q(u, v) = A u^2 + 2B uv + C v^2 evaluated in float: q minus a bound on its
+// rounding error.
+__device__ __forceinline__ float q_lower(float A, float B, float C, float u, float v) {
+    const float uu = A * u * u, uv = 2.0f * B * u * v, vv = C * v * v;
+    return (uu + uv + vv) - 16.0f * 5.96e-8f * (uu + fabsf(uv) + vv);
+}
+
+// May the splat reach alpha >= 1/255 at some pixel centre of the box [bx0,bx1] x [by0,by1]?
+// False only when provably not (NaN / inf data always answer true).
+__device__ __forceinline__ bool may_touch(float x, float y, float A, float B, float C, float ex,
+                                          float ey, float twoL, float bx0, float bx1, float by0,
+                                          float by1) {
+    const float ulo = bx0 - x, uhi = bx1 - x, vlo = by0 - y, vhi = by1 - y;
+    if (fmaxf(fmaxf(ulo, -uhi), 0.0f) > ex || fmaxf(fmaxf(vlo, -vhi), 0.0f) > ey) return false;
+    if (ulo <= 0.0f && uhi >= 0.0f && vlo <= 0.0f && vhi >= 0.0f) return true;
+    // centre outside the box: q is convex, so its minimum over the box lies on an edge whose
+    // constraint the centre violates (at the minimiser, the direction to the centre leaves the
+    // box through an active face), where it is the 1-D minimum clamped to the edge: at most one
+    // vertical and one horizontal edge.  The minimiser's slope -B/C (-B/A) comes from
+    // v_rcp_f32 (1 ulp) instead of an IEEE division (~10 VALU): a minimiser a few ulp off
+    // raises q there by C * dv^2 ~ 1e-13 * q, far inside q_lower's 16-ulp rounding margin.
+    const float su = -B * __builtin_amdgcn_rcpf(C), sv = -B * __builtin_amdgcn_rcpf(A);
+    const float ue = ulo > 0.0f ? ulo : uhi, ve = vlo > 0.0f ? vlo : vhi;
+    const float lu = q_lower(A, B, C, ue, fminf(fmaxf(su * ue, vlo), vhi));
+    const float lv = q_lower(A, B, C, fminf(fmaxf(sv * ve, ulo), uhi), ve);
+    const float inf = __builtin_huge_valf();
+    const float lb = fminf((ulo > 0.0f || uhi < 0.0f) ? lu : inf,
+                           (vlo > 0.0f || vhi < 0.0f) ? lv : inf);
+    return !(lb > twoL);
+}
+
 // --- wave / block scans (256-thread blocks, wave64) ------------------------------------
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
     const int lane = threadIdx.x & 63;
@@ -537,3 +584,38 @@ hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);
 uint32_t gsr_blend_order_groups(uint32_t n_tiles);
 hipError_t gsr_launch_blend_order(const uint2 *ranges, uint32_t n_tiles, uint32_t *order,
                                   hipStream_t s);
+
+// ---- the backward pass (backward.hip; gsr_backward in api.hip) ---------------------------------
+// The per-Gaussian 2D gradients the blend's backward sums and the per-Gaussian backward reads: one
+// 64-B row per Gaussian, {d/dmean2D x, y (pixels), d/dconic a, b, c, d/dopacity, d/drgb r, g, b,
+// 7 pad}, so one splat's nine sums are one contiguous segment of one 64-B atomic request.
+constexpr int kGradRow = 16;
+struct GsrBlendBwdArgs {
+    const uint2 *ranges;  // whole-frame tile ranges
+    const uint32_t *point_list;
+    const gsr::SplatRecord *records;
+    int W, H;
+    uint32_t grid_x, n_tiles;
+    const float *bg;
+    const float *dL_dcolor;  // [3, H, W]
+    uint32_t id_mask;
+    int cull;
+    float *grad2d;  // [P, kGradRow], zeroed by the caller
+};
+hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s);
+struct GsrPreprocessBwdArgs {
+    int64_t P;
+    int D, M;
+    float scale_modifier;
+    const float *means3D, *scales, *rotations, *shs, *colors_precomp, *cov3D_precomp;
+    const float *viewmatrix, *projmatrix, *campos;
+    float tanfovx, tanfovy, focal_x, focal_y;
+    int W, H;
+    int sh_vec4;  // set by the launcher: SH rows (and dL_dsh rows) of 16 coefficients, 16-B aligned
+    const int32_t *radii;  // of the rebuilt per-Gaussian stage: 0 = culled, every gradient 0
+    const float *grad2d;   // [P, kGradRow]
+    // outputs, each optional (gsr_gradients)
+    float *dL_dmeans3D, *dL_dmeans2D, *dL_dopacity, *dL_dcolors, *dL_dconic, *dL_dsh, *dL_dscales,
+        *dL_drotations, *dL_dcov3D;
+};
+hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t s);

@@ -10,10 +10,18 @@
 //       -> (num_rendered, color [3,H,W], radii [P], geomBuffer, binningBuffer, imgBuffer)
 //     upstream rasterize_points.cu RasterizeGaussiansCUDA, reached from GaussianRasterizer
 //     (renderer_cuda.py:211-224) through _RasterizeGaussians.  The three buffers hold upstream's
-//     backward state; the forward-only viewer (renderer_cuda.py:214, torch.no_grad) never reads
-//     them, and here they are empty.
+//     backward state; here they are empty: the backward rebuilds its state from the inputs.
 //   _C.rasterize_gaussians_shaded(<the same 19 arguments>, shading) -> the same 6-tuple
 //     this package's own: the forward under a GL shading (gsr_forward_shaded, GSR_SHADE_*).
+//   _C.rasterize_gaussians_backward(bg, means3D, radii, colors_precomp, scales, rotations,
+//                                   scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+//                                   tanfovx, tanfovy, dL_dout_color, sh, sh_degree, campos,
+//                                   geomBuffer, R, binningBuffer, imgBuffer, debug, opacities)
+//       -> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+//           dL_drotations)
+//     upstream RasterizeGaussiansBackwardCUDA's arguments and 8-tuple over gsr_backward, plus one
+//     trailing argument: upstream reads the opacities out of geomBuffer, here the state is
+//     rebuilt from the inputs.  radii, R and the three buffers are accepted and ignored.
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -145,6 +153,86 @@ Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tenso
                                       campos, prefiltered, debug, GSR_SHADE_SPLAT);
 }
 
+using Backward8 = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+                             torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+
+Backward8 rasterize_gaussians_backward(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+    const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy,
+    const torch::Tensor &dL_dout_color, const torch::Tensor &sh, int64_t degree,
+    const torch::Tensor &campos, const torch::Tensor &geomBuffer, int64_t R,
+    const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, bool debug,
+    const torch::Tensor &opacities) {
+    (void)radii, (void)geomBuffer, (void)R, (void)binningBuffer, (void)imageBuffer;
+    if (means3D.ndimension() != 2 || means3D.size(1) != 3)
+        AT_ERROR("means3D must have dimensions (num_points, 3)");
+    TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
+    TORCH_CHECK(dL_dout_color.dim() == 3 && dL_dout_color.size(0) == 3,
+                "dL_dout_color must have dimensions (3, H, W)");
+    const torch::Device dev = means3D.device();
+    const int64_t P = means3D.size(0);
+    const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
+    const int64_t M = !(sh.defined() && sh.numel() != 0) ? 0
+                      : sh.dim() == 3                    ? sh.size(1)
+                                                         : (P ? sh.numel() / P / 3 : 0);
+    auto f32 = means3D.options().dtype(torch::kFloat32);
+    torch::Tensor d_means3D = torch::zeros({P, 3}, f32), d_means2D = torch::zeros({P, 3}, f32);
+    torch::Tensor d_colors = torch::zeros({P, 3}, f32), d_opacity = torch::zeros({P, 1}, f32);
+    torch::Tensor d_cov3D = torch::zeros({P, 6}, f32), d_sh = torch::zeros({P, M, 3}, f32);
+    torch::Tensor d_scales = torch::zeros({P, 3}, f32), d_rot = torch::zeros({P, 4}, f32);
+    if (P != 0) {
+        std::vector<torch::Tensor> keep;
+        gsr_gaussians g{};
+        g.P = P;
+        g.D = (int32_t)degree;
+        g.M = (int32_t)M;
+        g.scale_modifier = (float)scale_modifier;
+        g.means3D = opt_ptr(means3D, dev, "means3D", keep, 3 * P);
+        g.scales = opt_ptr(scales, dev, "scales", keep, 3 * P);
+        g.rotations = opt_ptr(rotations, dev, "rotations", keep, 4 * P);
+        g.opacities = opt_ptr(opacities, dev, "opacities", keep, P);
+        g.shs = opt_ptr(sh, dev, "sh", keep, 3 * M * P);
+        g.colors_precomp = opt_ptr(colors, dev, "colors_precomp", keep, 3 * P);
+        g.cov3D_precomp = opt_ptr(cov3D_precomp, dev, "cov3D_precomp", keep, 6 * P);
+        gsr_raster_settings st{};
+        st.image_width = (int32_t)W;
+        st.image_height = (int32_t)H;
+        st.tanfovx = (float)tan_fovx;
+        st.tanfovy = (float)tan_fovy;
+        st.viewmatrix = opt_ptr(viewmatrix, dev, "viewmatrix", keep, 16);
+        st.projmatrix = opt_ptr(projmatrix, dev, "projmatrix", keep, 16);
+        st.campos = opt_ptr(campos, dev, "campos", keep, 3);
+        st.bg = opt_ptr(background, dev, "bg", keep, 3);
+        st.debug = debug ? 1 : 0;
+        gsr_backward_inputs in{};
+        in.dL_dcolor = opt_ptr(dL_dout_color, dev, "dL_dout_color", keep, 3 * H * W);
+        gsr_gradients gr{};
+        gr.dL_dmeans3D = d_means3D.data_ptr<float>();
+        gr.dL_dmeans2D = d_means2D.data_ptr<float>();
+        gr.dL_dopacity = d_opacity.data_ptr<float>();
+        gr.dL_dcolors = d_colors.data_ptr<float>();
+        gr.dL_dcov3D = d_cov3D.data_ptr<float>();
+        if (g.shs) gr.dL_dsh = d_sh.data_ptr<float>();
+        if (g.scales) {
+            gr.dL_dscales = d_scales.data_ptr<float>();
+            gr.dL_drotations = d_rot.data_ptr<float>();
+        }
+        c10::hip::HIPGuard guard(dev.index());
+        gsr_context *ctx = context_for(dev.index());
+        hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        int rc;
+        {  // the rebuild waits for K (pinned memory), as the forward does
+            pybind11::gil_scoped_release no_gil;
+            rc = gsr_backward(ctx, &g, &st, &in, &gr, s);
+        }
+        TORCH_CHECK(rc == GSR_OK, "gsr_backward failed (", rc, "): ", gsr_last_error());
+    }
+    return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales,
+                           d_rot);
+}
+
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
                            const torch::Tensor &projmatrix) {
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -184,6 +272,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians_shaded", &rasterize_gaussians_shaded,
           "rasterize_gaussians under a GL shading: its 19 arguments, then GSR_SHADE_* (0 splat, "
           "1 billboard, 2 flat ball, 3 gaussian ball)");
+    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward,
+          "upstream RasterizeGaussiansBackwardCUDA: its 21 arguments, then opacities -> "
+          "(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, "
+          "dL_drotations)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -10,7 +10,9 @@ GaussianRasterizer` and renderer_cuda.py:211-224 calls
 The names, field order, argument checks and return values below follow that third-party API
 (upstream `diff_gaussian_rasterization/__init__.py` and `_C.rasterize_gaussians` in
 rasterize_points.cu); the work is done by libgsr.so (HIP, gfx950) through `_lib`.
-Forward only: the viewer never differentiates (renderer_cuda.py:214 `torch.no_grad()`).
+The viewer renders under `torch.no_grad()` (renderer_cuda.py:214) and pays nothing for it, but the
+image is differentiable: `_RasterizeGaussians.backward` returns the gradients of the splat
+composite (`gsr_backward`, include/gsr.h), as upstream's does for training code.
 """
 from __future__ import annotations
 
@@ -195,6 +197,72 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     return ForwardResult(int(out.num_rendered), color, radii, ext)
 
 
+def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, scales, rotations,
+                                        scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                        tanfovx, tanfovy, dL_dout_color, sh, degree, campos,
+                                        debug=False, *, conic=False, stream=None, slot=0) -> dict:
+    """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
+    `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
+    Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
+    upstream's units, z = 0), dL_dopacity (P, 1), dL_dcolors, dL_dcov3D, dL_dsh (with SHs),
+    dL_dscales and dL_drotations (with scales and rotations); conic=True adds dL_dconic (P, 3)."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if dL_dout_color.ndimension() != 3 or dL_dout_color.size(0) != 3:
+        raise RuntimeError("dL_dout_color must have dimensions (3, H, W)")
+    device = _device_of(means3D)
+    dev_index = device.index if device.index is not None else torch.cuda.current_device()
+    P = int(means3D.size(0))
+    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    means3D = _as_dev(means3D, device, "P,3")
+    opacities = _as_dev(opacities, device, "P,1")
+    scales = _as_dev(scales, device, "P,3")
+    rotations = _as_dev(rotations, device, "P,4")
+    cov3D_precomp = _as_dev(cov3D_precomp, device, "P,6")
+    colors_precomp = _as_dev(colors_precomp, device, "P,3")
+    sh = _as_dev(sh, device, "P,M,3")
+    bg = _as_dev(bg, device, "3")
+    viewmatrix = _as_dev(viewmatrix, device, "4,4")
+    projmatrix = _as_dev(projmatrix, device, "4,4")
+    campos = _as_dev(campos, device, "3")
+    dL = _as_dev(dL_dout_color, device, "3,H,W")
+    M = 0
+    if sh is not None:
+        M = int(sh.size(1)) if sh.ndimension() == 3 else int(sh.numel() // max(P, 1) // 3)
+    f32 = dict(dtype=torch.float32, device=device)
+    grads = {"dL_dmeans3D": torch.zeros((P, 3), **f32), "dL_dmeans2D": torch.zeros((P, 3), **f32),
+             "dL_dopacity": torch.zeros((P, 1), **f32), "dL_dcolors": torch.zeros((P, 3), **f32),
+             "dL_dcov3D": torch.zeros((P, 6), **f32)}
+    if conic:
+        grads["dL_dconic"] = torch.zeros((P, 3), **f32)
+    if sh is not None:
+        grads["dL_dsh"] = torch.zeros((P, M, 3), **f32)
+    if scales is not None:
+        grads["dL_dscales"] = torch.zeros((P, 3), **f32)
+        grads["dL_drotations"] = torch.zeros((P, 4), **f32)
+    g = _lib.GsrGaussians(P=P, D=int(degree), M=M, scale_modifier=float(scale_modifier),
+                          means3D=_lib.ptr(means3D), scales=_lib.ptr(scales),
+                          rotations=_lib.ptr(rotations), opacities=_lib.ptr(opacities),
+                          shs=_lib.ptr(sh), colors_precomp=_lib.ptr(colors_precomp),
+                          cov3D_precomp=_lib.ptr(cov3D_precomp))
+    st = _lib.GsrRasterSettings(image_width=W, image_height=H, tanfovx=float(tanfovx),
+                                tanfovy=float(tanfovy), viewmatrix=_lib.ptr(viewmatrix),
+                                projmatrix=_lib.ptr(projmatrix), campos=_lib.ptr(campos),
+                                bg=_lib.ptr(bg), tile_row_begin=0, tile_row_end=0,
+                                prefiltered=0, debug=int(bool(debug)))
+    inp = _lib.GsrBackwardInputs(dL_dcolor=_lib.ptr(dL))
+    out = _lib.GsrGradients(**{n: _lib.ptr(t) for n, t in grads.items()})
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    lib = _lib.load_library()
+    ctx = _lib.context(dev_index, slot)
+    with torch.cuda.device(dev_index):
+        _lib.check(_lib.backward_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
+                                         ctypes.byref(out), ctypes.c_void_p(stream)),
+                   "gsr_backward")
+    return grads
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings: GaussianRasterizationSettings):
     """upstream rasterize_gaussians(...) -> (color, radii), through _RasterizeGaussians."""
@@ -225,14 +293,16 @@ def replay_snapshot(path: str = SNAPSHOT_FILE, device=None):
 
 class _RasterizeGaussians(torch.autograd.Function):
     """upstream `_RasterizeGaussians`: packs the settings into `_C.rasterize_gaussians`'s
-    argument tuple and keeps (color, radii) of its 6-tuple.  Forward only (the viewer renders
-    under `torch.no_grad()`, renderer_cuda.py:214)."""
+    argument tuple and keeps (color, radii) of its 6-tuple; `backward` hands the saved inputs and
+    the image's gradient to `_C.rasterize_gaussians_backward`.  Under `torch.no_grad()` (the
+    viewer, renderer_cuda.py:214) nothing is saved and the forward is the same call."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                 cov3Ds_precomp, raster_settings):
         from . import _C
-        del means2D  # only carries screen-space gradients upstream
+        # means2D only carries screen-space gradients, as upstream
+        ctx.has_means2D = isinstance(means2D, torch.Tensor)
         rs = raster_settings
         # absent inputs travel as empty tensors, as upstream's __init__.py passes them
         none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
@@ -260,13 +330,47 @@ class _RasterizeGaussians(torch.autograd.Function):
                       "(gaussiansplattingviewer_amd.rasterizer.replay_snapshot re-runs them).")
             raise
         ctx.num_rendered = num_rendered
+        ctx.raster_settings = rs
+        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
+                              none(rotations), none(cov3Ds_precomp), radii)
         ctx.mark_non_differentiable(radii)
         return color, radii
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii):
-        raise RuntimeError("gaussiansplattingviewer_amd renders forward only (the viewer never "
-                           "differentiates, renderer_cuda.py:214)")
+        """Gradients in input order (means3D, means2D, sh, colors_precomp, opacities, scales,
+        rotations, cov3Ds_precomp, None); None for absent inputs.  means2D's is upstream's
+        screen-space gradient, (P, 3) with z = 0 (densification reads it)."""
+        del grad_radii
+        rs = ctx.raster_settings
+        if rs.shading:
+            raise RuntimeError("gaussiansplattingviewer_amd differentiates the splat composite "
+                               f"only: no backward under shading {rs.shading}")
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, radii = ctx.saved_tensors
+        grad_color = grad_color.contiguous()
+        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
+            g = rasterize_gaussians_backward_native(
+                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
+                cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
+                rs.sh_degree, rs.campos, rs.debug)
+            z = lambda n: g.get(n)  # noqa: E731
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
+                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
+                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
+        else:
+            from . import _C
+            e = torch.empty(0)
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = \
+                _C.rasterize_gaussians_backward(
+                    rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier,
+                    cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
+                    rs.sh_degree, rs.campos, e, ctx.num_rendered, e, e, rs.debug, opacities)
+        has = lambda t: t.numel() != 0  # noqa: E731
+        return (d_means3D, d_means2D if ctx.has_means2D else None,
+                d_sh.reshape(sh.shape) if has(sh) else None,
+                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
+                d_scales if has(scales) else None, d_rot if has(rotations) else None,
+                d_cov3D if has(cov3Ds) else None, None)
 
 
 class GaussianRasterizer(torch.nn.Module):

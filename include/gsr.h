@@ -196,7 +196,60 @@ typedef struct {
 int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                       gsr_outputs *out, const gsr_depth_outputs *depth, void *stream);
 
-/* Binning state of the last gsr_forward on this context: the pair lists its blend read.  Writes
+/* The backward pass of gsr_forward (the splat composite): the gradients of a scalar loss L with
+ * respect to the Gaussians, from dL/dcolor.  (Additive to ABI 4.)
+ * The function differentiated is the forward exactly as stated above: upstream's preprocess and
+ * upstream's compositing in upstream's operation order (GSR_OPT_BLEND_FAST 0's arithmetic; the
+ * backward has this one arithmetic whatever the option says).  The derivative is derived from
+ * that forward, not copied from upstream's backward:
+ *   - gates select and are constants: z <= 0.2, det == 0, an empty rect and rect / tile
+ *     membership, the power > 0 and alpha < 1/255 skips, the T (1 - alpha) < 1e-4 termination
+ *     (the terminating splat contributes nothing);
+ *   - min, max and clamps pass nothing on their flat side: alpha = min(0.99, o G) gives 0 to o and
+ *     G where it caps, max(rgb + 0.5, 0) gives 0 to the SH of a clamped channel, and the 1.3 tan
+ *     clamp of t.x / t.z is differentiated as written, the clamped value times t.z (upstream's
+ *     hand-written backward lets the cap through and treats the clamped t.x as independent of
+ *     t.z);
+ *   - the background term final_T bg is part of the colour and is differentiated; bg gets none.
+ * dL_dmeans2D keeps upstream's shape and units: [P,3], x and y the pixel-space gradient times
+ * (0.5 W, 0.5 H) -- the gradient with respect to an offset added to the NDC centre before ndc2Pix
+ * -- and z = 0.  A Gaussian the forward culls (radius 0) gets exactly 0.0 in every gradient, and so
+ * do SH coefficients above the active degree D.  With cov3D_precomp the chain ends at dL_dcov3D
+ * (dL_dscales and dL_drotations, if asked for, are 0); with colors_precomp at dL_dcolors (dL_dsh 0).
+ * Whole frames only (a strip: GSR_E_INVALID); prefiltered, debug and scale_modifier as in the
+ * forward.  Gradients of the depth planes and of bg are not provided.
+ * Inputs only: the call is a function of its arguments.  It rebuilds the per-Gaussian stage, the
+ * depth sort and upstream's (untight) lists from them, launched directly (no frame graph is
+ * replayed; recorded graphs stay usable), and recomputes each pixel's transmittance inside its
+ * blend kernel, so it is correct whatever ran on the context since the matching forward.
+ * Afterwards gsr_get_binning exports the backward's lists (upstream's, K = num_rendered), as after
+ * a forward.  Every member of gsr_gradients is optional (NULL = not wanted); the call zeroes, then
+ * fills, each one given (it does not accumulate).  The sums over pixels are float atomics: the
+ * last bits of a gradient may differ from run to run. */
+typedef struct {
+    const float *dL_dcolor; /* [3,H,W] */
+} gsr_backward_inputs;
+typedef struct {
+    float *dL_dmeans3D;   /* [P,3] */
+    float *dL_dmeans2D;   /* [P,3], units above */
+    float *dL_dopacity;   /* [P,1] */
+    float *dL_dcolors;    /* [P,3] w.r.t. the per-Gaussian rgb after the clamp */
+    float *dL_dconic;     /* [P,3] a,b,c of the conic (b once, as stored) */
+    float *dL_dsh;        /* [P,M,3] */
+    float *dL_dscales;    /* [P,3] */
+    float *dL_drotations; /* [P,4] */
+    float *dL_dcov3D;     /* [P,6] */
+} gsr_gradients;
+int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                 const gsr_backward_inputs *in, gsr_gradients *grads, void *stream);
+/* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
+ * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
+ * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for
+ * that backward; writes min(n, 3); returns 3.  The rebuild records no forward stage times. */
+int gsr_backward_times(gsr_context *ctx, float *ms, int n);
+
+/* Binning state of the last gsr_forward (or gsr_backward) on this context: the pair lists its
+ * blend read.  Writes
  * the sizes (list_entries = K, the entries of the lists; num_tiles = T, tiles of the whole
  * frame) and, for each non-NULL caller-owned
  * DEVICE buffer, copies: point_list[K] Gaussian ids sorted by (tile, depth); point_tiles[K]

@@ -1,0 +1,121 @@
+"""The backward pass (gsr_backward) of a benchmark config beside its forward, serial, one context.
+
+Times with HIP events: the forward of the frame (torch events around gsr_forward), and the three
+stages of gsr_backward as the library records them under gsr_set_timing (gsr_backward_times): the
+rebuild of the per-Gaussian stage, the depth sort and upstream's lists; the blend's backward
+(k_blend_bwd_q, with the zeroing of its sums); the per-Gaussian backward (k_preprocess_bwd).
+Reports (one JSON line) their means and spreads, and the blend backward's atomic traffic against
+the chip-wide float atomic rate: 36 B per (splat, quadrant wave) contribution, the contributions
+per frame taken from --contributions (they are not counted on the device; the default is C3's,
+from the forward's ~118 composited splats per quadrant wave, blend.hip), so the byte figure is an
+upper estimate: a staged splat no pixel of the quadrant composites adds nothing.
+
+Each GPU step runs in a child process under its own time limit (--limit seconds).
+
+Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+ATOMIC_RATE_GBS = 1300.0  # chip-wide float atomic adds, bytes added per second (MI355X)
+BYTES_PER_CONTRIBUTION = 36  # nine float sums per (splat, quadrant wave)
+
+
+def worker(a):
+    import torch
+
+    from bench import Scene
+    from gaussiansplattingviewer_amd import _lib
+    from gaussiansplattingviewer_amd.rasterizer import (rasterize_gaussians_backward_native,
+                                                        rasterize_gaussians_native)
+    dev = torch.device("cuda", 0)
+    scene = Scene(a.config, dev)
+    lib = _lib.load_library()
+    ctx = _lib.context(0)
+    view, proj, campos, tx, ty, _ = scene.cams[0]
+    color = torch.empty((3, scene.H, scene.W), device=dev)
+    dL = torch.randn((3, scene.H, scene.W), device=dev)
+
+    def forward():
+        return rasterize_gaussians_native(scene.bg, scene.xyz, None, scene.opacity, scene.scale,
+                                          scene.rot, 1.0, None, view, proj, tx, ty, scene.H,
+                                          scene.W, scene.sh, scene.deg, campos, False, False,
+                                          out_color=color)
+
+    def backward():
+        return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
+                                                   scene.scale, scene.rot, 1.0, None, view, proj,
+                                                   tx, ty, dL, scene.sh, scene.deg, campos)
+
+    out = {"config": a.config, "steps": a.steps}
+    if a.step == "forward":
+        for _ in range(a.warmup):
+            forward()
+        ms = []
+        for _ in range(a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            res = forward()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        out.update(forward_ms=round(statistics.fmean(ms), 5),
+                   forward_ms_min_max=[round(min(ms), 5), round(max(ms), 5)],
+                   num_rendered=res.num_rendered)
+    else:
+        for _ in range(a.warmup):
+            backward()
+        _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
+        buf = (ctypes.c_float * 3)()
+        rows = []
+        for _ in range(a.steps):
+            backward()
+            _lib.check(lib.gsr_backward_times(ctx, buf, 3), "gsr_backward_times")
+            rows.append([float(buf[i]) for i in range(3)])
+        _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
+        for i, name in enumerate(("rebuild_ms", "blend_bwd_ms", "preprocess_bwd_ms")):
+            v = [r[i] for r in rows]
+            out[name] = round(statistics.fmean(v), 5)
+            out[name + "_min_max"] = [round(min(v), 5), round(max(v), 5)]
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="c3")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--limit", type=int, default=240, help="seconds per GPU step")
+    ap.add_argument("--contributions", type=float, default=3.9e6,
+                    help="(splat, quadrant) contributions per frame (C3: ~118 composited splats "
+                         "per quadrant wave, blend.hip)")
+    ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.step:
+        return worker(a)
+    out = {}
+    for step in ("forward", "backward"):  # a fresh process each, under its own time limit
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", a.config,
+                            "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step],
+                           capture_output=True, text=True, timeout=a.limit)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            sys.exit(f"bench_backward: the {step} step failed ({r.returncode}); nothing more is run")
+        out.update(json.loads(r.stdout.strip().splitlines()[-1]))
+    atomic_bytes = a.contributions * BYTES_PER_CONTRIBUTION
+    out["atomic_MB_per_frame_upper"] = round(atomic_bytes / 1e6, 1)
+    out["atomic_GBs_if_all_added"] = round(atomic_bytes / (out["blend_bwd_ms"] * 1e-3) / 1e9, 1)
+    out["atomic_rate_share"] = round(out["atomic_GBs_if_all_added"] / ATOMIC_RATE_GBS, 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
