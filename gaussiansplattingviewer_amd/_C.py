@@ -38,6 +38,14 @@ argument, `opacities`: upstream reads them out of geomBuffer, here nothing of th
 and `gsr_backward` (include/gsr.h, which states the semantics) rebuilds the state from the
 inputs.  `radii`, `num_rendered` and the three buffers are accepted and ignored.
 
+`_C.rasterize_gaussians_planes(<the 19 arguments>)` -> (num_rendered, color, radii, depth_map,
+inv_depth_map, final_T) and `_C.rasterize_gaussians_backward_planes(bg, means3D, colors_precomp,
+opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx,
+tanfovy, sh, sh_degree, campos, debug, dL_dout_color, dL_ddepth_map, dL_dinv_depth_map,
+dL_dfinal_T)` -> the same 8-tuple are this package's own: the forward with its per-pixel planes
+(`gsr_forward_depth`) and the backward that takes their gradients (`gsr_backward_planes`; an empty
+tensor is an unused gradient), behind `GaussianRasterizationSettings(depth_maps=True)`.
+
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
 """
@@ -45,7 +53,8 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
-                          rasterize_gaussians_backward, rasterize_gaussians_shaded)
+                          rasterize_gaussians_backward, rasterize_gaussians_backward_planes,
+                          rasterize_gaussians_planes, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
+    "gsr_backward_planes",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -95,6 +96,12 @@ class GsrGradients(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in GRADIENT_NAMES]
 
 
+class GsrPlaneGradients(ctypes.Structure):
+    """gsr_plane_gradients: gsr_backward_planes' plane gradients (None = unused) and dL_ddepths."""
+    _fields_ = [("dL_ddepth_map", ctypes.c_void_p), ("dL_dinv_depth_map", ctypes.c_void_p),
+                ("dL_dfinal_T", ctypes.c_void_p), ("dL_ddepths", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -137,6 +144,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_backward.restype = i32
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
+    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_planes_fn() says so)
+    if hasattr(lib, "gsr_backward_planes"):
+        lib.gsr_backward_planes.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                            ctypes.POINTER(GsrRasterSettings),
+                                            ctypes.POINTER(GsrBackwardInputs),
+                                            ctypes.POINTER(GsrPlaneGradients),
+                                            ctypes.POINTER(GsrGradients), vp]
+        lib.gsr_backward_planes.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -200,6 +215,17 @@ def backward_fn(lib: ctypes.CDLL):
         raise RuntimeError(
             f"{LIB_PATH} has no gsr_backward: gradients need a libgsr.so built from this tree "
             "(include/gsr.h declares it; ABI 4, additive)")
+    return fn
+
+
+def backward_planes_fn(lib: ctypes.CDLL):
+    """gsr_backward_planes of a loaded library; RuntimeError if that build does not have it."""
+    fn = getattr(lib, "gsr_backward_planes", None)
+    if fn is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_backward_planes: gradients of depth_map / inv_depth_map / "
+            "final_T need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
+            "additive)")
     return fn
 
 

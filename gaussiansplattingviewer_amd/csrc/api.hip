@@ -1427,17 +1427,25 @@ int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
 // per-Gaussian stage, the depth sort and upstream's (untight) lists, the direct way: no recorded
 // graph is replayed, none is invalidated beyond what a forward of the same shape would -- so
 // nothing of an earlier forward on this context is read; then backward.hip's two kernels.
-int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                 const gsr_backward_inputs *in, gsr_gradients *gr, void *stream) {
-    if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, "gsr_backward: NULL argument");
+// pl: gsr_backward_planes' struct, or NULL (gsr_backward).  With one of its three plane gradients
+// the two kernels are backward.hip's planes instantiations; without, they are gsr_backward's.
+static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                    const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
+                    gsr_gradients *gr, void *stream, const std::string &fn) {
+    if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
     if (st->tile_row_begin != 0 || st->tile_row_end != 0)
-        return fail(GSR_E_INVALID, "gsr_backward: whole frames only (a tile row strip is set)");
+        return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
     const int64_t P = g->P;
-    if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, "gsr_backward: bad P");
+    if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, fn + ": bad P");
     if (st->image_width <= 0 || st->image_height <= 0)
-        return fail(GSR_E_INVALID, "gsr_backward: image size must be positive");
+        return fail(GSR_E_INVALID, fn + ": image size must be positive");
+    const bool planes =
+        pl && (pl->dL_ddepth_map || pl->dL_dinv_depth_map || pl->dL_dfinal_T);
+    float *const dL_ddepths = pl ? pl->dL_ddepths : nullptr;
     if (P > 0) {
-        if (!in->dL_dcolor) return fail(GSR_E_INVALID, "gsr_backward: dL_dcolor is required");
+        if (!in->dL_dcolor && !planes)
+            return fail(GSR_E_INVALID, fn + (pl ? ": dL_dcolor or a plane gradient is required"
+                                                : ": dL_dcolor is required"));
         if ((g->shs == nullptr) == (g->colors_precomp == nullptr))
             return fail(GSR_E_INVALID,
                         "Please provide excatly one of either SHs or precomputed colors!");
@@ -1497,7 +1505,17 @@ int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_sett
     ba.id_mask = l.id_mask;
     ba.cull = ctx->cull;
     ba.grad2d = ctx->grad2d.get();
-    if (l.list > 0) GSR_HIP(gsr_launch_blend_bwd(ba, s), "blend backward launch");
+    if (l.list > 0) {
+        if (planes) {
+            // z by Gaussian id from the rebuild's depth keys, as launch_blend hands them to the
+            // forward's planes: written by the rebuild's preprocess on s and only read since
+            const GsrPlaneBwdArgs pa{ctx->sort_keys.get(), pl->dL_ddepth_map,
+                                     pl->dL_dinv_depth_map, pl->dL_dfinal_T};
+            GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s), "blend backward launch");
+        } else {
+            GSR_HIP(gsr_launch_blend_bwd(ba, s), "blend backward launch");
+        }
+    }
     GSR_TRY(mark(2));
     GSR_TRY(stage_check("stage blend backward"));
 
@@ -1532,10 +1550,29 @@ int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_sett
     pb.dL_dscales = gr->dL_dscales;
     pb.dL_drotations = gr->dL_drotations;
     pb.dL_dcov3D = gr->dL_dcov3D;
-    GSR_HIP(gsr_launch_preprocess_bwd(pb, s), "per-Gaussian backward launch");
+    if (planes) {
+        GSR_HIP(gsr_launch_preprocess_bwd_planes(pb, dL_ddepths, s),
+                "per-Gaussian backward launch");
+    } else {
+        GSR_HIP(gsr_launch_preprocess_bwd(pb, s), "per-Gaussian backward launch");
+        if (dL_ddepths)  // no plane gradient: nothing reaches the features
+            GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
+                    "hipMemsetAsync(dL_ddepths)");
+    }
     GSR_TRY(mark(3));
     ctx->bwd_timed = timing != 0;
     return stage_check("stage per-Gaussian backward");
+}
+
+int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                 const gsr_backward_inputs *in, gsr_gradients *gr, void *stream) {
+    return backward(ctx, g, st, in, nullptr, gr, stream, "gsr_backward");
+}
+
+int gsr_backward_planes(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                        gsr_gradients *gr, void *stream) {
+    return backward(ctx, g, st, in, planes, gr, stream, "gsr_backward_planes");
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

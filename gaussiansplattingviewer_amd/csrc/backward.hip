@@ -17,7 +17,15 @@
 //    a row (~7 rows of 36 B per instruction) -- never one atomic per lane and splat.
 //  * k_preprocess_bwd -- one thread per Gaussian: the 2D gradients through the conic, the EWA
 //    covariance, the projection, the SH colour and the 3D covariance to the inputs.
+//  * k_blend_bwd_planes_q, k_preprocess_bwd_planes -- the same two bodies with kPlanes set
+//    (gsr_backward_planes): depth_map, inv_depth_map and final_T are colour channels
+//    of the same composite with the features z, 1 / z, 0 and the backgrounds 0, 0, 1, so their
+//    gradients enter the recursion's start value and per-splat term, and a tenth sum per splat
+//    (dL/dz through the two features) goes to word 9 of the Gaussian's row and from there to
+//    dL_dmeans3D along the view matrix's z row.  Without the flag the bodies compile as before.
 #include "gsr_internal.h"
+
+#include <type_traits>
 
 using namespace gsr;
 
@@ -43,14 +51,26 @@ __device__ __forceinline__ float row_sum(float v) {
 
 // One staged splat: g = x, y, conic a, conic b; q = conic c, opacity, r, g; e = b, list position
 // + 1 (uint bits: upstream's `contributor`).
-struct BwdSplat {
+template <bool kPlanes>
+struct BwdSplatT {
     float4 g, q;
     float2 e;
 };
+// kPlanes: zf = z, 1 / z (the forward's features, blend.hip k_blend_depth_q), in the 8 B the
+// record's 16-B alignment pads anyway
+template <>
+struct BwdSplatT<true> {
+    float4 g, q;
+    float2 e, zf;
+};
 
-constexpr int kSums = 9;  // per (splat, quadrant): the words 0..8 of a gradient row
-
-__global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
+// The body of both blend backward kernels.  kPlanes: p holds the planes' gradients and the depth
+// keys; a.dL_dcolor may be NULL.  Without it p is not read.
+template <bool kPlanes>
+__device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p) {
+    using BwdSplat = BwdSplatT<kPlanes>;
+    // per (splat, quadrant): the words 0..8 of a gradient row, and word 9 (dL/dz) with the planes
+    constexpr int kSums = kPlanes ? 10 : 9;
     __shared__ BwdSplat s_spl_q[4][64];
     __shared__ uint32_t s_id_q[4][64];
     __shared__ float s_red_q[4][64 * kSums];
@@ -73,8 +93,9 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
     if (__ballot(inside) == 0ull || range.x >= range.y) return;
 
     // Stages chunk `start` (the forward's gather, cull and in-order compaction); returns the
-    // number of staged splats.
-    auto stage = [&](uint32_t start) {
+    // number of staged splats.  with_z (kPlanes, the back-to-front pass): also z by Gaussian id
+    // from the depth keys and 1 / z, once per staged splat.
+    auto stage = [&](uint32_t start, auto with_z) {
         const uint32_t idx = start + (uint32_t)lane;
         const bool valid = idx < range.y;
         SplatRecord r;
@@ -95,6 +116,12 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
             s_spl[slot].q = make_float4(r.b.x, r.b.y, r.c.y, r.c.z);
             s_spl[slot].e = make_float2(r.c.w, __uint_as_float(idx - range.x + 1u));
             s_id[slot] = id;
+            if constexpr (kPlanes) {
+                if constexpr (decltype(with_z)::value) {
+                    const float z = __uint_as_float(p.z_bits[id]);
+                    s_spl[slot].zf = make_float2(z, 1.0f / z);
+                }
+            }
         }
         return __popcll(bal);
     };
@@ -105,7 +132,7 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
     uint32_t chunks = 0u;             // chunks the forward walked
     for (uint32_t start = range.x; start < range.y; start += 64) {
         ++chunks;
-        const int count = stage(start);
+        const int count = stage(start, std::false_type{});
         for (int k = 0; k < count; ++k) {
             const BwdSplat sp = s_spl[k];
             const float dx = sp.g.x - pfx, dy = sp.g.y - pfy;
@@ -126,19 +153,31 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
     // (1 - alpha_i) R_i) the pixel is R_0 and dC/dalpha_i = T_i (c_i - R_i); only r = g . R is
     // carried (g = dL/dC of the pixel).  T_i is rebuilt as T_{i+1} / (1 - alpha_i), alpha <= 0.99.
     const size_t plane = (size_t)a.H * a.W, pid = (size_t)(inside ? py : 0) * a.W + (inside ? px : 0);
-    const float g0 = inside ? a.dL_dcolor[pid] : 0.0f;
-    const float g1 = inside ? a.dL_dcolor[plane + pid] : 0.0f;
-    const float g2 = inside ? a.dL_dcolor[2 * plane + pid] : 0.0f;
+    // (kPlanes: a NULL dL_dcolor, a NULL plane and a pixel outside the image all read 0)
+    const bool has_g = inside && (!kPlanes || a.dL_dcolor);
+    const float g0 = has_g ? a.dL_dcolor[pid] : 0.0f;
+    const float g1 = has_g ? a.dL_dcolor[plane + pid] : 0.0f;
+    const float g2 = has_g ? a.dL_dcolor[2 * plane + pid] : 0.0f;
+    // dL/ddepth_map, dL/dinv_depth_map, dL/dfinal_T
+    [[maybe_unused]] float gd = 0.0f, gi = 0.0f, gT = 0.0f;
+    if constexpr (kPlanes) {
+        gd = inside && p.dL_ddepth_map ? p.dL_ddepth_map[pid] : 0.0f;
+        gi = inside && p.dL_dinv_depth_map ? p.dL_dinv_depth_map[pid] : 0.0f;
+        gT = inside && p.dL_dfinal_T ? p.dL_dfinal_T[pid] : 0.0f;
+    }
     float Tc = fabsf(T);
+    // the planes' backgrounds are 0, 0, 1: final_T is the channel with feature 0
     float rr = g0 * a.bg[0] + g1 * a.bg[1] + g2 * a.bg[2];
+    if constexpr (kPlanes) rr += gT;
     for (uint32_t c = chunks; c-- > 0u;) {
-        const int count = stage(range.x + 64u * c);
+        const int count = stage(range.x + 64u * c, std::bool_constant<kPlanes>{});
         // groups of 16 slots, back to front: lane 16 r + j keeps row r's share of the nine sums
         // of the splat in slot 16 kg + j
         for (int kg = (count - 1) >> 4; kg >= 0; --kg) {
             const int k_lo = 16 * kg, k_hi = min(count, k_lo + 16);
             float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f,
                   s8 = 0.f;
+            [[maybe_unused]] float s9 = 0.f;
             uint32_t touched = 0u;  // slots of the group with a contributing pixel
             for (int k = k_hi; k-- > k_lo;) {
                 const BwdSplat sp = s_spl[k];
@@ -154,7 +193,8 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
                 touched |= 1u << (k & 15);
                 const float Ti = Tc / (1.0f - alpha);
                 const float w = alpha * Ti;
-                const float gc = g0 * sp.q.z + g1 * sp.q.w + g2 * sp.e.x;
+                float gc = g0 * sp.q.z + g1 * sp.q.w + g2 * sp.e.x;
+                if constexpr (kPlanes) gc += gd * sp.zf.x + gi * sp.zf.y;
                 const float dLa = Ti * (gc - rr);
                 // alpha = min(0.99, o G): nothing passes where it caps
                 const bool open = con && !(oG > 0.99f);
@@ -177,14 +217,22 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
                 s3 = mine ? t3 : s3, s4 = mine ? t4 : s4, s5 = mine ? t5 : s5;
                 const float t6 = row_sum(v6), t7 = row_sum(v7), t8 = row_sum(v8);
                 s6 = mine ? t6 : s6, s7 = mine ? t7 : s7, s8 = mine ? t8 : s8;
+                if constexpr (kPlanes) {
+                    // the direct path through the features: d(z w)/dz = w, d((1/z) w)/dz =
+                    // -(1/z)^2 w with the forward's rounded quotient
+                    const float v9 = con ? w * (gd - gi * (sp.zf.y * sp.zf.y)) : 0.0f;
+                    const float t9 = row_sum(v9);
+                    s9 = mine ? t9 : s9;
+                }
             }
             if (touched == 0u) continue;
             // slot-major in LDS, the four rows of a slot side by side; then word t of the group's
             // slots x 9 goes to word t % 9 of the row of slot t / 9: consecutive lanes add to
-            // consecutive words
+            // consecutive words (kPlanes: slots x 10 <= 160 words, still <= 3 instructions)
             float *mine9 = s_red + ((lane & 15) * 4 + (lane >> 4)) * kSums;
             mine9[0] = s0, mine9[1] = s1, mine9[2] = s2, mine9[3] = s3, mine9[4] = s4;
             mine9[5] = s5, mine9[6] = s6, mine9[7] = s7, mine9[8] = s8;
+            if constexpr (kPlanes) mine9[9] = s9;
             const int n = (k_hi - k_lo) * kSums;
             for (int t = lane; t < n; t += 64) {
                 const int slot = t / kSums, word = t - slot * kSums;
@@ -196,6 +244,14 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
+    blend_bwd<false>(a, GsrPlaneBwdArgs{});
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_q(const GsrBlendBwdArgs a,
+                                                            const GsrPlaneBwdArgs p) {
+    blend_bwd<true>(a, p);
 }
 
 // ---- per Gaussian ------------------------------------------------------------------------------
@@ -241,248 +297,34 @@ __device__ __forceinline__ void store3(float *p, int64_t i, float x, float y, fl
     if (p) p[3 * i] = x, p[3 * i + 1] = y, p[3 * i + 2] = z;
 }
 
+
+// Both kernels are the statements of backward_gaussian.inc; the second adds the planes' term.
 __global__ __launch_bounds__(256) void k_preprocess_bwd(const GsrPreprocessBwdArgs a) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= a.P) return;
-    float *const sh_out = a.dL_dsh ? a.dL_dsh + idx * (int64_t)a.M * 3 : nullptr;
-    if (a.radii[idx] <= 0) {  // culled by the forward: exact zeros
-        store3(a.dL_dmeans3D, idx, 0.f, 0.f, 0.f);
-        store3(a.dL_dmeans2D, idx, 0.f, 0.f, 0.f);
-        if (a.dL_dopacity) a.dL_dopacity[idx] = 0.f;
-        store3(a.dL_dcolors, idx, 0.f, 0.f, 0.f);
-        store3(a.dL_dconic, idx, 0.f, 0.f, 0.f);
-        store3(a.dL_dscales, idx, 0.f, 0.f, 0.f);
-        if (a.dL_drotations)
-            for (int i = 0; i < 4; ++i) a.dL_drotations[4 * idx + i] = 0.f;
-        if (a.dL_dcov3D)
-            for (int i = 0; i < 6; ++i) a.dL_dcov3D[6 * idx + i] = 0.f;
-        if (sh_out && a.sh_vec4) {
-            for (int i = 0; i < 12; ++i)
-                reinterpret_cast<float4 *>(sh_out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else if (sh_out) {
-            for (int i = 0; i < 3 * a.M; ++i) sh_out[i] = 0.f;
-        }
-        return;
-    }
-    const float *gr = a.grad2d + idx * kGradRow;
-    const float gmx = gr[0], gmy = gr[1], gca = gr[2], gcb = gr[3], gcc = gr[4], gop = gr[5];
-    const float grgb[3] = {gr[6], gr[7], gr[8]};
-    // upstream's units: the gradient with respect to an offset added to the NDC centre
-    const float gnx = gmx * (0.5f * (float)a.W), gny = gmy * (0.5f * (float)a.H);
-    store3(a.dL_dmeans2D, idx, gnx, gny, 0.f);
-    if (a.dL_dopacity) a.dL_dopacity[idx] = gop;
-    store3(a.dL_dcolors, idx, grgb[0], grgb[1], grgb[2]);
-    store3(a.dL_dconic, idx, gca, gcb, gcc);
-
-    const float *vm = a.viewmatrix, *pm = a.projmatrix;
-    const float3 p = make_float3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
-    float dpx = 0.f, dpy = 0.f, dpz = 0.f;  // dL/dmeans3D
-
-    // ---- the projective divide: ndc = hom.xy / (hom.w + 1e-7) --------------------------------
-    {
-        const float4 h = transform_point_4x4(p, pm);
-        const float pw = 1.0f / (h.w + 0.0000001f);
-        const float dhx = gnx * pw, dhy = gny * pw;
-        const float dhw = -(gnx * h.x + gny * h.y) * pw * pw;
-        dpx += pm[0] * dhx + pm[1] * dhy + pm[3] * dhw;
-        dpy += pm[4] * dhx + pm[5] * dhy + pm[7] * dhw;
-        dpz += pm[8] * dhx + pm[9] * dhy + pm[11] * dhw;
-    }
-
-    // ---- the colour: rgb = max(sum_b basis_b(dir) sh_b + 0.5, 0), dir = (p - campos) / len -----
-    if (a.shs) {
-        const float *sh = a.shs + idx * (int64_t)a.M * 3;
-        const int ncoef = (a.D + 1) * (a.D + 1);
-        float dx = p.x - a.campos[0], dy = p.y - a.campos[1], dz = p.z - a.campos[2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        dx = dx / len, dy = dy / len, dz = dz / len;
-        float b[16], bx[16], by[16], bz[16];
-        sh_basis(dx, dy, dz, b, bx, by, bz);
-        // the coefficients of the active degree (the others read as 0), kept in registers; rows
-        // of 16 coefficients at 16-B aligned pointers move as 12 float4 (a.sh_vec4), in and out
-        float c[48];
-        const int nflt = 3 * ncoef;
-        if (a.sh_vec4) {
-            const float4 *v = reinterpret_cast<const float4 *>(sh);
-            float4 rowv[12];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) rowv[i] = v[i];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                c[4 * i] = 4 * i < nflt ? rowv[i].x : 0.f;
-                c[4 * i + 1] = 4 * i + 1 < nflt ? rowv[i].y : 0.f;
-                c[4 * i + 2] = 4 * i + 2 < nflt ? rowv[i].z : 0.f;
-                c[4 * i + 3] = 4 * i + 3 < nflt ? rowv[i].w : 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 48; ++i) c[i] = i < nflt ? sh[i] : 0.f;
-        }
-        float val[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (k < ncoef)
-                for (int ch = 0; ch < 3; ++ch) val[ch] += b[k] * c[3 * k + ch];
-        float G[3];  // max(v + 0.5, 0) passes nothing on its flat side
-        for (int ch = 0; ch < 3; ++ch) G[ch] = (val[ch] + 0.5f < 0.0f) ? 0.0f : grgb[ch];
-        float ddx = 0.f, ddy = 0.f, ddz = 0.f;  // dL/ddir
-        float o[48];                            // dL/dsh: 0 above the active degree
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const bool on = k < ncoef;
-            if (on) {
-                const float m = G[0] * c[3 * k] + G[1] * c[3 * k + 1] + G[2] * c[3 * k + 2];
-                ddx += bx[k] * m, ddy += by[k] * m, ddz += bz[k] * m;
-            }
-            for (int ch = 0; ch < 3; ++ch) o[3 * k + ch] = on ? b[k] * G[ch] : 0.f;
-        }
-        if (sh_out) {
-            if (a.sh_vec4) {
-                float4 *w = reinterpret_cast<float4 *>(sh_out);
-#pragma unroll
-                for (int i = 0; i < 12; ++i)
-                    w[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 48; ++i)
-                    if (i < 3 * a.M) sh_out[i] = o[i];
-                for (int i = 48; i < 3 * a.M; ++i) sh_out[i] = 0.f;
-            }
-        }
-        // dir = d / |d|: (I - dir dir^T) / len
-        const float dot = dx * ddx + dy * ddy + dz * ddz;
-        dpx += (ddx - dx * dot) / len;
-        dpy += (ddy - dy * dot) / len;
-        dpz += (ddz - dz * dot) / len;
-    } else if (sh_out) {
-        for (int i = 0; i < 3 * a.M; ++i) sh_out[i] = 0.f;
-    }
-
-    // ---- the 3D covariance --------------------------------------------------------------------
-    float c6[6];
-    float3 sc = make_float3(0.f, 0.f, 0.f);
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.cov3D_precomp) {
-        for (int i = 0; i < 6; ++i) c6[i] = a.cov3D_precomp[6 * idx + i];
-    } else {
-        sc = make_float3(a.scales[3 * idx], a.scales[3 * idx + 1], a.scales[3 * idx + 2]);
-        q = make_float4(a.rotations[4 * idx], a.rotations[4 * idx + 1], a.rotations[4 * idx + 2],
-                        a.rotations[4 * idx + 3]);
-        compute_cov3d(sc, a.scale_modifier, q, c6);
-    }
-
-    // ---- the conic: (c, -b, a) / det of cov2 = A V A^T + 0.3 I, A = J R (2 x 3) ----------------
-    const float3 t = transform_point_4x3(p, vm);
-    const float limx = 1.3f * a.tanfovx, limy = 1.3f * a.tanfovy;
-    const float txtz = t.x / t.z, tytz = t.y / t.z;
-    const float cx = fminf(limx, fmaxf(-limx, txtz)), cy = fminf(limy, fmaxf(-limy, tytz));
-    const bool clx = cx != txtz, cly = cy != tytz;  // on the clamp's flat side
-    const float tx = cx * t.z, ty = cy * t.z, tz = t.z;
-    const float fx = a.focal_x, fy = a.focal_y;
-    const float tz2 = tz * tz;
-    const float J00 = fx / tz, J02 = -(fx * tx) / tz2, J11 = fy / tz, J12 = -(fy * ty) / tz2;
-    // R[r][c] = vm[4 c + r] (the view rotation); A = J R
-    float A0[3], A1[3];
-    for (int c = 0; c < 3; ++c) {
-        A0[c] = J00 * vm[4 * c] + J02 * vm[4 * c + 2];
-        A1[c] = J11 * vm[4 * c + 1] + J12 * vm[4 * c + 2];
-    }
-    const float V[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-    float VA0[3], VA1[3];  // V A^T
-    for (int i = 0; i < 3; ++i) {
-        VA0[i] = V[i][0] * A0[0] + V[i][1] * A0[1] + V[i][2] * A0[2];
-        VA1[i] = V[i][0] * A1[0] + V[i][1] * A1[1] + V[i][2] * A1[2];
-    }
-    const float ca = A0[0] * VA0[0] + A0[1] * VA0[1] + A0[2] * VA0[2] + 0.3f;
-    const float cb = A0[0] * VA1[0] + A0[1] * VA1[1] + A0[2] * VA1[2];
-    const float cc = A1[0] * VA1[0] + A1[1] * VA1[1] + A1[2] * VA1[2] + 0.3f;
-    const float det = ca * cc - cb * cb;
-    const float id2 = 1.0f / (det * det);
-    // conic = (cc, -cb, ca) / det, det - ca cc = -cb^2
-    const float dca = (-cc * cc * gca + cb * cc * gcb - cb * cb * gcc) * id2;
-    const float dcc = (-cb * cb * gca + ca * cb * gcb - ca * ca * gcc) * id2;
-    const float dcb = (2.0f * cb * cc * gca - (ca * cc + cb * cb) * gcb + 2.0f * ca * cb * gcc) * id2;
-    const float hb = 0.5f * dcb;  // each off-diagonal of the symmetric dL/dcov2
-    // dL/dV = A^T G2 A (an off-diagonal of V stands for two entries: twice in dL/dcov3D)
-    float GA0[3], GA1[3];  // G2 A
-    for (int c = 0; c < 3; ++c) {
-        GA0[c] = dca * A0[c] + hb * A1[c];
-        GA1[c] = hb * A0[c] + dcc * A1[c];
-    }
-    float dV[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) dV[i][j] = A0[i] * GA0[j] + A1[i] * GA1[j];
-    const float d6[6] = {dV[0][0], 2.0f * dV[0][1], 2.0f * dV[0][2], dV[1][1], 2.0f * dV[1][2],
-                         dV[2][2]};
-    if (a.dL_dcov3D)
-        for (int i = 0; i < 6; ++i) a.dL_dcov3D[6 * idx + i] = d6[i];
-    // dL/dA = 2 G2 A V, dL/dJ = dL/dA R^T
-    float dA0[3], dA1[3];
-    for (int c = 0; c < 3; ++c) {
-        dA0[c] = 2.0f * (dca * VA0[c] + hb * VA1[c]);
-        dA1[c] = 2.0f * (hb * VA0[c] + dcc * VA1[c]);
-    }
-    const float dJ00 = dA0[0] * vm[0] + dA0[1] * vm[4] + dA0[2] * vm[8];
-    const float dJ02 = dA0[0] * vm[2] + dA0[1] * vm[6] + dA0[2] * vm[10];
-    const float dJ11 = dA1[0] * vm[1] + dA1[1] * vm[5] + dA1[2] * vm[9];
-    const float dJ12 = dA1[0] * vm[2] + dA1[1] * vm[6] + dA1[2] * vm[10];
-    const float tz3 = tz2 * tz;
-    float dtz = -fx / tz2 * dJ00 - fy / tz2 * dJ11 + 2.0f * fx * tx / tz3 * dJ02 +
-                2.0f * fy * ty / tz3 * dJ12;
-    const float dtxc = -fx / tz2 * dJ02, dtyc = -fy / tz2 * dJ12;  // d/d(clamped t.x, t.y)
-    // t.x' = clamp(t.x / t.z) t.z, as written: (t.x / t.z) t.z inside (d/dt.x = 1, d/dt.z = 0),
-    // +-lim t.z on the flat side (d/dt.x = 0, d/dt.z = +-lim)
-    const float dtx = clx ? 0.0f : dtxc, dty = cly ? 0.0f : dtyc;
-    dtz += (clx ? cx * dtxc : 0.0f) + (cly ? cy * dtyc : 0.0f);
-    dpx += vm[0] * dtx + vm[1] * dty + vm[2] * dtz;
-    dpy += vm[4] * dtx + vm[5] * dty + vm[6] * dtz;
-    dpz += vm[8] * dtx + vm[9] * dty + vm[10] * dtz;
-    store3(a.dL_dmeans3D, idx, dpx, dpy, dpz);
-
-    // ---- Sigma = N N^T, N = Rq diag(mod s) (the rotation as given, not renormalised) ------------
-    if (a.cov3D_precomp) {
-        store3(a.dL_dscales, idx, 0.f, 0.f, 0.f);
-        if (a.dL_drotations)
-            for (int i = 0; i < 4; ++i) a.dL_drotations[4 * idx + i] = 0.f;
-        return;
-    }
-    const float r = q.x, x = q.y, y = q.z, z = q.w;
-    const float Rq[3][3] = {
-        {1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y)},
-        {2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x)},
-        {2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y)}};
-    const float sm[3] = {a.scale_modifier * sc.x, a.scale_modifier * sc.y, a.scale_modifier * sc.z};
-    float ds[3], D[3][3];  // dL/ds, dL/dRq
-    for (int j = 0; j < 3; ++j) {
-        ds[j] = 0.f;
-        for (int i = 0; i < 3; ++i) {
-            // dL/dN[i][j] = 2 (dV N)[i][j], N[k][j] = Rq[k][j] sm[j]
-            const float dN = 2.0f * sm[j] *
-                             (dV[i][0] * Rq[0][j] + dV[i][1] * Rq[1][j] + dV[i][2] * Rq[2][j]);
-            ds[j] += dN * Rq[i][j];
-            D[i][j] = dN * sm[j];
-        }
-        ds[j] *= a.scale_modifier;
-    }
-    store3(a.dL_dscales, idx, ds[0], ds[1], ds[2]);
-    if (a.dL_drotations) {
-        float *o = a.dL_drotations + 4 * idx;
-        o[0] = 2.f * (-z * D[0][1] + y * D[0][2] + z * D[1][0] - x * D[1][2] - y * D[2][0] +
-                      x * D[2][1]);
-        o[1] = 2.f * (y * D[0][1] + z * D[0][2] + y * D[1][0] - 2.f * x * D[1][1] - r * D[1][2] +
-                      z * D[2][0] + r * D[2][1] - 2.f * x * D[2][2]);
-        o[2] = 2.f * (-2.f * y * D[0][0] + x * D[0][1] + r * D[0][2] + x * D[1][0] + z * D[1][2] -
-                      r * D[2][0] + z * D[2][1] - 2.f * y * D[2][2]);
-        o[3] = 2.f * (-2.f * z * D[0][0] - r * D[0][1] + x * D[0][2] + r * D[1][0] -
-                      2.f * z * D[1][1] + y * D[1][2] + x * D[2][0] + y * D[2][1]);
-    }
+    constexpr bool kPlanes = false;
+    [[maybe_unused]] float *const dL_ddepths = nullptr;
+#include "backward_gaussian.inc"
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_planes(const GsrPreprocessBwdArgs a,
+                                                               float *dL_ddepths) {
+    constexpr bool kPlanes = true;
+#include "backward_gaussian.inc"
 }
 
 }  // namespace
 
 hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s) {
     if (a.n_tiles == 0) return hipSuccess;
+    if (!a.dL_dcolor) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_blend_bwd_q, dim3(a.n_tiles), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
+                                       hipStream_t s) {
+    if (!p.z_bits || (!p.dL_ddepth_map && !p.dL_dinv_depth_map && !p.dL_dfinal_T))
+        return hipErrorInvalidValue;
+    if (a.n_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
     return hipGetLastError();
 }
 
@@ -493,5 +335,16 @@ hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &args, hipStream
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
     hipLaunchKernelGGL(k_preprocess_bwd, dim3((unsigned)gsr_preprocess_blocks(a.P)), dim3(256), 0,
                        s, a);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &args, float *dL_ddepths,
+                                            hipStream_t s) {
+    if (args.P == 0) return hipSuccess;
+    GsrPreprocessBwdArgs a = args;
+    a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
+                (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
+    hipLaunchKernelGGL(k_preprocess_bwd_planes, dim3((unsigned)gsr_preprocess_blocks(a.P)),
+                       dim3(256), 0, s, a, dL_ddepths);
     return hipGetLastError();
 }

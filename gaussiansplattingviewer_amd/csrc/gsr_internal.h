@@ -588,7 +588,8 @@ hipError_t gsr_launch_blend_order(const uint2 *ranges, uint32_t n_tiles, uint32_
 // ---- the backward pass (backward.hip; gsr_backward in api.hip) ---------------------------------
 // The per-Gaussian 2D gradients the blend's backward sums and the per-Gaussian backward reads: one
 // 64-B row per Gaussian, {d/dmean2D x, y (pixels), d/dconic a, b, c, d/dopacity, d/drgb r, g, b,
-// 7 pad}, so one splat's nine sums are one contiguous segment of one 64-B atomic request.
+// 7 pad}, so one splat's nine sums are one contiguous segment of one 64-B atomic request.  With the
+// planes (gsr_backward_planes) word 9 is d/dz through the features z and 1 / z, 6 pad.
 constexpr int kGradRow = 16;
 struct GsrBlendBwdArgs {
     const uint2 *ranges;  // whole-frame tile ranges
@@ -603,6 +604,16 @@ struct GsrBlendBwdArgs {
     float *grad2d;  // [P, kGradRow], zeroed by the caller
 };
 hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s);
+// gsr_backward_planes (k_blend_bwd_planes_q): the gradients of depth_map, inv_depth_map and
+// final_T ([H, W] each, any NULL but not all) beside a.dL_dcolor, which may then be NULL.  z_bits:
+// per Gaussian, the bits of its view-space z (the rebuild's depth keys, as GsrDepthArgs).  The
+// tenth sum, dL/dz through the features z and 1 / z, goes to word 9 of the Gaussian's row.
+struct GsrPlaneBwdArgs {
+    const uint32_t *z_bits;
+    const float *dL_ddepth_map, *dL_dinv_depth_map, *dL_dfinal_T;
+};
+hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
+                                       hipStream_t s);
 struct GsrPreprocessBwdArgs {
     int64_t P;
     int D, M;
@@ -619,3 +630,7 @@ struct GsrPreprocessBwdArgs {
         *dL_drotations, *dL_dcov3D;
 };
 hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t s);
+// k_preprocess_bwd_planes: also reads word 9 of the rows, adds (vm[2], vm[6], vm[10]) times it to
+// dL_dmeans3D and writes it to dL_ddepths ([P], optional).
+hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &a, float *dL_ddepths,
+                                            hipStream_t s);

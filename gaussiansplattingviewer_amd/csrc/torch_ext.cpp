@@ -22,6 +22,15 @@
 //     upstream RasterizeGaussiansBackwardCUDA's arguments and 8-tuple over gsr_backward, plus one
 //     trailing argument: upstream reads the opacities out of geomBuffer, here the state is
 //     rebuilt from the inputs.  radii, R and the three buffers are accepted and ignored.
+//   _C.rasterize_gaussians_planes(<rasterize_gaussians' 19 arguments>)
+//       -> (num_rendered, color, radii, depth_map [H,W], inv_depth_map [H,W], final_T [H,W])
+//   _C.rasterize_gaussians_backward_planes(bg, means3D, colors_precomp, opacities, scales,
+//                                          rotations, scale_modifier, cov3D_precomp, viewmatrix,
+//                                          projmatrix, tanfovx, tanfovy, sh, sh_degree, campos,
+//                                          debug, dL_dout_color, dL_ddepth_map,
+//                                          dL_dinv_depth_map, dL_dfinal_T) -> the same 8-tuple
+//     this package's own (GaussianRasterizationSettings.depth_maps): gsr_forward_depth with
+//     final_T, and gsr_backward_planes; an empty gradient tensor is an unused one.
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -71,14 +80,20 @@ const float *opt_ptr(const torch::Tensor &t, const torch::Device &dev, const cha
 using Forward6 =
     std::tuple<int64_t, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
 
-// upstream's 19 arguments and the shading (GSR_SHADE_*, gsr_forward_shaded)
-Forward6 rasterize_gaussians_shaded(
+// The per-pixel planes of rasterize_gaussians_planes: depth_map, inv_depth_map, final_T, [H,W] each.
+struct Planes {
+    torch::Tensor depth_map, inv_depth_map, final_T;
+};
+
+// upstream's 19 arguments and the shading (GSR_SHADE_*, gsr_forward_shaded); planes: the splat
+// composite through gsr_forward_depth, which also fills them
+Forward6 forward_impl(
     const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
     const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
     double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
     int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
-    bool prefiltered, bool debug, int64_t shading) {
+    bool prefiltered, bool debug, int64_t shading, Planes *planes) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -95,6 +110,11 @@ Forward6 rasterize_gaussians_shaded(
     torch::Tensor geom = torch::empty({0}, bytes), binning = torch::empty({0}, bytes),
                   img = torch::empty({0}, bytes);
     int64_t num_rendered = 0;
+    if (planes) {  // a pixel that composites nothing: depth 0, inverse depth 0, transmittance 1
+        planes->depth_map = P ? torch::empty({H, W}, f32) : torch::zeros({H, W}, f32);
+        planes->inv_depth_map = P ? torch::empty({H, W}, f32) : torch::zeros({H, W}, f32);
+        planes->final_T = P ? torch::empty({H, W}, f32) : torch::ones({H, W}, f32);
+    }
     if (P != 0) {
         std::vector<torch::Tensor> keep;
         gsr_gaussians g{};
@@ -131,12 +151,48 @@ Forward6 rasterize_gaussians_shaded(
         int rc;
         {  // the forward waits for K (pinned memory): other Python threads may run meanwhile
             pybind11::gil_scoped_release no_gil;
-            rc = gsr_forward_shaded(ctx, &g, &st, &out, (int32_t)shading, s);
+            if (planes) {
+                out.final_T = planes->final_T.data_ptr<float>();
+                gsr_depth_outputs d{planes->depth_map.data_ptr<float>(),
+                                    planes->inv_depth_map.data_ptr<float>()};
+                rc = gsr_forward_depth(ctx, &g, &st, &out, &d, s);
+            } else {
+                rc = gsr_forward_shaded(ctx, &g, &st, &out, (int32_t)shading, s);
+            }
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_forward failed (", rc, "): ", gsr_last_error());
         num_rendered = out.num_rendered;
     }
     return std::make_tuple(num_rendered, color, radii, geom, binning, img);
+}
+
+Forward6 rasterize_gaussians_shaded(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
+    int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
+    bool prefiltered, bool debug, int64_t shading) {
+    return forward_impl(background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height,
+                        image_width, sh, degree, campos, prefiltered, debug, shading, nullptr);
+}
+
+// upstream's 19 arguments -> (num_rendered, color, radii, depth_map, inv_depth_map, final_T)
+Forward6 rasterize_gaussians_planes(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
+    int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
+    bool prefiltered, bool debug) {
+    Planes pl;
+    Forward6 r = forward_impl(background, means3D, colors, opacity, scales, rotations,
+                              scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                              tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                              debug, GSR_SHADE_SPLAT, &pl);
+    return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), pl.depth_map,
+                           pl.inv_depth_map, pl.final_T);
 }
 
 Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tensor &means3D,
@@ -156,24 +212,42 @@ Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tenso
 using Backward8 = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
                              torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
 
-Backward8 rasterize_gaussians_backward(
-    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
-    const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
-    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+// The backward of both entries.  planes (3 tensors: dL_ddepth_map, dL_dinv_depth_map,
+// dL_dfinal_T, each [H,W] or empty = unused), or nullptr: gsr_backward.  With a plane gradient
+// dL_dout_color may be empty.
+Backward8 backward_impl(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &scales, const torch::Tensor &rotations, double scale_modifier,
+    const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy,
     const torch::Tensor &dL_dout_color, const torch::Tensor &sh, int64_t degree,
-    const torch::Tensor &campos, const torch::Tensor &geomBuffer, int64_t R,
-    const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, bool debug,
-    const torch::Tensor &opacities) {
-    (void)radii, (void)geomBuffer, (void)R, (void)binningBuffer, (void)imageBuffer;
+    const torch::Tensor &campos, bool debug, const torch::Tensor &opacities,
+    const torch::Tensor *planes) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
-    TORCH_CHECK(dL_dout_color.dim() == 3 && dL_dout_color.size(0) == 3,
-                "dL_dout_color must have dimensions (3, H, W)");
+    const bool has_color = dL_dout_color.defined() && dL_dout_color.numel() != 0;
+    int64_t H = 0, W = 0;
+    if (has_color || !planes) {
+        TORCH_CHECK(dL_dout_color.dim() == 3 && dL_dout_color.size(0) == 3,
+                    "dL_dout_color must have dimensions (3, H, W)");
+        H = dL_dout_color.size(1), W = dL_dout_color.size(2);
+    }
+    if (planes) {
+        bool any = false;
+        for (int i = 0; i < 3; ++i) {
+            const torch::Tensor &t = planes[i];
+            if (!t.defined() || t.numel() == 0) continue;
+            TORCH_CHECK(t.dim() == 2, "a plane gradient must have dimensions (H, W)");
+            if (!has_color && !any) H = t.size(0), W = t.size(1);
+            TORCH_CHECK(t.size(0) == H && t.size(1) == W,
+                        "the image and plane gradients must share (H, W)");
+            any = true;
+        }
+        TORCH_CHECK(any || has_color, "dL_dout_color or a plane gradient is required");
+    }
     const torch::Device dev = means3D.device();
     const int64_t P = means3D.size(0);
-    const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
     const int64_t M = !(sh.defined() && sh.numel() != 0) ? 0
                       : sh.dim() == 3                    ? sh.size(1)
                                                          : (P ? sh.numel() / P / 3 : 0);
@@ -208,6 +282,12 @@ Backward8 rasterize_gaussians_backward(
         st.debug = debug ? 1 : 0;
         gsr_backward_inputs in{};
         in.dL_dcolor = opt_ptr(dL_dout_color, dev, "dL_dout_color", keep, 3 * H * W);
+        gsr_plane_gradients pg{};
+        if (planes) {
+            pg.dL_ddepth_map = opt_ptr(planes[0], dev, "dL_ddepth_map", keep, H * W);
+            pg.dL_dinv_depth_map = opt_ptr(planes[1], dev, "dL_dinv_depth_map", keep, H * W);
+            pg.dL_dfinal_T = opt_ptr(planes[2], dev, "dL_dfinal_T", keep, H * W);
+        }
         gsr_gradients gr{};
         gr.dL_dmeans3D = d_means3D.data_ptr<float>();
         gr.dL_dmeans2D = d_means2D.data_ptr<float>();
@@ -225,12 +305,44 @@ Backward8 rasterize_gaussians_backward(
         int rc;
         {  // the rebuild waits for K (pinned memory), as the forward does
             pybind11::gil_scoped_release no_gil;
-            rc = gsr_backward(ctx, &g, &st, &in, &gr, s);
+            rc = planes ? gsr_backward_planes(ctx, &g, &st, &in, &pg, &gr, s)
+                        : gsr_backward(ctx, &g, &st, &in, &gr, s);
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_backward failed (", rc, "): ", gsr_last_error());
     }
     return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales,
                            d_rot);
+}
+
+Backward8 rasterize_gaussians_backward(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+    const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy,
+    const torch::Tensor &dL_dout_color, const torch::Tensor &sh, int64_t degree,
+    const torch::Tensor &campos, const torch::Tensor &geomBuffer, int64_t R,
+    const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, bool debug,
+    const torch::Tensor &opacities) {
+    (void)radii, (void)geomBuffer, (void)R, (void)binningBuffer, (void)imageBuffer;
+    return backward_impl(background, means3D, colors, scales, rotations, scale_modifier,
+                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
+                         sh, degree, campos, debug, opacities, nullptr);
+}
+
+// This package's own: the forward's inputs in rasterize_gaussians' order (opacities in place),
+// then the four gradients of rasterize_gaussians_planes' image-like outputs (empty = unused).
+Backward8 rasterize_gaussians_backward_planes(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T) {
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    return backward_impl(background, means3D, colors, scales, rotations, scale_modifier,
+                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
+                         sh, degree, campos, debug, opacities, planes);
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -276,6 +388,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "upstream RasterizeGaussiansBackwardCUDA: its 21 arguments, then opacities -> "
           "(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, "
           "dL_drotations)");
+    m.def("rasterize_gaussians_planes", &rasterize_gaussians_planes,
+          "rasterize_gaussians' 19 arguments -> (num_rendered, color, radii, depth_map, "
+          "inv_depth_map, final_T): the splat composite with its per-pixel planes");
+    m.def("rasterize_gaussians_backward_planes", &rasterize_gaussians_backward_planes,
+          "bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, "
+          "cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, sh, sh_degree, campos, debug, "
+          "dL_dout_color, dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T (empty = unused) -> "
+          "rasterize_gaussians_backward's 8-tuple");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -12,7 +12,9 @@ The names, field order, argument checks and return values below follow that thir
 rasterize_points.cu); the work is done by libgsr.so (HIP, gfx950) through `_lib`.
 The viewer renders under `torch.no_grad()` (renderer_cuda.py:214) and pays nothing for it, but the
 image is differentiable: `_RasterizeGaussians.backward` returns the gradients of the splat
-composite (`gsr_backward`, include/gsr.h), as upstream's does for training code.
+composite (`gsr_backward`, include/gsr.h), as upstream's does for training code.  With
+`GaussianRasterizationSettings.depth_maps` the rasterizer also returns depth_map, inv_depth_map and
+final_T, differentiable too (`_RasterizeGaussiansPlanes`, `gsr_backward_planes`).
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import torch
 from . import _lib
 
 
-class GaussianRasterizationSettings(NamedTuple):
+class _SettingsTuple(NamedTuple):
     image_height: int
     image_width: int
     tanfovx: float
@@ -40,6 +42,30 @@ class GaussianRasterizationSettings(NamedTuple):
     # not upstream's: one of _lib.GSR_SHADE_* (the GL backend's billboard / ball shadings,
     # include/gsr.h gsr_forward_shaded); last and defaulted, so upstream's constructions hold
     shading: int = 0
+
+
+class GaussianRasterizationSettings(_SettingsTuple):
+    """upstream's settings tuple (its 12 fields, then `shading`) and one more setting beside it:
+    depth_maps (not upstream's; the last argument, after shading, default False).  With it
+    GaussianRasterizer returns (color, radii, depth_map, inv_depth_map, final_T), the three (H, W)
+    planes of gsr_forward_depth / gsr_outputs, differentiable like the image
+    (gsr_backward_planes); the splat composite only.  It is an attribute of the instance, not an
+    element of the tuple: `_fields`, `_field_defaults`, unpacking and comparison stay those of the
+    13-field tuple that callers and tests of the shading rely on; `_replace` carries it."""
+    depth_maps = False  # (instances made by _make)
+
+    def __new__(cls, *args, depth_maps=False, **kwargs):
+        if len(args) == len(cls._fields) + 1:  # given by position, after shading
+            *args, depth_maps = args
+        self = super().__new__(cls, *args, **kwargs)
+        self.depth_maps = bool(depth_maps)
+        return self
+
+    def _replace(self, **kwargs):
+        depth_maps = kwargs.pop("depth_maps", self.depth_maps)
+        new = super()._replace(**kwargs)
+        new.depth_maps = bool(depth_maps)
+        return new
 
 
 def _device_of(t: torch.Tensor) -> torch.device:
@@ -200,20 +226,40 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
 def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, scales, rotations,
                                         scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
                                         tanfovx, tanfovy, dL_dout_color, sh, degree, campos,
-                                        debug=False, *, conic=False, stream=None, slot=0) -> dict:
+                                        debug=False, *, conic=False, stream=None, slot=0,
+                                        dL_ddepth_map=None, dL_dinv_depth_map=None,
+                                        dL_dfinal_T=None, depths=False) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
     upstream's units, z = 0), dL_dopacity (P, 1), dL_dcolors, dL_dcov3D, dL_dsh (with SHs),
-    dL_dscales and dL_drotations (with scales and rotations); conic=True adds dL_dconic (P, 3)."""
+    dL_dscales and dL_drotations (with scales and rotations); conic=True adds dL_dconic (P, 3).
+
+    With dL_ddepth_map, dL_dinv_depth_map or dL_dfinal_T ((H, W) each, None = unused), or
+    depths=True, the call is `gsr_backward_planes`: the planes' gradients join the image's
+    (dL_dout_color may then be None; H, W come from the first plane given), and depths=True adds
+    dL_ddepths (P,), dL/dz through the features z and 1 / z only."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if dL_dout_color.ndimension() != 3 or dL_dout_color.size(0) != 3:
+    plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
+                   "dL_dfinal_T": dL_dfinal_T}
+    plane_grads = {n: t for n, t in plane_grads.items() if t is not None}
+    if dL_dout_color is None and not plane_grads:
+        raise RuntimeError("dL_dout_color or a plane gradient is required")
+    if dL_dout_color is not None and (dL_dout_color.ndimension() != 3 or
+                                      dL_dout_color.size(0) != 3):
         raise RuntimeError("dL_dout_color must have dimensions (3, H, W)")
     device = _device_of(means3D)
     dev_index = device.index if device.index is not None else torch.cuda.current_device()
     P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    if dL_dout_color is not None:
+        H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    else:
+        first = next(iter(plane_grads.values()))
+        H, W = int(first.size(-2)), int(first.size(-1))
+    for n, t in plane_grads.items():
+        if t.ndimension() != 2 or tuple(t.shape) != (H, W):
+            raise RuntimeError(f"{n} must have dimensions (H, W) = ({H}, {W})")
     means3D = _as_dev(means3D, device, "P,3")
     opacities = _as_dev(opacities, device, "P,1")
     scales = _as_dev(scales, device, "P,3")
@@ -252,20 +298,35 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                 prefiltered=0, debug=int(bool(debug)))
     inp = _lib.GsrBackwardInputs(dL_dcolor=_lib.ptr(dL))
     out = _lib.GsrGradients(**{n: _lib.ptr(t) for n, t in grads.items()})
+    plane_grads = {n: _as_dev(t, device, "H,W") for n, t in plane_grads.items()}
+    if depths:
+        grads["dL_ddepths"] = torch.zeros((P,), **f32)
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     with torch.cuda.device(dev_index):
-        _lib.check(_lib.backward_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
-                                         ctypes.byref(out), ctypes.c_void_p(stream)),
-                   "gsr_backward")
+        if plane_grads or depths:
+            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
+                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
+            _lib.check(_lib.backward_planes_fn(lib)(
+                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp), ctypes.byref(planes),
+                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_planes")
+        else:
+            _lib.check(_lib.backward_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st),
+                                             ctypes.byref(inp), ctypes.byref(out),
+                                             ctypes.c_void_p(stream)), "gsr_backward")
     return grads
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings: GaussianRasterizationSettings):
-    """upstream rasterize_gaussians(...) -> (color, radii), through _RasterizeGaussians."""
+    """upstream rasterize_gaussians(...) -> (color, radii), through _RasterizeGaussians; with
+    raster_settings.depth_maps -> (color, radii, depth_map, inv_depth_map, final_T), through
+    _RasterizeGaussiansPlanes."""
+    if raster_settings.depth_maps:
+        return _RasterizeGaussiansPlanes.apply(means3D, means2D, sh, colors_precomp, opacities,
+                                               scales, rotations, cov3Ds_precomp, raster_settings)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      rotations, cov3Ds_precomp, raster_settings)
 
@@ -365,6 +426,79 @@ class _RasterizeGaussians(torch.autograd.Function):
                     rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier,
                     cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
                     rs.sh_degree, rs.campos, e, ctx.num_rendered, e, e, rs.debug, opacities)
+        has = lambda t: t.numel() != 0  # noqa: E731
+        return (d_means3D, d_means2D if ctx.has_means2D else None,
+                d_sh.reshape(sh.shape) if has(sh) else None,
+                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
+                d_scales if has(scales) else None, d_rot if has(rotations) else None,
+                d_cov3D if has(cov3Ds) else None, None)
+
+
+PLANE_NAMES = ("depth_map", "inv_depth_map", "final_T")
+
+
+class _RasterizeGaussiansPlanes(torch.autograd.Function):
+    """`_RasterizeGaussians` with the per-pixel planes (GaussianRasterizationSettings.depth_maps):
+    returns (color, radii, depth_map, inv_depth_map, final_T).  The planes are those of
+    `rasterize_gaussians_native(extras=PLANE_NAMES)` bit for bit, color and radii those of the
+    plain call.  All four image-like outputs are differentiable through one `gsr_backward_planes`
+    call; an output the loss does not use (its incoming gradient is None) travels as NULL.  Under
+    `torch.no_grad()` nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                cov3Ds_precomp, raster_settings):
+        rs = raster_settings
+        if rs.shading != _lib.GSR_SHADE_SPLAT:
+            raise RuntimeError("depth_map / inv_depth_map come from the splat composite: not "
+                               f"available with shading {rs.shading}")
+        ctx.has_means2D = isinstance(means2D, torch.Tensor)
+        none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
+        args = (rs.bg, means3D, none(colors_precomp), opacities, none(scales), none(rotations),
+                rs.scale_modifier, none(cov3Ds_precomp), rs.viewmatrix, rs.projmatrix,
+                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, none(sh), rs.sh_degree,
+                rs.campos, rs.prefiltered, rs.debug)
+        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
+            res = rasterize_gaussians_native(*args, extras=PLANE_NAMES)
+            color, radii = res.color, res.radii
+            planes = tuple(res.extras[n] for n in PLANE_NAMES)
+        else:
+            from . import _C
+            _, color, radii, *planes = _C.rasterize_gaussians_planes(*args)
+        ctx.raster_settings = rs
+        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
+                              none(rotations), none(cov3Ds_precomp))
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not zeros
+        return (color, radii, *planes)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_inv_depth, grad_final_T):
+        """Gradients in input order, as `_RasterizeGaussians.backward`."""
+        del grad_radii
+        rs = ctx.raster_settings
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = ctx.saved_tensors
+        grads = [None if t is None else t.contiguous()
+                 for t in (grad_color, grad_depth, grad_inv_depth, grad_final_T)]
+        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
+            g = rasterize_gaussians_backward_native(
+                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
+                cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
+                rs.sh_degree, rs.campos, rs.debug, dL_ddepth_map=grads[1],
+                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3])
+            z = lambda n: g.get(n)  # noqa: E731
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
+                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
+                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
+        else:
+            from . import _C
+            e = torch.empty(0)
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = \
+                _C.rasterize_gaussians_backward_planes(
+                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
+                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
+                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug,
+                    *(e if t is None else t for t in grads))
         has = lambda t: t.numel() != 0  # noqa: E731
         return (d_means3D, d_means2D if ctx.has_means2D else None,
                 d_sh.reshape(sh.shape) if has(sh) else None,

@@ -217,7 +217,7 @@ int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster
  * do SH coefficients above the active degree D.  With cov3D_precomp the chain ends at dL_dcov3D
  * (dL_dscales and dL_drotations, if asked for, are 0); with colors_precomp at dL_dcolors (dL_dsh 0).
  * Whole frames only (a strip: GSR_E_INVALID); prefiltered, debug and scale_modifier as in the
- * forward.  Gradients of the depth planes and of bg are not provided.
+ * forward.  The gradients of the depth planes come from gsr_backward_planes (below); bg gets none.
  * Inputs only: the call is a function of its arguments.  It rebuilds the per-Gaussian stage, the
  * depth sort and upstream's (untight) lists from them, launched directly (no frame graph is
  * replayed; recorded graphs stay usable), and recomputes each pixel's transmittance inside its
@@ -242,6 +242,48 @@ typedef struct {
 } gsr_gradients;
 int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                  const gsr_backward_inputs *in, gsr_gradients *grads, void *stream);
+/* gsr_backward that also takes the gradients of the per-pixel planes of the same composite:
+ * depth_map and inv_depth_map (gsr_forward_depth) and final_T (gsr_outputs).  (Additive to ABI 4:
+ * gsr_backward, gsr_backward_inputs and gsr_gradients keep their layout.)
+ * With alpha_i, T_i and w_i = alpha_i T_i of the splats i = 1..n a pixel composites,
+ *   depth_map     = sum_i z_i w_i        a colour channel with feature z_i,     background 0
+ *   inv_depth_map = sum_i (1 / z_i) w_i  a colour channel with feature 1 / z_i, background 0
+ *   final_T       = prod_i (1 - alpha_i) a colour channel with feature 0,       background 1
+ * -- the channel identity gsr_forward_depth states bit for bit -- so their gradients run through
+ * gsr_backward's recursion as three more channels.  With g = dL/dcolor, gd = dL/ddepth_map,
+ * gi = dL/dinv_depth_map and gT = dL/dfinal_T at the pixel, and every gate, skip and cap held
+ * constant exactly as in gsr_backward:
+ *   - the value carried back to front starts at g . bg + gT (gsr_backward: g . bg);
+ *   - the per-splat term is gc_i = g . c_i + gd z_i + gi (1 / z_i), and dL/dalpha_i =
+ *     T_i (gc_i - r_i) with r_i the carried value behind splat i; from it dL_dmeans2D, dL_dconic
+ *     and dL_dopacity follow as in gsr_backward (the 0.99 cap passes nothing);
+ *   - one more sum per splat, the direct path through the features:
+ *     dL/dz_i += w_i (gd - gi (1 / z_i)^2), with 1 / z_i the rounded float32 quotient the forward
+ *     uses and its derivative taken as -(1 / z_i)^2.
+ * z is the view-space depth, z = vm[2] x + vm[6] y + vm[10] z_world + vm[14] (column-major), so the
+ * per-Gaussian stage adds (vm[2], vm[6], vm[10]) dL/dz to dL_dmeans3D.  The z <= 0.2 cull is a
+ * gate: a listed Gaussian has a finite z > 0.2, a culled one gets exact zeros.
+ * final_T is here because every consumer of the two depth planes divides by 1 - final_T: the
+ * expected depth of the covered part, and stereo.metric_disparity(normalise=True).
+ * dL_ddepths (optional output, [P]) is dL/dz through the features z and 1 / z only -- the new sum
+ * by itself, not the gradient through the projection (depths is not an input).  The plane features
+ * are not colours: dL_dcolors gets nothing from them; every member of gsr_gradients means what it
+ * means in gsr_backward.
+ * A NULL struct, or one whose three inputs are NULL, is gsr_backward itself: the same kernels, the
+ * same arguments, dL_dcolor required; dL_ddepths, if given, is then zero-filled.  With at least one
+ * plane gradient in->dL_dcolor may be NULL and reads as zero.  Everything else is gsr_backward's:
+ * whole frames only, a function of its inputs (it rebuilds the lists), zeroes then fills each
+ * gradient given, exact zeros for culled Gaussians, timing through gsr_backward_times, and
+ * gsr_get_binning exports the backward's lists afterwards. */
+typedef struct {
+    const float *dL_ddepth_map;     /* [H,W] or NULL */
+    const float *dL_dinv_depth_map; /* [H,W] or NULL */
+    const float *dL_dfinal_T;       /* [H,W] or NULL */
+    float *dL_ddepths;              /* optional output [P]: dL/dz through the features only */
+} gsr_plane_gradients;
+int gsr_backward_planes(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                        gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

@@ -10,9 +10,14 @@ per frame taken from --contributions (they are not counted on the device; the de
 from the forward's ~118 composited splats per quadrant wave, blend.hip), so the byte figure is an
 upper estimate: a staged splat no pixel of the quadrant composites adds nothing.
 
+--planes: the backward is gsr_backward_planes with the gradients of depth_map, inv_depth_map and
+final_T beside the image's (k_blend_bwd_planes_q, k_preprocess_bwd_planes: ten sums, 40 B per
+contribution); the forward timed is then gsr_forward_depth with final_T, the frame that backward
+belongs to.
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
-Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10]
+Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
 """
 import argparse
 import ctypes
@@ -43,19 +48,24 @@ def worker(a):
     view, proj, campos, tx, ty, _ = scene.cams[0]
     color = torch.empty((3, scene.H, scene.W), device=dev)
     dL = torch.randn((3, scene.H, scene.W), device=dev)
+    extras, plane_grads = (), {}
+    if a.planes:
+        extras = ("depth_map", "inv_depth_map", "final_T")
+        plane_grads = {f"dL_d{n}": torch.randn((scene.H, scene.W), device=dev) for n in extras}
 
     def forward():
         return rasterize_gaussians_native(scene.bg, scene.xyz, None, scene.opacity, scene.scale,
                                           scene.rot, 1.0, None, view, proj, tx, ty, scene.H,
                                           scene.W, scene.sh, scene.deg, campos, False, False,
-                                          out_color=color)
+                                          out_color=color, extras=extras)
 
     def backward():
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
                                                    scene.scale, scene.rot, 1.0, None, view, proj,
-                                                   tx, ty, dL, scene.sh, scene.deg, campos)
+                                                   tx, ty, dL, scene.sh, scene.deg, campos,
+                                                   **plane_grads)
 
-    out = {"config": a.config, "steps": a.steps}
+    out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes)}
     if a.step == "forward":
         for _ in range(a.warmup):
             forward()
@@ -97,6 +107,8 @@ def main():
     ap.add_argument("--contributions", type=float, default=3.9e6,
                     help="(splat, quadrant) contributions per frame (C3: ~118 composited splats "
                          "per quadrant wave, blend.hip)")
+    ap.add_argument("--planes", action="store_true",
+                    help="gsr_backward_planes: colour plus the three planes' gradients")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -104,13 +116,14 @@ def main():
     out = {}
     for step in ("forward", "backward"):  # a fresh process each, under its own time limit
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", a.config,
-                            "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step],
+                            "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step] +
+                           (["--planes"] if a.planes else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"bench_backward: the {step} step failed ({r.returncode}); nothing more is run")
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    atomic_bytes = a.contributions * BYTES_PER_CONTRIBUTION
+    atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0))
     out["atomic_MB_per_frame_upper"] = round(atomic_bytes / 1e6, 1)
     out["atomic_GBs_if_all_added"] = round(atomic_bytes / (out["blend_bwd_ms"] * 1e-3) / 1e9, 1)
     out["atomic_rate_share"] = round(out["atomic_GBs_if_all_added"] / ATOMIC_RATE_GBS, 3)
