@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = (
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
-    "gsr_backward_planes",
+    "gsr_backward_planes", "gsr_forward_surface",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -80,6 +80,11 @@ class GsrOutputs(ctypes.Structure):
 class GsrDepthOutputs(ctypes.Structure):
     """gsr_depth_outputs: gsr_forward_depth's optional per-pixel planes."""
     _fields_ = [("depth_map", ctypes.c_void_p), ("inv_depth_map", ctypes.c_void_p)]
+
+
+class GsrSurfaceOutputs(ctypes.Structure):
+    """gsr_surface_outputs: gsr_forward_surface's optional per-pixel median planes."""
+    _fields_ = [("median_depth", ctypes.c_void_p), ("median_id", ctypes.c_void_p)]
 
 
 class GsrBackwardInputs(ctypes.Structure):
@@ -135,6 +140,14 @@ def _declare(lib: ctypes.CDLL) -> None:
                                           ctypes.POINTER(GsrOutputs),
                                           ctypes.POINTER(GsrDepthOutputs), vp]
         lib.gsr_forward_depth.restype = i32
+    # (an older build of ABI 4 loaded through GSR_LIB lacks it: forward_surface_fn() says so)
+    if hasattr(lib, "gsr_forward_surface"):
+        lib.gsr_forward_surface.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                            ctypes.POINTER(GsrRasterSettings),
+                                            ctypes.POINTER(GsrOutputs),
+                                            ctypes.POINTER(GsrDepthOutputs),
+                                            ctypes.POINTER(GsrSurfaceOutputs), vp]
+        lib.gsr_forward_surface.restype = i32
     # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_fn() says so)
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward.argtypes = [vp, ctypes.POINTER(GsrGaussians),
@@ -204,6 +217,16 @@ def forward_depth_fn(lib: ctypes.CDLL):
     if fn is None:
         raise RuntimeError(
             f"{LIB_PATH} has no gsr_forward_depth: the depth_map / inv_depth_map outputs need a "
+            "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
+    return fn
+
+
+def forward_surface_fn(lib: ctypes.CDLL):
+    """gsr_forward_surface of a loaded library; RuntimeError if that build does not have it."""
+    fn = getattr(lib, "gsr_forward_surface", None)
+    if fn is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_forward_surface: the median_depth / median_id outputs need a "
             "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
     return fn
 

@@ -14,6 +14,7 @@
 //   6 join                                          <- join
 //   7 blend             (blend.hip)               gsr_forward_shaded: a GL shading's first-hit kernel
 //                                                  gsr_forward_depth: the depth-accumulating composite
+//                                                  gsr_forward_surface: ... that notes the median splat
 //
 // Binning has two forms with identical results: the column-first form above (default), and the
 // per-pair form (offsets scan -> duplicate fused with the first tile-sort pass -> the remaining
@@ -112,8 +113,9 @@ constexpr int64_t kMinListCap = 1 << 16;
 // The shading (gsr_forward_shaded) reaches the recorded chains only through `tight` -- the
 // billboard's full lists -- and selects the blend's kernel, which is launched directly after
 // them: frames of different shadings and equal lists share their graphs.  So do depth frames
-// (gsr_forward_depth) and plain ones: the planes are arguments of that direct launch alone, and the
-// depth keys it reads are written by the preprocess, which is a direct launch too.
+// (gsr_forward_depth), surface frames (gsr_forward_surface) and plain ones: the planes are
+// arguments of that direct launch alone, and the depth keys it reads are written by the
+// preprocess, which is a direct launch too.
 struct GraphKey {
     uint64_t ws_gen;
     int64_t cap, P;
@@ -362,6 +364,9 @@ struct Frame {
     int shading = GSR_SHADE_SPLAT;  // gsr_forward_shaded: the kernel of stage 7
     // gsr_forward_depth: the planes stage 7 also fills (both NULL: the plain composite)
     float *depth_map = nullptr, *inv_depth_map = nullptr;
+    // gsr_forward_surface: the median planes stage 7 also fills (both NULL: none)
+    float *median_depth = nullptr;
+    int32_t *median_id = nullptr;
     bool no_blend = false;  // gsr_backward's rebuild: everything up to the lists, no stage 7
     uint64_t K = 0;   // upstream's num_rendered
     uint64_t KL = 0;  // pairs in the list (K, or fewer with tight binning)
@@ -826,6 +831,12 @@ int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st
         GSR_HIP(gsr_launch_shade(ba, f.shading, f.s), "shade launch");
         return GSR_OK;
     }
+    if (f.median_depth || f.median_id) {  // (the depth keys: as below)
+        const GsrDepthArgs da{f.pa.sort_keys, f.depth_map, f.inv_depth_map};
+        const GsrSurfaceArgs ma{f.median_depth, f.median_id};
+        GSR_HIP(gsr_launch_blend_surface(ba, da, ma, f.s), "surface blend launch");
+        return GSR_OK;
+    }
     if (f.depth_map || f.inv_depth_map) {
         // z by Gaussian id from the depth keys: written by this frame's preprocess on f.s and only
         // read since (the depth sort takes them const); the next writer is the next call's
@@ -1122,12 +1133,17 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
             gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth,
-            bool no_blend = false) {
+            bool no_blend = false, const gsr_surface_outputs *surface = nullptr) {
     Frame f;
     ctx->last.valid = false;
+    // the planes of the call, set again after every setup_frame
+    auto planes = [&]() {
+        if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
+        if (surface) f.median_depth = surface->median_depth, f.median_id = surface->median_id;
+        f.no_blend = no_blend;
+    };
     GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
-    if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
-    f.no_blend = no_blend;
+    planes();
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
@@ -1148,8 +1164,7 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         ctx->list_cap = list_capacity((int64_t)f.KL, ctx->list_cap);
         GSR_TRY(reserve_K(ctx, ctx->list_cap, s));
         GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
-        if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
-        f.no_blend = no_blend;
+        planes();
         f.graph = false;
     }
 
@@ -1160,6 +1175,12 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
             if (plane)
                 GSR_HIP(hipMemsetAsync(plane, 0, (size_t)f.rows_out * f.W * sizeof(float), s),
                         "hipMemsetAsync(depth plane)");
+        if (f.median_depth)
+            GSR_HIP(hipMemsetAsync(f.median_depth, 0, (size_t)f.rows_out * f.W * sizeof(float), s),
+                    "hipMemsetAsync(median depth)");
+        if (f.median_id)  // -1: no surface
+            GSR_HIP(hipMemsetAsync(f.median_id, 0xFF, (size_t)f.rows_out * f.W * sizeof(int32_t), s),
+                    "hipMemsetAsync(median id)");
         GSR_HIP(hipMemsetAsync(ctx->ranges_words(), 0, f.T_strip * 8, s), "hipMemsetAsync");
         // an empty list in the per-pair form's buffers; no stage ran, so no timed frame
         f.K = f.KL = 0;
@@ -1416,6 +1437,16 @@ int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster
     std::lock_guard<std::mutex> lock(ctx->mu);
     GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
     return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth);
+}
+
+int gsr_forward_surface(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                        gsr_outputs *out, const gsr_depth_outputs *depth,
+                        const gsr_surface_outputs *surface, void *stream) {
+    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
+    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth, false,
+                   surface);
 }
 
 int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,

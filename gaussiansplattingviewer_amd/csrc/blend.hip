@@ -132,11 +132,22 @@ struct StagedSplat {
 // z1, 1/z1} lies in 16 B of LDS of its own (the paired-slot layout has no spare word in e): one
 // more LDS read per composited pair.  The pad slot of an odd count holds 0, 0 (weight 0 times a
 // finite feature).  Without kDepth none of it is compiled: k_blend_q is the kernel it was.
-template <bool kFast, bool kContrib, bool kDepth>
+//
+// kMedian (k_blend_surface_q, gsr_forward_surface): the median splat of a pixel is the composited
+// splat in front of which T > 0.5 and behind which T <= 0.5.  T only falls, so at most one splat
+// of a list qualifies: the pixel keeps that splat's list position + 1 (the word the kContrib
+// staging carries, so these kernels stage unpaired whatever kContrib is) -- two compares and a
+// select per composited splat -- and the epilogue gathers the Gaussian id from the list and z from
+// the depth keys once per pixel.  The terminating splat cannot qualify (alpha <= 0.99 and
+// T' < 1e-4 need T < 0.01), nor can a skipped one (T' = T), nor anything after the pixel is done
+// (T <= 0).  Without kMedian none of it is compiled.
+template <bool kFast, bool kContrib, bool kDepth, bool kMedian = false>
 __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
-                                        const GsrDepthArgs &d) {
+                                        const GsrDepthArgs &d,
+                                        const GsrSurfaceArgs &m = GsrSurfaceArgs{}) {
     __shared__ StagedSplat s_spl_q[4][64];  // per quadrant wave
-    constexpr bool kPair = kFast && !kContrib;  // paired colour / bound words (see staging)
+    // paired colour / bound words (see staging)
+    constexpr bool kPair = kFast && !kContrib && !kMedian;
 
     const uint32_t tile = xcd_tile(blockIdx.x, a.order, (n_tiles + kGroupTiles - 1) / kGroupTiles);
     if (tile >= n_tiles) return;
@@ -164,6 +175,7 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
     float T = inside ? 1.0f : -1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
     float D0 = 0.0f, D1 = 0.0f;  // kDepth: sum z w, sum (1 / z) w
     uint32_t last_contributor = 0;
+    uint32_t median_pos = 0;  // kMedian: list position + 1 of the median splat, 0 = none (yet)
     auto live_any = [&]() { return __ballot(!(T <= 0.0f)) != 0ull; };
     if (!live_any()) return;
 
@@ -201,6 +213,8 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             }
             if (kContrib)
                 last_contributor = (vis && !lo) ? __float_as_uint(sp.e.y) : last_contributor;
+            if constexpr (kMedian)  // (a done pixel has T <= 0; a skipped splat test_T = T)
+                median_pos = (T > 0.5f && test_T <= 0.5f) ? __float_as_uint(sp.e.y) : median_pos;
             T = T_next;
             return;
         } else {
@@ -219,6 +233,9 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
                 D0 = acc ? D0 + fz * alpha * T : D0;
                 D1 = acc ? D1 + fiz * alpha * T : D1;
             }
+            if constexpr (kMedian)
+                median_pos =
+                    (acc && T > 0.5f && test_T <= 0.5f) ? __float_as_uint(sp.e.y) : median_pos;
         }
         T = acc ? test_T : (term ? -fabsf(T) : T);
         if (kContrib) last_contributor = acc ? __float_as_uint(sp.e.y) : last_contributor;
@@ -365,6 +382,17 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             if (d.depth_map) d.depth_map[pid] = D0;
             if (d.inv_depth_map) d.inv_depth_map[pid] = D1;
         }
+        if constexpr (kMedian) {  // no surface: id -1, depth 0
+            // (median_pos is a staged position + 1 of this list: range.x + median_pos - 1 < range.y)
+            int32_t id = -1;
+            float z = 0.0f;
+            if (median_pos) {
+                id = (int32_t)(a.point_list[range.x + median_pos - 1u] & a.id_mask);
+                if (m.median_depth) z = __uint_as_float(d.z_bits[id]);
+            }
+            if (m.median_depth) m.median_depth[pid] = z;
+            if (m.median_id) m.median_id[pid] = id;
+        }
     }
 }
 
@@ -381,6 +409,17 @@ __global__ __launch_bounds__(256, kDepthWaves) void k_blend_depth_q(const GsrBle
                                                                     uint32_t n_tiles,
                                                                     const GsrDepthArgs d) {
     blend_q<kFast, kContrib, true>(a, n_tiles, d);
+}
+
+// The median-noting forms: the plain composite's 12 KiB of LDS or the depth form's 14 (kDepth).
+// The median position is one more live register per pixel: at the plain composite's 8 waves per
+// SIMD (64 VGPRs) the fast forms spilled 8 and 16 B per lane, at kSurfaceWaves none do
+// (profiles/median_resources.txt); with kDepth the depth form's budget holds it.
+constexpr int kSurfaceWaves = 7;
+template <bool kFast, bool kContrib, bool kDepth>
+__global__ __launch_bounds__(256, kDepth ? kDepthWaves : kSurfaceWaves) void k_blend_surface_q(
+    const GsrBlendArgs a, uint32_t n_tiles, const GsrDepthArgs d, const GsrSurfaceArgs m) {
+    blend_q<kFast, kContrib, kDepth, true>(a, n_tiles, d, m);
 }
 
 // Grid of whole XCD groups: one block per tile, kGroupTiles per XCD round; blocks past the
@@ -579,4 +618,29 @@ hipError_t gsr_launch_blend_depth(const GsrBlendArgs &a, const GsrDepthArgs &d, 
     else
         hipLaunchKernelGGL((k_blend_depth_q<false, true>), grid, dim3(256), 0, s, a, n_tiles, d);
     return hipGetLastError();
+}
+
+template <bool kDepth>
+static hipError_t launch_surface(const GsrBlendArgs &a, const GsrDepthArgs &d,
+                                 const GsrSurfaceArgs &m, uint32_t n_tiles, hipStream_t s) {
+    const dim3 grid(xcd_grid(n_tiles));
+    if (a.fast && !a.n_contrib)
+        hipLaunchKernelGGL((k_blend_surface_q<true, false, kDepth>), grid, dim3(256), 0, s, a,
+                           n_tiles, d, m);
+    else if (a.fast)
+        hipLaunchKernelGGL((k_blend_surface_q<true, true, kDepth>), grid, dim3(256), 0, s, a,
+                           n_tiles, d, m);
+    else
+        hipLaunchKernelGGL((k_blend_surface_q<false, true, kDepth>), grid, dim3(256), 0, s, a,
+                           n_tiles, d, m);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_blend_surface(const GsrBlendArgs &a, const GsrDepthArgs &d,
+                                    const GsrSurfaceArgs &m, hipStream_t s) {
+    if (!d.z_bits || (!m.median_depth && !m.median_id)) return hipErrorInvalidValue;
+    if (a.rows_tiles == 0 || a.grid_x == 0) return hipSuccess;
+    const uint32_t n_tiles = a.grid_x * a.rows_tiles;
+    if (d.depth_map || d.inv_depth_map) return launch_surface<true>(a, d, m, n_tiles, s);
+    return launch_surface<false>(a, d, m, n_tiles, s);
 }

@@ -576,6 +576,16 @@ struct GsrDepthArgs {
     float *depth_map, *inv_depth_map;
 };
 hipError_t gsr_launch_blend_depth(const GsrBlendArgs &a, const GsrDepthArgs &d, hipStream_t s);
+// gsr_forward_surface's planes (blend.hip k_blend_surface_q): the composite of gsr_launch_blend
+// (d's planes both NULL) or of gsr_launch_blend_depth, which also notes the splat at which the
+// pixel's transmittance crosses 0.5 and writes its Gaussian id and that Gaussian's z (d.z_bits,
+// required).  Either plane may be NULL (not both), [rows_out, W] strip-local like final_T.
+struct GsrSurfaceArgs {
+    float *median_depth;
+    int32_t *median_id;
+};
+hipError_t gsr_launch_blend_surface(const GsrBlendArgs &a, const GsrDepthArgs &d,
+                                    const GsrSurfaceArgs &m, hipStream_t s);
 // The GL backend's geometry shadings in place of the composite (blend.hip k_shade_q): shading =
 // GSR_SHADE_BILLBOARD / FLAT_BALL / GAUSS_BALL.  Same arguments; a.fast is not read.
 hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);

@@ -110,6 +110,11 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                    inv_depth_map, (rows, W) float32: the sums of z and 1 / z under the colour's
                    weights, premultiplied (gsr_forward_depth in include/gsr.h; `depths` stays the
                    per-Gaussian view-space z).  Splat composite only: RuntimeError with a shading;
+                   and the median planes median_depth (rows, W) float32 and median_id (rows, W)
+                   int32: the view-space z and the global Gaussian id of the splat at which the
+                   pixel's transmittance crosses 0.5, 0.0 / -1 where it never does
+                   (gsr_forward_surface; any combination with the other extras).  Splat composite
+                   only, like the depth planes;
       stream    -- HIP stream handle (default: torch's current stream);
       slot      -- context slot (`_lib.context`): forwards in different slots may overlap;
       out_color -- preallocated contiguous f32 (3, rows, W) output (e.g. a gather buffer);
@@ -127,6 +132,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     depth_planes = [n for n in ("depth_map", "inv_depth_map") if n in extras]
     if depth_planes and shading != _lib.GSR_SHADE_SPLAT:
         raise RuntimeError("depth_map / inv_depth_map come from the splat composite: not "
+                           f"available with shading {shading}")
+    surface_planes = [n for n in ("median_depth", "median_id") if n in extras] if extras else ()
+    if surface_planes and shading != _lib.GSR_SHADE_SPLAT:
+        raise RuntimeError("median_depth / median_id come from the splat composite: not "
                            f"available with shading {shading}")
     device = _device_of(means3D)
     dev_index = device.index if device.index is not None else torch.cuda.current_device()
@@ -181,8 +190,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
             ext[name] = torch.zeros((P, 3), **f32)
         elif name == "tiles_touched":
             ext[name] = torch.zeros((P,), dtype=torch.int32, device=device)
-        elif name in ("final_T", "depth_map", "inv_depth_map"):
+        elif name in ("final_T", "depth_map", "inv_depth_map", "median_depth"):
             ext[name] = torch.zeros((rows, W), **f32)
+        elif name == "median_id":
+            ext[name] = torch.full((rows, W), -1, dtype=torch.int32, device=device)
         elif name == "n_contrib":
             ext[name] = torch.zeros((rows, W), dtype=torch.int32, device=device)
         else:
@@ -201,14 +212,21 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     out = _lib.GsrOutputs(color=color.data_ptr(),
                           radii=radii.data_ptr() if P and radii is not None else None)
     for name, t in ext.items():
-        if name not in depth_planes:
+        if name not in depth_planes and name not in surface_planes:
             setattr(out, name, t.data_ptr())
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     with torch.cuda.device(dev_index):
-        if depth_planes:
+        if surface_planes:
+            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
+            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
+            _lib.check(_lib.forward_surface_fn(lib)(
+                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
+                ctypes.byref(planes) if depth_planes else None, ctypes.byref(surface),
+                ctypes.c_void_p(stream)), "gsr_forward_surface")
+        elif depth_planes:
             planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
             _lib.check(_lib.forward_depth_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st),
                                                   ctypes.byref(out), ctypes.byref(planes),

@@ -82,13 +82,15 @@ def gaus_hip_from_cpu(gau, device="cuda") -> GaussianDataHIP:
 
 
 class _RendererOptions(type):
-    """HIPRenderer(w, h, ..., depth_maps=False): the keyword is taken at construction, here,
-    because `__init__`'s parameter list is pinned as it stands (tests/test_shading_reference.py
-    test_python_api_carries_the_shading compares it name for name)."""
+    """HIPRenderer(w, h, ..., depth_maps=False, surface_maps=False): the keywords are taken at
+    construction, here, because `__init__`'s parameter list is pinned as it stands
+    (tests/test_shading_reference.py test_python_api_carries_the_shading compares it name for
+    name)."""
 
-    def __call__(cls, *args, depth_maps=False, **kw):
+    def __call__(cls, *args, depth_maps=False, surface_maps=False, **kw):
         r = super().__call__(*args, **kw)
         r.depth_maps = bool(depth_maps)
+        r.surface_maps = bool(surface_maps)
         return r
 
 
@@ -99,7 +101,13 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
     (gsr_forward_depth) in self.depth_map / self.inv_depth_map / self.final_T, (rows, W) float32
     beside self.image; None under a GL shading (nothing is composited there).  It then renders
     through rasterize_gaussians_native (ctypes) for full frames too: the `_C` entry points keep
-    upstream's signatures.  False: nothing changes."""
+    upstream's signatures.  False: nothing changes.
+
+    surface_maps (keyword, default False): draw() also leaves the median planes of the same blend
+    pass (gsr_forward_surface) in self.median_depth (float32) / self.median_id (int32), (rows, W):
+    the view-space z and the Gaussian id of the splat at which the pixel's transmittance crosses
+    0.5, 0.0 / -1 where nothing does; None under a GL shading.  pick(x, y) reads one id back.
+    Independent of depth_maps; renders through ctypes like it.  False: nothing changes."""
 
     # GL render_mod -> gsr_forward_shaded's shading (gau_frag.glsl:15-38)
     GL_SHADINGS = {-2: _lib.GSR_SHADE_BILLBOARD, -3: _lib.GSR_SHADE_FLAT_BALL,
@@ -110,6 +118,8 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
         self.gl_shading = bool(gl_shading)  # render the GL backend's ball / billboard modes
         self.depth_maps = False  # (set by the constructor's depth_maps keyword)
         self.depth_map = self.inv_depth_map = self.final_T = None
+        self.surface_maps = False  # (set by the constructor's surface_maps keyword)
+        self.median_depth = self.median_id = None
         self.device = torch.device(device)
         self.raster_settings = {
             "image_height": int(h),
@@ -217,8 +227,12 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
         rs = GaussianRasterizationSettings(**settings)
         planes = {}
         with torch.no_grad():
-            if self.depth_maps:
-                extras = () if rs.shading else ("depth_map", "inv_depth_map", "final_T")
+            if self.depth_maps or self.surface_maps:
+                extras = ()
+                if self.depth_maps and not rs.shading:
+                    extras += ("depth_map", "inv_depth_map", "final_T")
+                if self.surface_maps and not rs.shading:
+                    extras += ("median_depth", "median_id")
                 res = rasterize_gaussians_native(
                     rs.bg, g.xyz, colors, g.opacity, g.scale, g.rot, rs.scale_modifier, None,
                     rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
@@ -240,7 +254,25 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
         if self.depth_maps:
             self.depth_map, self.inv_depth_map = planes.get("depth_map"), planes.get("inv_depth_map")
             self.final_T = planes.get("final_T")
+        if self.surface_maps:
+            self.median_depth, self.median_id = planes.get("median_depth"), planes.get("median_id")
         return img
+
+    def pick(self, x: int, y: int) -> int:
+        """The Gaussian under pixel (x, y) of the last frame: the id (index into the Gaussian
+        data) of the pixel's median splat, or -1 where there is no surface (the transmittance
+        stays above 0.5), outside the frame or under a GL shading.  y counts the rows of
+        self.image (strip-local on a strip).  Needs surface_maps=True and a drawn frame; reads
+        one element back (one synchronising 4-byte copy)."""
+        if not self.surface_maps:
+            raise RuntimeError("pick needs HIPRenderer(..., surface_maps=True)")
+        if self.image is None:
+            raise RuntimeError("pick needs a drawn frame (draw() first)")
+        ids = self.median_id
+        x, y = int(x), int(y)
+        if ids is None or not (0 <= y < ids.shape[0] and 0 <= x < ids.shape[1]):
+            return -1
+        return int(ids[y, x].item())
 
     def rgba(self) -> torch.Tensor:
         """renderer_cuda.py:226-228: (3,H,W) -> (H,W,4) with alpha = 1 (one device pack

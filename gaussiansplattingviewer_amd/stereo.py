@@ -14,6 +14,9 @@ FBO readbacks).  Here the same three images come from the HIP rasterizer:
 * `metric_disparity` -- the left view's disparity in pixels, fx |B| / z, from the inverse-depth
   plane of the left image's own blend pass (`gsr_forward_depth`): metric, pixel-aligned with
   the left image, and no third forward (`StereoCapture(disparity="metric")`);
+* `median_disparity` -- fx |B| / z of the pixel's median splat (`gsr_forward_surface`): the
+  disparity of one Gaussian of the pixel's list, never a mix of foreground and background at a
+  silhouette (`StereoCapture(disparity="median")`);
 * `StereoCapture` -- the capture sequence of main.py:843-917 (left pose, disparity with the
   left pose still bound, right pose) on a `HIPRenderer`, returning device tensors; `save`
   writes the PNGs (PIL) the way the viewer names them.
@@ -115,6 +118,21 @@ def metric_disparity(inv_depth_map: torch.Tensor, final_T: torch.Tensor, tanfovx
     return torch.where(cover > 0, d / cover, torch.zeros((), dtype=d.dtype, device=d.device))
 
 
+def median_disparity(median_depth: torch.Tensor, tanfovx: float, width: int,
+                     baseline: float = BASELINE) -> torch.Tensor:
+    """Disparity in pixels, float32 (H, W), of the pixel's median splat: fx |baseline| / z with
+    fx = width / (2 tanfovx) where median_depth > 0, else 0 (no surface: the transmittance never
+    reaches 0.5).  median_depth is the left frame's plane (gsr_forward_surface), the view-space z
+    of one Gaussian per pixel, so every value is the disparity of a Gaussian of the scene: no
+    pixel lies between a foreground and a background surface, as the expected inverse depth
+    (metric_disparity) does along a silhouette.  One float32 division of the float32 product
+    fx |baseline|.  Plain torch ops: device or host tensors."""
+    z = median_depth.to(torch.float32)
+    scale = torch.tensor(float(width) / (2.0 * float(tanfovx)) * abs(float(baseline)),
+                         dtype=torch.float32, device=z.device)
+    return torch.where(z > 0, scale / z, torch.zeros((), dtype=z.dtype, device=z.device))
+
+
 def disparity_u16(disparity: torch.Tensor) -> torch.Tensor:
     """The KITTI disparity PNG's values: uint16 = min(65535, round(256 d)), 0 = no surface;
     returned as int32 (H, W) (torch's uint16 has no rounding ops), cast at the save."""
@@ -128,14 +146,19 @@ class StereoCapture:
     `disparity`: "gl" (default) the GL backend's mode -1 image as "depth", a third forward;
     "metric" the left frame's own inverse-depth plane as "disparity" (metric_disparity, float32
     pixels), two forwards -- the renderer must be a HIPRenderer(depth_maps=True); "both" all
-    four from three forwards."""
+    four from three forwards; "median" the left frame's median-depth plane as "disparity"
+    (median_disparity, float32 pixels), two forwards -- the renderer must be a
+    HIPRenderer(surface_maps=True)."""
 
-    DISPARITIES = ("gl", "metric", "both")
+    DISPARITIES = ("gl", "metric", "both", "median")
 
     def __init__(self, renderer, camera, render_mode: int = 3, disparity: str = "gl"):
         if disparity not in self.DISPARITIES:
             raise ValueError(f"disparity must be one of {self.DISPARITIES}, not {disparity!r}")
-        if disparity != "gl" and not getattr(renderer, "depth_maps", False):
+        if disparity == "median":
+            if not getattr(renderer, "surface_maps", False):
+                raise RuntimeError('disparity="median" needs HIPRenderer(..., surface_maps=True)')
+        elif disparity != "gl" and not getattr(renderer, "depth_maps", False):
             raise RuntimeError(f'disparity="{disparity}" needs HIPRenderer(..., depth_maps=True)')
         self.renderer = renderer
         self.camera = camera
@@ -145,7 +168,8 @@ class StereoCapture:
     def render(self, camera_pose) -> dict:
         """One images.txt entry -> {"left": u8 (H,W,3), "depth": u16 (H,W), "right": u8
         (H,W,3)} device tensors, in the viewer's draw order (main.py:845-900); with
-        disparity="metric" {"left", "right", "disparity": f32 (H,W) pixels}, "both" all four."""
+        disparity="metric" or "median" {"left", "right", "disparity": f32 (H,W) pixels}, "both"
+        all four."""
         r, cam = self.renderer, self.camera
         pose_left, pose_right = load_camera_positions(camera_pose)
         r.update_camera_intrin(cam)                       # main.py:826-827
@@ -153,7 +177,13 @@ class StereoCapture:
         r.sort_and_update(cam, True, pose_left)
         r.update_camera_pose(cam, True, pose_left)
         out = {"left": pack_image(r.draw(), "rgb8")}
-        if self.disparity != "gl":
+        if self.disparity == "median":
+            if r.median_depth is None:
+                raise RuntimeError("the median disparity needs the splat composite (render_mode "
+                                   f"{self.render_mode} is a GL shading)")
+            rs = r.raster_settings
+            out["disparity"] = median_disparity(r.median_depth, rs["tanfovx"], rs["image_width"])
+        elif self.disparity != "gl":
             if r.inv_depth_map is None:
                 raise RuntimeError("the metric disparity needs the splat composite (render_mode "
                                    f"{self.render_mode} is a GL shading)")
@@ -162,8 +192,11 @@ class StereoCapture:
                                                 rs["image_width"])
         # only the left frame needs its planes (they stay in the renderer, the left view's)
         planes, r.depth_maps = r.depth_maps, r.depth_maps and self.disparity == "gl"
+        surface = getattr(r, "surface_maps", False)
+        if self.disparity == "median":
+            r.surface_maps = False
         try:
-            if self.disparity != "metric":
+            if self.disparity not in ("metric", "median"):
                 r.set_render_mod(-1)                       # main.py:867-868: left pose bound
                 out["depth"] = pack_image(r.draw(), "r16")
             r.set_render_mod(self.render_mode)             # main.py:885-889
@@ -172,6 +205,8 @@ class StereoCapture:
             out["right"] = pack_image(r.draw(), "rgb8")
         finally:
             r.depth_maps = planes
+            if self.disparity == "median":
+                r.surface_maps = surface
         return out
 
     @staticmethod

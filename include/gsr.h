@@ -196,6 +196,45 @@ typedef struct {
 int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                       gsr_outputs *out, const gsr_depth_outputs *depth, void *stream);
 
+/* gsr_forward_depth that also fills two optional per-pixel planes of the pixel's MEDIAN splat,
+ * strip-local like final_T ([rows, W]), from the same blend pass as the image and the depth planes.
+ * For a pixel, walk the splats the colour composites, in list order (the power > 0 and
+ * alpha < 1/255 skips, the 0.99 cap and the T < 1e-4 termination are the colour's, in the context's
+ * arithmetic: GSR_OPT_BLEND_FAST 0 or 1, with that mode's own float32 T).  With T_k the
+ * transmittance in front of composited splat k and T_{k+1} = T_k (1 - alpha_k) the one behind it,
+ * the median splat is the first -- the only -- composited splat with T_k > 0.5 and T_{k+1} <= 0.5:
+ * the splat at which half of the light is absorbed.  The terminating splat can never be it
+ * (alpha <= 0.99 and T_{k+1} < 1e-4 force T_k < 0.01).
+ *   median_id[y,x]    = int32, that splat's Gaussian id: the global index into the input tensors,
+ *                       on strips too;
+ *   median_depth[y,x] = float32, that Gaussian's view-space z -- the bits of the `depths` output
+ *                       and of its depth-sort key, as in gsr_forward_depth; no arithmetic.
+ * A pixel whose transmittance never reaches 0.5 (final_T > 0.5, an empty list, everything culled,
+ * P = 0) gets median_id = -1 and median_depth = 0.0f: "no surface", the 0 of a KITTI-style
+ * disparity PNG.  No background term.  Unlike the expected depth of gsr_forward_depth, which at a
+ * silhouette mixes foreground and background into a depth where no surface is, median_depth is
+ * always the depth of one Gaussian of the pixel's list.
+ * Everything else is the same gsr_forward_depth call's, bit for bit: every gsr_outputs member, the
+ * depth planes (`depth` may be NULL), num_rendered and the lists gsr_get_binning exports.  A NULL
+ * `surface`, or one with two NULL members, is gsr_forward_depth itself (the same kernels, the same
+ * arguments); one plane gives the bits it has when both are asked for, and the planes are the same
+ * bits with and without n_contrib and with and without the depth planes.  Strips (radii NULL
+ * included), debug, every option and every context work as in gsr_forward_depth;
+ * GSR_OPT_BLEND_CULL and GSR_OPT_TIGHT_BINNING leave the planes bit-identical (a dropped splat has
+ * alpha_eff = 0: T does not move across it, so it cannot be the median; tight binning stays on for
+ * surface frames).  Frame graphs: the blend is launched directly after the recorded chains with
+ * this call's pointers, so surface, depth and plain frames share their graphs and nothing of a
+ * plane is recorded; a frame whose list outgrew the capacity writes no plane before it is rendered
+ * again.  The kernel is timed as the "blend" stage.  The GL shadings (gsr_forward_shaded) have no
+ * median.  The planes have no gradient.  (Additive to ABI 4.) */
+typedef struct {
+    float *median_depth; /* [rows, W] or NULL */
+    int32_t *median_id;  /* [rows, W] or NULL */
+} gsr_surface_outputs;
+int gsr_forward_surface(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                        gsr_outputs *out, const gsr_depth_outputs *depth,
+                        const gsr_surface_outputs *surface, void *stream);
+
 /* The backward pass of gsr_forward (the splat composite): the gradients of a scalar loss L with
  * respect to the Gaussians, from dL/dcolor.  (Additive to ABI 4.)
  * The function differentiated is the forward exactly as stated above: upstream's preprocess and

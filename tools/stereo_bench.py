@@ -15,9 +15,11 @@ per pixel, uint16 pack 6 B per pixel).
 --disparity metric captures the left view's disparity from its own blend pass instead
 (StereoCapture(disparity="metric"): the inverse-depth plane of gsr_forward_depth, float32 pixels):
 two forwards per pose instead of three, and no disparity-colour or uint16 pack kernel.
+--disparity median does the same from the median-depth plane of gsr_forward_surface
+(StereoCapture(disparity="median")).
 
 Usage: python tools/stereo_bench.py [--P 1000000] [--poses 60] [--warmup 5] [--png]
-                                    [--disparity {gl,metric}]
+                                    [--disparity {gl,metric,median}]
 """
 import argparse
 import json
@@ -89,7 +91,7 @@ def main():
     ap.add_argument("--poses", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--png", action="store_true")
-    ap.add_argument("--disparity", choices=("gl", "metric"), default="gl")
+    ap.add_argument("--disparity", choices=("gl", "metric", "median"), default="gl")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     W, H = colmap.VIEWER_RESOLUTION
@@ -98,8 +100,9 @@ def main():
         poses = colmap.read_images_txt(d)
     g = synthetic_gaussians(a.P, 3, 2)
     cam = Camera(H, W)
-    metric = a.disparity == "metric"
-    r = HIPRenderer(W, H, device=dev, depth_maps=metric)
+    metric = a.disparity != "gl"  # two forwards per pose: the disparity is a plane of the left's
+    r = HIPRenderer(W, H, device=dev, depth_maps=a.disparity == "metric",
+                    surface_maps=a.disparity == "median")
     r.update_gaussian_data(g)
     cap = StereoCapture(r, cam, disparity=a.disparity)
     for i in range(a.warmup):
