@@ -7,10 +7,11 @@
 //
 //   main stream                                    second stream (fork after the preprocess)
 //   1 preprocess        (preprocess.hip)           pair count K + depth-key bits -> pinned host
-//   2 depth sort        (depth_sort.hip)           tile ranges from the rects (column pairs)
-//   3 column counts + scan  (binning.hip)          SH -> RGB colour
+//   2 depth sort        (depth_sort.hip)           SH -> RGB colour
+//   3 column counts + scan  (binning.hip)
 //   4 column scatter    = tile-sort pass 1
-//   5 row pass          = tile-sort pass 2 (radix_sort.hip)
+//   5 row pass          = tile-sort pass 2 (radix_sort.hip); its downsweep also writes the
+//                         tile ranges and the blend's tile-group order
 //   6 join                                          <- join
 //   7 blend             (blend.hip)               gsr_forward_shaded: a GL shading's first-hit kernel
 //                                                  gsr_forward_depth: the depth-accumulating composite
@@ -19,8 +20,7 @@
 // Binning has two forms with identical results: the column-first form above (default), and the
 // per-pair form (offsets scan -> duplicate fused with the first tile-sort pass -> the remaining
 // passes -> tile ranges from the sorted keys) for the frames the column form cannot take: more
-// than 256 tile columns or strip rows, a difference array larger than LDS, or more Gaussians than
-// the packed pair word holds (the choice is automatic; tests reach the per-pair form with images
+// than 256 tile columns or strip rows, or more Gaussians than the packed pair word holds (the choice is automatic; tests reach the per-pair form with images
 // wider than 256 tiles).
 #include <algorithm>
 #include <chrono>
@@ -172,8 +172,10 @@ struct gsr_context {
     // the strip's tile ranges; also as words (the per-pair form's range kernel)
     Buf<uint2> ranges_local{bufs};
     uint32_t *ranges_words() const { return reinterpret_cast<uint32_t *>(ranges_local.get()); }
-    Buf<uint32_t> tile_diff{bufs};    // difference-array partials of the second-stream tile ranges
-    Buf<uint32_t> blend_order{bufs};  // the blend's tile groups, heaviest first (second stream)
+    // column-first binning: the columns' starts in the column-sorted list, from the column
+    // scatter, for the tile ranges the row pass computes (257 words, GsrTileStarts)
+    Buf<uint32_t> col_starts{bufs};
+    Buf<uint32_t> blend_order{bufs};  // the blend's tile groups, heaviest first
     // gsr_backward: the per-Gaussian 2D gradient rows (kGradRow floats each) the blend's backward
     // sums into, and the radii of the per-Gaussian stage it rebuilds
     Buf<float> grad2d{bufs};
@@ -214,7 +216,7 @@ struct gsr_context {
     int64_t timed_frames = 0;
     hipEvent_t ev[kTimingRing][kStages + 1] = {};
     hipEvent_t ev_color[kTimingRing][2] = {};
-    // second stream: pair count, tile ranges and colour, between a fork after the preprocess and
+    // second stream: pair count and colour, between a fork after the preprocess and
     // a join before the blend.  Created on the first forward that uses it; GSR_OPT_SECOND_STREAM
     // 0 runs that work on the frame's stream and destroys it, freeing its hardware queue for
     // another frame in flight.  Normal priority, as the callers' streams: a stream's hardware
@@ -448,19 +450,18 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     f.evc = ctx->ev_color[ctx->timed_frames % kTimingRing];
     f.tmode = ctx->timing == 1 ? 1 : (ctx->timing == 2 && ctx->forwards++ % 8 == 0) ? 2 : 0;
 
-    // column-first binning: the tile ranges come from the rects' difference arrays (in LDS),
-    // the column pass ranks <= 256 columns and the packed word holds the strip row and the id
+    // column-first binning: the column pass ranks <= 256 columns, the row pass is one 8-bit
+    // pass (whose scanned histogram gives the tile ranges) and the packed word holds the strip
+    // row and the id
     const int ybits = f.rows_tiles > 1 ? bits_for(f.rows_tiles - 1) : 0;
     f.col_shift = 32 - ybits;
     f.colpairs = f.gx <= 256 && f.rows_tiles <= 256 &&
-                 gsr_tile_diff_cells(f.gx, f.rows_tiles) <= kTileDiffMaxCells &&
                  (f.col_shift == 32 || (uint64_t)P <= (1ull << f.col_shift));
 
     GSR_TRY(reserve_P(ctx, P, s));
     GSR_TRY(grow(ctx, ctx->ranges_local, (size_t)std::max<uint64_t>(f.T_strip, 1) * 8, s));
     if (f.colpairs) {
-        GSR_TRY(grow(ctx, ctx->tile_diff,
-                     (size_t)kTileDiffBlocks * gsr_tile_diff_cells(f.gx, f.rows_tiles) * 4, s));
+        GSR_TRY(grow(ctx, ctx->col_starts, 257 * 4, s));
         GSR_TRY(grow(ctx, ctx->blend_order,
                      (size_t)gsr_blend_order_groups((uint32_t)f.T_strip) * 4, s));
     }
@@ -603,28 +604,21 @@ int color_waves_of(const Frame &f) {
     return f.rows_tiles < f.gy ? kColorWavesStrip : kColorWavesFull;
 }
 
-// ---- the second stream: K, the tile ranges (column pairs), the colour -----------------------
+// ---- the second stream: K, the colour -----------------------------------------------------
 // The second stream's kernels on stream `as` (a frame graph records them on its capture
 // stream; d_tag then names the device word holding the frame's tag).
-int aux_chain(gsr_context *ctx, const Frame &f, hipStream_t as, const uint32_t *d_tag) {
+constexpr int kAuxPublish = 1, kAuxColor = 2;  // aux_chain's parts
+int aux_chain(gsr_context *ctx, const Frame &f, hipStream_t as, const uint32_t *d_tag,
+              int parts = kAuxPublish | kAuxColor) {
     // K first: k_publish_K sums the preprocess blocks' counts into pinned memory; the host
     // waits for it only after the depth sort and the column counts are queued (MSD frames
     // publish on the main stream instead, with the sort's D)
-    if (!f.main_publish)
-        GSR_HIP(gsr_launch_count_pairs(f.pa, as, nullptr, d_tag), "pair count launch");
-    if (f.tmode == 1) GSR_HIP(hipEventRecord(f.evc[0], as), "hipEventRecord");
-    // the tile ranges before the colour, so the colour overlaps the column count and scatter
-    // rather than the depth sort (C3 two frames in flight 3,470 -> 3,600 frames/s)
-    // (column pairs: the ranges, then the blend's heaviest-first order of the tile groups)
-    if (f.colpairs) {
-        GSR_HIP(gsr_launch_tile_ranges_aux(f.pa.strip_rect, f.pa.strip_rc, f.P, f.gx,
-                                           f.rows_tiles, ctx->tile_diff.get(),
-                                           ctx->ranges_local.get(), as),
-                "tile ranges launch");
-        GSR_HIP(gsr_launch_blend_order(ctx->ranges_local.get(), (uint32_t)f.T_strip,
-                                       ctx->blend_order.get(), as),
-                "blend order launch");
+    if (parts & kAuxPublish) {
+        if (!f.main_publish)
+            GSR_HIP(gsr_launch_count_pairs(f.pa, as, nullptr, d_tag), "pair count launch");
+        if (f.tmode == 1) GSR_HIP(hipEventRecord(f.evc[0], as), "hipEventRecord");
     }
+    if (!(parts & kAuxColor)) return GSR_OK;
     const int color_waves = color_waves_of(f);
     if (f.color_ids) {
         GSR_HIP(hipStreamWaitEvent(as, ctx->compacted, 0), "hipStreamWaitEvent(compacted)");
@@ -638,11 +632,33 @@ int aux_chain(gsr_context *ctx, const Frame &f, hipStream_t as, const uint32_t *
     return GSR_OK;
 }
 
+// The colour of a column-first frame starts on the second stream once the depth sort is done, so
+// that it runs beside the column count, the column scatter and the row pass rather than beside
+// the depth sort, which it slows more (C4 serial: depth sort 226 -> 420 us with the colour beside
+// it; the tile-count pass that used to precede the colour on this stream delayed it as long).
+bool color_after_sort(const gsr_context *ctx, const Frame &f) {
+    return ctx->second_stream && f.colpairs;
+}
+
 int launch_second_stream(gsr_context *ctx, const Frame &f) {
     if (!ctx->second_stream) return aux_chain(ctx, f, f.s, nullptr);  // in order, same stream
     hipStream_t as = ctx->aux;
     GSR_HIP(hipStreamWaitEvent(as, ctx->fork, 0), "hipStreamWaitEvent(fork)");
-    GSR_TRY(aux_chain(ctx, f, as, nullptr));
+    GSR_TRY(aux_chain(ctx, f, as, nullptr,
+                      color_after_sort(ctx, f) ? kAuxPublish : kAuxPublish | kAuxColor));
+    GSR_HIP(hipEventRecord(ctx->join, as), "hipEventRecord(join)");
+    if (f.dbg) GSR_HIP(hipStreamSynchronize(as), "stage color");
+    return GSR_OK;
+}
+
+// ... and the colour behind the depth sort (color_after_sort frames): the fork event is
+// recorded again, after the sort's last pass, for the second stream to wait on.
+int launch_color_after_sort(gsr_context *ctx, const Frame &f) {
+    if (!color_after_sort(ctx, f)) return GSR_OK;
+    hipStream_t as = ctx->aux;
+    GSR_HIP(hipEventRecord(ctx->fork, f.s), "hipEventRecord(sorted)");
+    GSR_HIP(hipStreamWaitEvent(as, ctx->fork, 0), "hipStreamWaitEvent(sorted)");
+    GSR_TRY(aux_chain(ctx, f, as, nullptr, kAuxColor));
     GSR_HIP(hipEventRecord(ctx->join, as), "hipEventRecord(join)");
     if (f.dbg) GSR_HIP(hipStreamSynchronize(as), "stage color");
     return GSR_OK;
@@ -738,21 +754,33 @@ uint32_t id_mask_of(int col_shift) {
 // the packed words' row bits, keys only; on f.s, the list it ends in and its id mask into f.
 // n: the list's length, known to the host, or with list_n (deferred-K frames) the capacity the
 // list is binned into, its length stored to and read from that device word.
+//
+// The tile ranges and the blend's tile-group order come from the row pass itself: its scanned
+// histogram and the column starts the scatter kept give every tile's start, and the leading
+// blocks of its downsweep write them (radix_sort.hip, GsrTileStarts); a one-block kernel behind
+// it orders the tile groups.  A strip of one tile row has no row pass (its tiles are the column
+// runs) and an empty list has all-zero ranges: one small kernel writes those and the order.
 int launch_col_binning(gsr_context *ctx, Frame &f, int64_t n, uint32_t *list_n) {
     uint32_t *tv = ctx->tile_vals.get(), *tv_alt = ctx->tile_vals_alt.get();
+    uint32_t *col_starts = ctx->col_starts.get();
     if (n > 0)
         GSR_HIP(gsr_launch_col_pairs_scatter(ctx->perm.get(), ctx->rect_sorted.get(),
                                              f.tight ? ctx->rc_sorted.get() : nullptr, f.P,
                                              ctx->ds_ctl.get(), ctx->col_hist.get(),
-                                             ctx->digit_total.get(), f.col_shift, tv_alt, f.s,
+                                             ctx->digit_total.get(), f.col_shift, tv_alt,
+                                             col_starts, f.s,
                                              list_n ? (uint32_t)n : 0xFFFFFFFFu, list_n),
                 "column scatter launch");
     std::swap(tv, tv_alt);
     GSR_TRY(stage_end(ctx, f, 3));
+    const GsrTileStarts ts{col_starts, f.gx, f.rows_tiles, ctx->ranges_local.get(),
+                           ctx->blend_order.get()};
     if (n > 0 && f.col_shift < 32)  // (hist: after reserve_K)
         GSR_HIP(gsr_radix_sort_keys(&tv, &tv_alt, n, f.col_shift, 32, ctx->hist.get(),
-                                    ctx->digit_total.get(), f.s, list_n),
+                                    ctx->digit_total.get(), f.s, list_n, &ts),
                 "tile sort launch");
+    else
+        GSR_HIP(gsr_launch_tile_runs(n, list_n, ts, f.s), "tile ranges launch");
     GSR_TRY(stage_end(ctx, f, 4));
     f.point_list = tv;
     f.tiles_local = nullptr;
@@ -884,8 +912,8 @@ int frame_head(gsr_context *ctx, const Frame &f) {
     return stage_end(ctx, f, 0);
 }
 
-// ... and its tail, once the list is binned: ---- 6. join: the blend reads the colours and the
-// second-stream ranges; ---- 7. blend
+// ... and its tail, once the list is binned: ---- 6. join: the blend reads the second stream's
+// colours; ---- 7. blend
 int frame_tail(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st,
                gsr_outputs *out) {
     if (ctx->second_stream)
@@ -898,9 +926,9 @@ int frame_tail(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st,
 // ---- frame graphs (DESIGN.md decision 12) -----------------------------------------------------
 // A small frame is bound by the host: ~17 kernel launches at ~5 us each.  ROCm launches a linear
 // graph as one batch of pre-built packets (a 20-kernel chain in ~6 us), so the frame stream's
-// chain after the preprocess (K publish, depth sort, column counts, column scatter, row pass)
-// and the second stream's chain (tile ranges, blend order, colour) are each recorded once as a
-// linear graph and replayed; the preprocess (the frame's camera and outputs) and the blend (its
+// chain after the preprocess (K publish, depth sort, column counts, column scatter, row pass
+// with the tile ranges and the blend order) and the second stream's chain (K publish of LSD
+// frames, colour) are each recorded once as a linear graph and replayed; the preprocess (the frame's camera and outputs) and the blend (its
 // image) stay direct launches, so 2 launches + 2 graph launches + the fork / join remain.  A
 // graph cannot take per-frame arguments: the preprocess stores the frame's tag and camera
 // position into device words the recorded kernels read, and the binning is sized by a capacity
@@ -1112,6 +1140,8 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
     if (replay) GSR_HIP(hipGraphLaunch(e->sort, s), "hipGraphLaunch(depth sort)");
     else GSR_TRY(chain_sort(ctx, g, s));
     const bool two = ctx->second_stream != 0;  // (else mode 2 on one stream: in order on s)
+    // (the second stream's chain behind the depth sort: color_after_sort; K is read last)
+    if (two) GSR_HIP(hipEventRecord(ctx->fork, s), "hipEventRecord(sorted)");
     if (two) GSR_HIP(hipStreamWaitEvent(ctx->aux, ctx->fork, 0), "hipStreamWaitEvent(fork)");
     if (replay) GSR_HIP(hipGraphLaunch(e->aux, two ? ctx->aux : s), "hipGraphLaunch(aux chain)");
     else GSR_TRY(aux_chain(ctx, g, two ? ctx->aux : s, fw));
@@ -1218,6 +1248,7 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
             depth_passes = gsr_depth_sort_passes((uint32_t)dv);
         GSR_TRY(launch_depth_sort(ctx, f, 1, depth_passes));
     }
+    GSR_TRY(launch_color_after_sort(ctx, f));
     GSR_TRY(stage_end(ctx, f, 1));
 
     // ---- 3. scan

@@ -9,8 +9,6 @@
 // by Gaussian index, exactly as upstream's stable 64-bit sort orders it, so point lists and
 // ranges are bit-identical while the K-sized sort moves 8-B pairs over 2 passes instead of
 // 12-B pairs over 6.
-#include <atomic>
-
 #include "radix_tile.h"
 
 using namespace gsr;
@@ -516,6 +514,7 @@ __global__ __launch_bounds__(kCG) void k_col_scatter(const uint32_t *__restrict_
                                                      const uint32_t *__restrict__ off,
                                                      const uint32_t *__restrict__ digit_total,
                                                      int pack_shift, uint32_t *__restrict__ out,
+                                                     uint32_t *__restrict__ col_starts,
                                                      uint32_t cap, uint32_t *__restrict__ list_n) {
     __shared__ ColScatterSmem c;
     __shared__ union {
@@ -529,6 +528,12 @@ __global__ __launch_bounds__(kCG) void k_col_scatter(const uint32_t *__restrict_
     uint32_t tot;
     const uint32_t dstart = block256_exclusive_scan(digit_total[tid], c.tmp, tot);
     if (list_n && blk == 0 && tid == 0) *list_n = tot;  // (frame graphs: the row pass)
+    // the columns' starts and the list length, for the tile ranges (the row pass's scan
+    // overwrites digit_total)
+    if (blk == 0) {
+        col_starts[tid] = dstart;
+        if (tid == 0) col_starts[kRadixBins] = tot;
+    }
     if (tot > cap) return;  // (frame graphs) the list does not fit: the host re-renders
     const int64_t n = *d_n;
     const int64_t base = (int64_t)blk * kCG;
@@ -689,197 +694,6 @@ hipError_t gsr_launch_dup_sort_pass(const uint4 *bin, const uint32_t *chunk_firs
     return hipGetLastError();
 }
 
-namespace {
-
-// ---- tile ranges from per-tile pair counts (second stream) ---------------------------------
-// The sorted pair list holds each tile's pairs contiguously in tile order, so ranges[t] =
-// [start_t, start_t + count_t) with start_t the exclusive scan of the per-tile pair counts --
-// which depend only on the Gaussians' tile rects, not on any sort.  They are computed on the
-// second stream while the main stream sorts, in two kernels:
-//   k_tile_diff     -- per block of Gaussians, in LDS: for every tile column of a rect (or of
-//                      its tight spans), a difference array down the rows (+1 at the first row,
-//                      -1 past the last: two LDS atomics per column), then per column the prefix
-//                      down the rows = the block's per-tile counts, and the rows' totals; the
-//                      block's counts and totals go to `partial` (kTileDiffBlocks of them);
-//   k_tile_finalize -- one block per tile row: sums the partials' counts of its row; the row's
-//                      first offset = the sum of the row totals above; then an exclusive scan
-//                      along the row.
-// Tiles without pairs get (0, 0), as upstream's memset leaves them.  Replaces k_ranges, a pass
-// over the K sorted keys on the main stream (the packed pair list has no tile keys to scan).
-constexpr int kDiffThreads = 1024;
-
-// kTight: the {rect, span word} records, column-major differences (two atomics per kept column,
-// then a prefix down each column); else the rects, row-major differences (two atomics per rect
-// row -- a strip clips the rows but not the columns -- then a prefix along each row).
-template <bool kTight>
-__global__ __launch_bounds__(kDiffThreads) void k_tile_diff(const uint2 *__restrict__ strip_rect,
-                                                            const uint4 *__restrict__ strip_rc,
-                                                            int64_t P, uint32_t gx, uint32_t rows,
-                                                            uint32_t *__restrict__ partial) {
-    extern __shared__ uint32_t s_diff[];
-    const uint32_t w1 = gx + 1, cells = gsr_tile_diff_cells(gx, rows);
-    uint32_t *s_rows = s_diff + w1 * (rows + 1);  // the rows' pair totals
-    for (uint32_t c = threadIdx.x; c < cells; c += kDiffThreads) s_diff[c] = 0u;
-    __syncthreads();
-    const int64_t b0 = P * blockIdx.x / gridDim.x, b1 = P * (blockIdx.x + 1) / gridDim.x;
-    // 4 rects per thread and step, their loads issued together
-    constexpr int kU = 4;
-    for (int64_t i = b0 + threadIdx.x; i < b1; i += kU * kDiffThreads) {
-        uint2 r[kU], q[kU];
-#pragma unroll
-        for (int k = 0; k < kU; ++k) {
-            const int64_t j = i + (int64_t)k * kDiffThreads;
-            r[k] = q[k] = make_uint2(0u, 0u);
-            if (j < b1 && kTight) {  // the rect and its span word, one load
-                const uint4 rq = strip_rc[j];
-                r[k] = make_uint2(rq.x, rq.y);
-                q[k] = make_uint2(rq.z, rq.w);
-            } else if (j < b1) {
-                r[k] = strip_rect[j];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kU; ++k) {
-            if (r[k].x == 0u) continue;  // no pairs in the strip (a rect with pairs has width > 0)
-            const uint32_t x0 = r[k].x & 0xFFFFu, w = r[k].x >> 16, y0 = r[k].y & 0xFFFFu;
-            if (!kTight) {
-                for (uint32_t y = y0; y < y0 + (r[k].y >> 16); ++y) {
-                    atomicAdd(&s_diff[y * w1 + x0], 1u);
-                    atomicAdd(&s_diff[y * w1 + x0 + w], 0xFFFFFFFFu);  // -1 (mod 2^32)
-                }
-                continue;
-            }
-            const bool coded = span_coded(r[k]);
-            // column x0 + c holds rows [y0 + lo, y0 + lo + cnt): +1 / -1 down the column
-            for (uint32_t c = 0; c < w; ++c) {
-                uint32_t lo = 0u, cnt = r[k].y >> 16;
-                if (coded) col_span(r[k], q[k], c, lo, cnt);
-                if (cnt) {
-                    atomicAdd(&s_diff[(y0 + lo) * w1 + x0 + c], 1u);
-                    atomicAdd(&s_diff[(y0 + lo + cnt) * w1 + x0 + c], 0xFFFFFFFFu);  // -1
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    if (kTight) {
-        // per column, the prefix down the rows: each tile's pair count (in place)
-        for (uint32_t x = threadIdx.x; x < gx; x += kDiffThreads) {
-            uint32_t run = 0u;
-            for (uint32_t y = 0; y < rows; ++y) {
-                run += s_diff[y * w1 + x];
-                s_diff[y * w1 + x] = run;
-            }
-        }
-    } else {
-        // per row (a wave each), the prefix along the row
-        for (uint32_t y = wv; y < rows; y += kDiffThreads / 64) {
-            uint32_t carry = 0u;
-            for (uint32_t x0 = 0; x0 < gx; x0 += 64) {
-                const uint32_t x = x0 + ln;
-                const uint32_t v = x < gx ? s_diff[y * w1 + x] : 0u;
-                const uint32_t inc = wave_inclusive_scan(v) + carry;
-                if (x < gx) s_diff[y * w1 + x] = inc;
-                carry = __shfl(inc, 63);
-            }
-        }
-    }
-    __syncthreads();
-    // the rows' totals
-    for (uint32_t y = wv; y < rows; y += kDiffThreads / 64) {
-        uint32_t acc = 0u;
-        for (uint32_t x = ln; x < gx; x += 64) acc += s_diff[y * w1 + x];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        if (ln == 0) s_rows[y] = acc;
-    }
-    __syncthreads();
-    uint32_t *dst = partial + (int64_t)blockIdx.x * cells;
-    for (uint32_t c = threadIdx.x; c < cells; c += kDiffThreads) dst[c] = s_diff[c];
-}
-
-// Inclusive scan over the block (kW waves); s_tmp: kW words.  Returns the prefix, total out.
-template <int kW>
-__device__ __forceinline__ uint32_t blockw_inclusive_scan(uint32_t v, uint32_t *s_tmp,
-                                                          uint32_t &total) {
-    return blockw_exclusive_scan<kW>(v, s_tmp, total) + v;
-}
-
-constexpr int kFinThreads = 256;
-__global__ __launch_bounds__(kFinThreads) void k_tile_finalize(const uint32_t *__restrict__ partial,
-                                                               int nparts, uint32_t gx,
-                                                               uint32_t rows,
-                                                               uint2 *__restrict__ ranges) {
-    constexpr int kW = kFinThreads / 64;
-    __shared__ uint32_t s_tmp[kW];
-    const uint32_t y = blockIdx.x, w1 = gx + 1, cells = gsr_tile_diff_cells(gx, rows);
-    const int tid = threadIdx.x;
-    // offset of this row: the sum of the row totals above it
-    uint32_t before = 0;
-    for (uint32_t y0 = 0; y0 < y; y0 += kFinThreads) {
-        const uint32_t yy = y0 + tid;
-        uint32_t rt = 0;
-        if (yy < y)
-#pragma unroll 8
-            for (int b = 0; b < nparts; ++b) rt += partial[(int64_t)b * cells + w1 * (rows + 1) + yy];
-        uint32_t t;
-        blockw_inclusive_scan<kW>(rt, s_tmp, t);
-        before += t;
-    }
-    // this row's counts (the partials' sum), then an exclusive scan along the row
-    uint32_t start = before;
-    for (uint32_t x0 = 0; x0 < gx; x0 += kFinThreads) {
-        const uint32_t x = x0 + tid;
-        uint32_t cnt = 0;
-        if (x < gx)
-#pragma unroll 8
-            for (int b = 0; b < nparts; ++b) cnt += partial[(int64_t)b * cells + y * w1 + x];
-        uint32_t t2;
-        const uint32_t ex = blockw_exclusive_scan<kW>(x < gx ? cnt : 0u, s_tmp, t2) + start;
-        start += t2;
-        if (x < gx) ranges[y * gx + x] = cnt ? make_uint2(ex, ex + cnt) : make_uint2(0u, 0u);
-    }
-}
-
-}  // namespace
-
-hipError_t gsr_launch_tile_ranges_aux(const uint2 *strip_rect, const uint4 *strip_rc, int64_t P,
-                                      uint32_t gx, uint32_t rows, uint32_t *partial, uint2 *ranges,
-                                      hipStream_t s) {
-    const uint32_t cells = gsr_tile_diff_cells(gx, rows);
-    const size_t lds = (size_t)cells * 4;
-    if (cells > kTileDiffMaxCells) return hipErrorInvalidValue;
-    // the > 64 KiB dynamic-LDS attribute is per (function, device): one bit per device, set
-    // atomically (setting it twice from racing threads is harmless)
-    static std::atomic<uint64_t> attr_done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = dev < 64 ? (1ull << dev) : 0ull;
-    if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
-        for (const void *fn : {reinterpret_cast<const void *>(&k_tile_diff<true>),
-                               reinterpret_cast<const void *>(&k_tile_diff<false>)}) {
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kTileDiffMaxCells * 4);
-            if (e != hipSuccess) return e;
-        }
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    // one block per 16k rects (at least 64, at most kTileDiffBlocks): the rect pass stays
-    // short at 6M Gaussians while the finalize's sum over the partials stays small at 1M
-    const int nparts = (int)std::min<int64_t>(kTileDiffBlocks, std::max<int64_t>(64, (P + 16383) / 16384));
-    if (strip_rc)
-        hipLaunchKernelGGL(k_tile_diff<true>, dim3(nparts), dim3(kDiffThreads), lds, s, strip_rect,
-                           strip_rc, P, gx, rows, partial);
-    else
-        hipLaunchKernelGGL(k_tile_diff<false>, dim3(nparts), dim3(kDiffThreads), lds, s,
-                           strip_rect, strip_rc, P, gx, rows, partial);
-    hipLaunchKernelGGL(k_tile_finalize, dim3(rows), dim3(kFinThreads), 0, s, partial,
-                       nparts, gx, rows, ranges);
-    return hipGetLastError();
-}
-
 hipError_t gsr_launch_ranges(const uint32_t *tile_keys, int64_t K, uint32_t *ranges,
                              hipStream_t s) {
     if (K == 0) return hipSuccess;
@@ -944,12 +758,13 @@ hipError_t gsr_launch_col_pairs_scatter(const uint32_t *perm, const uint2 *rect_
                                         const uint4 *rc_sorted, int64_t n_max,
                                         const uint32_t *d_n, const uint32_t *hist,
                                         const uint32_t *digit_total, int pack_shift, uint32_t *out,
-                                        hipStream_t s, uint32_t cap, uint32_t *list_n) {
+                                        uint32_t *col_starts, hipStream_t s, uint32_t cap,
+                                        uint32_t *list_n) {
     const int64_t nb = (n_max + kCG - 1) / kCG, ng = (nb + kCGroup - 1) / kCGroup;
     if (nb == 0) return hipSuccess;
     const uint32_t *off = hist + ng * kRadixBins;
     const dim3 grid(xcd_run_grid(nb));
     hipLaunchKernelGGL(k_col_scatter, grid, dim3(kCG), 0, s, perm, rect_sorted, rc_sorted, d_n,
-                       hist, ng, off, digit_total, pack_shift, out, cap, list_n);
+                       hist, ng, off, digit_total, pack_shift, out, col_starts, cap, list_n);
     return hipGetLastError();
 }

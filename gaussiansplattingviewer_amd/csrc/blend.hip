@@ -24,7 +24,7 @@
 // image tolerance of tests/gpu_helpers.py.
 #include <type_traits>
 
-#include "gsr_internal.h"
+#include "blend_order.h"
 
 using namespace gsr;
 
@@ -33,71 +33,15 @@ namespace {
 // Block -> tile, XCD-aware: the hardware deals block b to XCD b % 8 (speed only, never
 // correctness); groups of kGroupTiles consecutive tiles (four row-adjacent tiles, 16 quadrant
 // waves) go round-robin over the XCDs, so each group shares one L2 while the image's heavy and
-// light regions are spread evenly over the 8 XCDs.  With `order` (k_blend_order) the groups are
+// light regions are spread evenly over the 8 XCDs.  With `order` (blend_order.h) the groups are
 // dealt heaviest first: every wave of the last round is then a short one, and the kernel's
 // tail -- the last waves finishing on an emptying chip -- shrinks.
-constexpr uint32_t kGroupTiles = 4;
 __device__ __forceinline__ uint32_t xcd_tile(uint32_t b, const uint32_t *order,
                                              uint32_t n_groups) {
     const uint32_t x = b & 7u, l = b >> 3;
     uint32_t g = (l / kGroupTiles) * 8u + x;
     if (order && g < n_groups) g = order[g];
     return g * kGroupTiles + l % kGroupTiles;
-}
-
-// Counting sort of the tile groups by a log-scale pair count, descending (one block; order
-// within a bucket is arbitrary and does not matter: each wave's output depends only on its own
-// quadrant).  Key: 32 steps per octave of (pairs + 1), 1024 buckets.
-constexpr int kOrderBuckets = 1024;
-__device__ __forceinline__ uint32_t order_key(const uint2 *ranges, uint32_t g, uint32_t n_tiles) {
-    uint32_t n = 0;
-    const uint32_t t0 = g * kGroupTiles;
-#pragma unroll
-    for (uint32_t i = 0; i < kGroupTiles; ++i)
-        if (t0 + i < n_tiles) {
-            const uint2 r = ranges[t0 + i];
-            n += r.y - r.x;
-        }
-    const int k = (int)(__builtin_amdgcn_logf((float)n + 1.0f) * 32.0f);
-    return (uint32_t)(kOrderBuckets - 1 - min(k, kOrderBuckets - 1));
-}
-
-constexpr int kOrderThreads = 1024;  // one block; kOrderBuckets / it per thread
-constexpr int kOrderPer = kOrderBuckets / kOrderThreads;
-__global__ __launch_bounds__(kOrderThreads) void k_blend_order(const uint2 *__restrict__ ranges,
-                                                               uint32_t n_tiles, uint32_t n_groups,
-                                                               uint32_t *__restrict__ order) {
-    __shared__ uint32_t s_h[kOrderBuckets];
-    __shared__ uint32_t s_w[kOrderThreads / 64];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < kOrderBuckets; i += kOrderThreads) s_h[i] = 0u;
-    __syncthreads();
-    for (uint32_t g = tid; g < n_groups; g += kOrderThreads)
-        atomicAdd(&s_h[order_key(ranges, g, n_tiles)], 1u);
-    __syncthreads();
-    // exclusive scan of the 1024 bucket counts, kOrderPer consecutive buckets per thread
-    uint32_t c[kOrderPer], sum = 0;
-#pragma unroll
-    for (int i = 0; i < kOrderPer; ++i) sum += (c[i] = s_h[tid * kOrderPer + i]);
-    uint32_t x = sum;
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    uint32_t base = x - sum;
-    for (int i = 0; i < w; ++i) base += s_w[i];
-#pragma unroll
-    for (int i = 0; i < kOrderPer; ++i) {
-        s_h[tid * kOrderPer + i] = base;
-        base += c[i];
-    }
-    __syncthreads();
-    for (uint32_t g = tid; g < n_groups; g += kOrderThreads)
-        order[atomicAdd(&s_h[order_key(ranges, g, n_tiles)], 1u)] = g;
 }
 
 // One staged splat as the inner loop reads it: three 16-B LDS reads from one address (fast
@@ -583,14 +527,6 @@ hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s) {
 
 uint32_t gsr_blend_order_groups(uint32_t n_tiles) {
     return (n_tiles + kGroupTiles - 1) / kGroupTiles;
-}
-
-hipError_t gsr_launch_blend_order(const uint2 *ranges, uint32_t n_tiles, uint32_t *order,
-                                  hipStream_t s) {
-    if (n_tiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_blend_order, dim3(1), dim3(kOrderThreads), 0, s, ranges, n_tiles,
-                       gsr_blend_order_groups(n_tiles), order);
-    return hipGetLastError();
 }
 
 hipError_t gsr_launch_blend(const GsrBlendArgs &a, hipStream_t s) {

@@ -408,9 +408,23 @@ hipError_t gsr_radix_sort_pairs(uint32_t **keys, uint32_t **vals, uint32_t **key
 // d_n (frame graphs): the element count is *d_n, read on the device; n is then the capacity
 // the grids, the buffers and hist are sized for, and a count above it sorts nothing (the host
 // re-renders such a frame, api.hip).
+// tile_starts (optional; single-pass sorts only, the column-first binning's row pass): the
+// downsweep also writes the strip's tile ranges, from the scanned histogram it ranks by, and a
+// one-block kernel behind it the blend's tile-group order (radix_sort.hip).
+// ranges[r * gx + c] = {start, end} of strip tile (r, c) in the sorted list, (0, 0) for a tile
+// without entries; order: gsr_blend_order_groups(gx * rows) words.  col_starts: the columns'
+// starts in the column-sorted input and its length (257 words,
+// gsr_launch_col_pairs_scatter).  gx = 0: none.
+struct GsrTileStarts {
+    const uint32_t *col_starts;
+    uint32_t gx, rows;
+    uint2 *ranges;
+    uint32_t *order;
+};
 hipError_t gsr_radix_sort_keys(uint32_t **keys, uint32_t **keys_alt, int64_t n, int begin_bit,
                                int end_bit, uint32_t *hist, uint32_t *digit_total, hipStream_t s,
-                               const uint32_t *d_n = nullptr);
+                               const uint32_t *d_n = nullptr,
+                               const GsrTileStarts *tile_starts = nullptr);
 // k_rs_scan alone: per digit, exclusive scan of hist[d][0..nb) across tiles -> digit_total[d].
 hipError_t gsr_launch_digit_scan(uint32_t *hist, int64_t nb, uint32_t *digit_total,
                                  hipStream_t s);
@@ -509,11 +523,14 @@ hipError_t gsr_launch_col_pairs_count(const uint32_t *perm, const uint2 *strip_r
                                       uint32_t *digit_total, hipStream_t s);
 // list_n (frame graphs, else NULL): the list length (the column totals' sum) is stored there
 // for the row pass; a list longer than cap is not written (the host re-renders the frame).
+// col_starts (257 words): the columns' starts in the list and its length, kept for the tile
+// ranges (GsrTileStarts; the row pass overwrites digit_total).
 hipError_t gsr_launch_col_pairs_scatter(const uint32_t *perm, const uint2 *rect_sorted,
                                         const uint4 *rc_sorted, int64_t n_max,
                                         const uint32_t *d_n, const uint32_t *hist,
                                         const uint32_t *digit_total, int pack_shift, uint32_t *out,
-                                        hipStream_t s, uint32_t cap = 0xFFFFFFFFu,
+                                        uint32_t *col_starts, hipStream_t s,
+                                        uint32_t cap = 0xFFFFFFFFu,
                                         uint32_t *list_n = nullptr);
 hipError_t gsr_launch_digit_scan_n(uint32_t *hist, int64_t nb, uint32_t *digit_total,
                                    const uint32_t *d_n, int64_t tile, hipStream_t s);
@@ -525,21 +542,11 @@ hipError_t gsr_launch_fill_tiles(const uint2 *ranges, uint32_t n_tiles, uint32_t
                                  uint32_t *out, hipStream_t s);
 hipError_t gsr_launch_ranges(const uint32_t *tile_keys, int64_t K, uint32_t *ranges,
                              hipStream_t s);
-// Tile ranges from the Gaussians' strip tile rects alone (no sorted keys): per-tile pair
-// counts via per-row difference arrays, then an exclusive scan; runs on the second stream.
-// partial: kTileDiffBlocks * cells words (capacity), cells = gsr_tile_diff_cells(...) <= kTileDiffMaxCells
-// (the difference arrays live in LDS).
-constexpr int kTileDiffBlocks = 256;  // at most; 64 up to 1M Gaussians, more for more
-constexpr uint32_t kTileDiffMaxCells = 38912;  // 152 KiB of LDS
-// (gx + 1) cells per tile row for rows + 1 rows (the column differences, then the per-tile
-// counts), then the rows' pair totals
-__host__ __device__ inline uint32_t gsr_tile_diff_cells(uint32_t gx, uint32_t rows) {
-    return (gx + 1) * (rows + 1) + rows;
-}
-hipError_t gsr_launch_tile_ranges_aux(const uint2 *strip_rect, const uint4 *strip_rc, int64_t P,
-                                      uint32_t gx,
-                                      uint32_t rows, uint32_t *partial, uint2 *ranges,
-                                      hipStream_t s);
+// A list without a row pass -- a strip of one tile row (its tiles are the column runs), or an
+// empty list (n = 0, d_n NULL: every range (0, 0)) -- gets its ranges and the order from one
+// small kernel instead.  n / d_n as in gsr_radix_sort_keys.
+hipError_t gsr_launch_tile_runs(int64_t n, const uint32_t *d_n, const GsrTileStarts &ts,
+                                hipStream_t s);
 // Pair count per tile row of a strip's ranges (gsr_tile_row_pairs).
 hipError_t gsr_launch_row_pairs(const uint2 *ranges, uint32_t gx, uint32_t rows, uint32_t *out,
                                 hipStream_t s);
@@ -559,7 +566,7 @@ struct GsrBlendArgs {
     int cull;            // 0: no quadrant cull (identical output, tested)
     int fast;            // 1: folded-constant FMA arithmetic + raw v_exp_f32; 0: upstream order
     uint32_t id_mask;    // point_list word -> Gaussian id (packed pair lists; else ~0u)
-    const uint32_t *order;  // tile groups heaviest first (gsr_launch_blend_order), or nullptr
+    const uint32_t *order;  // tile groups heaviest first (GsrTileStarts.order), or nullptr
     // frame graphs: the list length on the device (k_col_scatter) and the capacity the list was
     // binned into; a longer list was not binned, so the blend writes nothing (the host
     // re-renders the frame).  NULL: the host sized the list.
@@ -591,9 +598,8 @@ hipError_t gsr_launch_blend_surface(const GsrBlendArgs &a, const GsrDepthArgs &d
 hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);
 // The blend's dispatch order: the groups of 4 row-adjacent tiles (16 quadrant waves, one XCD)
 // by descending pair count, so the last waves to start are the short ones.
+// (computed with the tile ranges: GsrTileStarts, blend_order.h)
 uint32_t gsr_blend_order_groups(uint32_t n_tiles);
-hipError_t gsr_launch_blend_order(const uint2 *ranges, uint32_t n_tiles, uint32_t *order,
-                                  hipStream_t s);
 
 // ---- the backward pass (backward.hip; gsr_backward in api.hip) ---------------------------------
 // The per-Gaussian 2D gradients the blend's backward sums and the per-Gaussian backward reads: one

@@ -16,6 +16,7 @@
 // concatenated in order, so each pass -- and the sort -- is stable.
 #include <algorithm>
 
+#include "blend_order.h"
 #include "radix_tile.h"
 
 using namespace gsr;
@@ -141,6 +142,95 @@ __global__ __launch_bounds__(kBlock) void k_rs_scan(uint32_t *__restrict__ hist,
     if (threadIdx.x == 0) digit_total[blockIdx.x] = carry;
 }
 
+// ---- tile ranges from the row pass (column-first binning) ------------------------------------
+// The final list is sorted by (tile row, tile column) and the row pass is stable, so tile (r, c)
+// holds the row-r words of column c's run [B_c, B_c+1) of the column-sorted list, and starts at
+//   rowbase[r] + (row-r words of list[0, B_c)),
+// rowbase the exclusive scan of the row totals.  After k_rs_scan, hist[r][t] is the number of
+// row-r words in the sort tiles before tile t, so only the words between the base of the sort
+// tile that holds B_c and B_c itself (< kT of them) are counted here.  One block per tile column
+// counts up to both of its boundaries: thread r forms {start, end} of tile (r, c) and writes
+// (0, 0) for a tile without entries, as upstream's memset leaves it.  The blocks are the first of
+// the row pass's downsweep grid (k_rs_downsweep), which reads the same scanned histogram: they
+// cost no launch and run beside the sort's tiles.  The tile groups' order for the blend
+// (blend_order.h) needs every column's ranges: k_blend_order, one block, follows the pass.  (The
+// last column block to finish could compute it, behind device-scope fences: that saved the
+// launch on a frame that runs alone, C3 serial 0.309 -> 0.305 ms, but its L2 write-backs under
+// other frames' blends cost four frames in flight 2 %, and a small frame's pass waited for that
+// one block, C2 tile sort 15 -> 27 us.)
+
+// Thread r < 256: the row-r words of list[0, B).  B >= n (the list's end): the row's total.
+// (block-uniform branches; s_h, kW x 256 words, is free again on return)
+template <int kW>
+__device__ __forceinline__ uint32_t rows_before(const uint32_t *__restrict__ list, uint32_t B,
+                                                int64_t n, int shift, uint32_t mask,
+                                                const uint32_t *__restrict__ hist, int64_t stride,
+                                                int64_t kT, uint32_t row_total, uint32_t *s_h) {
+    if ((int64_t)B >= n) return row_total;
+    constexpr int kThreads = kW * 64;
+    const int tid = threadIdx.x, w = tid >> 6;
+    const int64_t t = (int64_t)B / kT, base = t * kT;
+    for (int i = tid; i < kW * kRadix; i += kThreads) s_h[i] = 0u;
+    __syncthreads();
+    for (int64_t e = base + tid; e < (int64_t)B; e += kThreads)
+        atomicAdd(&s_h[w * kRadix + ((list[e] >> shift) & mask)], 1u);
+    __syncthreads();
+    uint32_t c = 0u;
+    if (tid < kRadix) {
+        c = hist[(int64_t)tid * stride + t];
+#pragma unroll
+        for (int i = 0; i < kW; ++i) c += s_h[i * kRadix + tid];
+    }
+    __syncthreads();
+    return c;
+}
+
+// LDS words tile_starts_block needs: the per-wave histograms and the scan's words.
+template <int kW>
+constexpr int tile_starts_smem() { return kW * kRadix + kW; }
+
+// Column c of the ranges (every thread of the block calls it; n: the list's live length).
+template <int kW>
+__device__ __forceinline__ void tile_starts_block(uint32_t c, const uint32_t *__restrict__ list,
+                                                  int64_t n, int shift,
+                                                  const uint32_t *__restrict__ hist, int64_t stride,
+                                                  int64_t kT,
+                                                  const uint32_t *__restrict__ digit_total,
+                                                  const GsrTileStarts &ts, uint32_t *s_mem) {
+    uint32_t *s_h = s_mem, *s_tmp = s_h + kW * kRadix;
+    const uint32_t r = threadIdx.x;
+    const uint32_t mask = (1u << (32 - shift)) - 1u;
+    const uint32_t B0 = ts.col_starts[c], B1 = ts.col_starts[c + 1];
+    // (an over-capacity list has n = 0: nothing was sorted and the frame is rendered again)
+    const bool empty = n <= 0 || B0 >= B1 || (int64_t)B1 > n;
+    uint2 out = make_uint2(0u, 0u);
+    if (!empty) {
+        const uint32_t row_total = r < (uint32_t)kRadix ? digit_total[r] : 0u;
+        uint32_t all;
+        const uint32_t rowbase = blockw_exclusive_scan<kW>(row_total, s_tmp, all);
+        const uint32_t s0 =
+            rows_before<kW>(list, B0, n, shift, mask, hist, stride, kT, row_total, s_h);
+        const uint32_t s1 =
+            rows_before<kW>(list, B1, n, shift, mask, hist, stride, kT, row_total, s_h);
+        if (s1 > s0) out = make_uint2(rowbase + s0, rowbase + s1);
+    }
+    if (r < ts.rows) ts.ranges[(size_t)r * ts.gx + c] = out;
+}
+
+// The tile groups' order, a launch of its own after the pass (one block).
+constexpr int kOrderThreads = 1024;
+__global__ __launch_bounds__(kOrderThreads) void k_blend_order(const GsrTileStarts ts) {
+    __shared__ uint32_t s_h[kOrderBuckets];
+    __shared__ uint32_t s_w[kOrderThreads / 64];
+    const uint32_t n_tiles = ts.gx * ts.rows;
+    blend_order_block<kOrderThreads>(ts.ranges, n_tiles, (n_tiles + kGroupTiles - 1) / kGroupTiles,
+                                     ts.order, s_h, s_w);
+}
+
+// The downsweep's leading blocks that compute the tile ranges: the columns rounded up to whole
+// rounds of the 8 XCDs, so the sort tiles' XCD mapping (xcd_run_block) stays what it is.
+__host__ __device__ inline uint32_t tile_start_blocks(uint32_t gx) { return (gx + 7u) & ~7u; }
+
 // kVals = false: keys only (vals_in / vals_out unused) -- no LDS for values, so more blocks
 // share a CU.
 template <int kW, int kIt, bool kVals>
@@ -148,14 +238,26 @@ __global__ __launch_bounds__(kW * 64) void k_rs_downsweep(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, int64_t n_cap,
     int shift, int nbits, const uint32_t *__restrict__ hist,
-    const uint32_t *__restrict__ digit_total, int64_t nb, const uint32_t *__restrict__ d_n) {
+    const uint32_t *__restrict__ digit_total, int64_t nb, const uint32_t *__restrict__ d_n,
+    const GsrTileStarts ts) {
     constexpr int kT = kW * 64 * kIt;
+    static_assert(kT >= tile_starts_smem<kW>(), "the tile-range blocks work in s_keys");
     const int64_t n = live_count(d_n, n_cap);
     __shared__ uint32_t s_keys[kT];
     __shared__ uint32_t s_vals[kVals ? kT : 1];
     __shared__ RadixTileSmem<kW, kIt> sm;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t tile = xcd_run_block(blockIdx.x);
+    uint32_t b = blockIdx.x;
+    if (ts.gx) {  // (ts.gx = 0: a plain sort pass)
+        const uint32_t lead = tile_start_blocks(ts.gx);
+        if (b < lead) {
+            if (b < ts.gx)
+                tile_starts_block<kW>(b, keys_in, n, shift, hist, nb, kT, digit_total, ts, s_keys);
+            return;
+        }
+        b -= lead;
+    }
+    const uint32_t tile = xcd_run_block(b);
     const int64_t base = (int64_t)tile * kT;
     if (base >= n) return;  // whole block
     uint32_t k[kIt], v[kIt];
@@ -226,7 +328,7 @@ int64_t gsr_radix_hist_words(int64_t n) {
 // (n the capacity; live_count).
 static void rts_pass(const uint32_t *k, const uint32_t *v, uint32_t *ko, uint32_t *vo, int64_t n,
                      int shift, int nbits, uint32_t *hist, uint32_t *digit_total, hipStream_t s,
-                     const uint32_t *d_n = nullptr) {
+                     const uint32_t *d_n = nullptr, const GsrTileStarts *tile_starts = nullptr) {
     const int64_t nb = (n + kST - 1) / kST;  // tiles: the downsweep's grid
     if (nb == 0) return;
     const int64_t stride = hist_stride(nb);
@@ -242,13 +344,17 @@ static void rts_pass(const uint32_t *k, const uint32_t *v, uint32_t *ko, uint32_
     // sorts nothing)
     hipLaunchKernelGGL(k_rs_scan, dim3(kRadix), dim3(kBlock), 0, s, hist, stride, digit_total,
                        RsCount{nb, d_n}, kST);
-    const dim3 down_grid(xcd_run_grid(nb));
+    // (the tile-range blocks lead the grid: they are dealt first and finish beside the tiles)
+    const GsrTileStarts ts = tile_starts ? *tile_starts : GsrTileStarts{};
+    const dim3 down_grid(xcd_run_grid(nb) + (ts.gx ? tile_start_blocks(ts.gx) : 0u));
     if (v)
         hipLaunchKernelGGL((k_rs_downsweep<kSW, kSIt, true>), down_grid, dim3(kSW * 64), 0, s, k,
-                           v, ko, vo, n, shift, nbits, hist, digit_total, stride, d_n);
+                           v, ko, vo, n, shift, nbits, hist, digit_total, stride, d_n, ts);
     else
         hipLaunchKernelGGL((k_rs_downsweep<kSW, kSIt, false>), down_grid, dim3(kSW * 64), 0, s,
-                           k, v, ko, vo, n, shift, nbits, hist, digit_total, stride, d_n);
+                           k, v, ko, vo, n, shift, nbits, hist, digit_total, stride, d_n, ts);
+    if (ts.gx)
+        hipLaunchKernelGGL(k_blend_order, dim3(1), dim3(kOrderThreads), 0, s, ts);
 }
 
 hipError_t gsr_radix_sort_pairs(uint32_t **keys, uint32_t **vals, uint32_t **keys_alt,
@@ -268,13 +374,53 @@ hipError_t gsr_radix_sort_pairs(uint32_t **keys, uint32_t **vals, uint32_t **key
 
 hipError_t gsr_radix_sort_keys(uint32_t **keys, uint32_t **keys_alt, int64_t n, int begin_bit,
                                int end_bit, uint32_t *hist, uint32_t *digit_total, hipStream_t s,
-                               const uint32_t *d_n) {
-    if (n <= 1 && !d_n) return hipSuccess;
+                               const uint32_t *d_n, const GsrTileStarts *tile_starts) {
     const GsrRadixPlan plan = gsr_radix_plan(begin_bit, end_bit);
+    // with tile_starts even a list of one entry takes its (single) pass: its downsweep carries
+    // the tile ranges
+    if (tile_starts && (plan.n != 1 || n < 1 || tile_starts->gx < 1 ||
+                        tile_starts->gx > (uint32_t)kRadix || tile_starts->rows > (uint32_t)kRadix))
+        return hipErrorInvalidValue;
+    if (n <= 1 && !d_n && !tile_starts) return hipSuccess;
     for (int p = 0; p < plan.n; ++p) {
         rts_pass(*keys, nullptr, *keys_alt, nullptr, n, plan.shift[p], plan.nbits[p], hist,
-                 digit_total, s, d_n);
+                 digit_total, s, d_n, tile_starts);
         std::swap(*keys, *keys_alt);
     }
+    return hipGetLastError();
+}
+
+namespace {
+
+// The tile ranges of a list without a row pass, and the blend's tile-group order, one block: a
+// strip of one tile row (its tiles are the column runs of the column-sorted list), or an empty
+// list (n_host = 0: every range (0, 0)).
+__global__ __launch_bounds__(kBlock) void k_tile_runs(int64_t n_cap,
+                                                      const uint32_t *__restrict__ d_n,
+                                                      const GsrTileStarts ts) {
+    __shared__ uint32_t s_h[kOrderBuckets];
+    __shared__ uint32_t s_w[kBlock / 64];
+    const int64_t n = live_count(d_n, n_cap);
+    const uint32_t n_tiles = ts.gx * ts.rows;
+    for (uint32_t t = threadIdx.x; t < n_tiles; t += kBlock) {
+        uint2 out = make_uint2(0u, 0u);
+        if (n > 0) {  // (then rows = 1: tile t is column t)
+            const uint32_t B0 = ts.col_starts[t], B1 = ts.col_starts[t + 1];
+            if (B0 < B1 && (int64_t)B1 <= n) out = make_uint2(B0, B1);
+        }
+        ts.ranges[t] = out;
+    }
+    __syncthreads();  // (the block reads its own ranges back)
+    blend_order_block<kBlock>(ts.ranges, n_tiles, (n_tiles + kGroupTiles - 1) / kGroupTiles,
+                              ts.order, s_h, s_w);
+}
+
+}  // namespace
+
+hipError_t gsr_launch_tile_runs(int64_t n, const uint32_t *d_n, const GsrTileStarts &ts,
+                                hipStream_t s) {
+    if (ts.gx == 0 || ts.rows == 0) return hipSuccess;
+    if (n > 0 && (ts.rows != 1 || ts.gx > (uint32_t)kRadix)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_tile_runs, dim3(1), dim3(kBlock), 0, s, n, d_n, ts);
     return hipGetLastError();
 }

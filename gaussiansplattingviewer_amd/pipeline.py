@@ -44,7 +44,7 @@ class FramePipeline:
         self.count = 0
         self.graphs = bool(graphs)
         # second_stream (gsr.h GSR_OPT_SECOND_STREAM; default: off at depth >= 3 without graphs):
-        # a frame's tile ranges, blend order and colour on its context's second stream, or in
+        # a frame's K publish and colour on its context's second stream, or in
         # order on the frame's own stream.  The process has GPU_MAX_HW_QUEUES = 4 hardware
         # queues: two frames of two streams each fill them, and so do four frames of one stream
         # each -- which keeps more independent work beside every blend (C3 3,955-3,975 ->

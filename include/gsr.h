@@ -432,8 +432,8 @@ const char *gsr_stage_name(int i);
  *     range of <= 25 bits (3 or 2), else the LSD passes (1 or 0).  Every form gives the same
  *     permutation.
  *   GSR_OPT_FRAME_GRAPHS (default 0): deferred-K frames.  1: the chains of the frame after the
- *     preprocess (the frame stream's K publish + depth sort and its binning; the second
- *     stream's tile ranges, blend order and colour) are recorded once per context and key
+ *     preprocess (the frame stream's K publish + depth sort and its binning with the
+ *     tile ranges and blend order; the second stream's colour) are recorded once per context and key
  *     (input pointers, sizes, strip, workspace) as three linear HIP graphs and replayed; 2: the
  *     same chains launched directly.  Either way the binning is sized by a capacity (the list
  *     lengths seen so far + 25 %) instead of a mid-frame wait for K, the host reads K after
@@ -448,7 +448,7 @@ const char *gsr_stage_name(int i);
  *     Full frames only (a strip's replicated preprocess would write a record per Gaussian for
  *     one strip's lists).  num_rendered stays upstream's count; gsr_get_binning exports the
  *     tight lists (0 binds upstream's lists).
- *   GSR_OPT_SECOND_STREAM (default 1): the frame's tile ranges, blend order and colour run on
+ *   GSR_OPT_SECOND_STREAM (default 1): the frame's K publish (LSD frames) and colour run on
  *     the context's second stream (created on first use), beside the same frame's depth sort and
  *     binning.  0: they run in order on the frame's own stream and the second stream is
  *     destroyed, so the context holds one hardware queue instead of two -- with the process's
