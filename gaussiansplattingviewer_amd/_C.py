@@ -45,6 +45,9 @@ tanfovy, sh, sh_degree, campos, debug, dL_dout_color, dL_ddepth_map, dL_dinv_dep
 dL_dfinal_T)` -> the same 8-tuple are this package's own: the forward with its per-pixel planes
 (`gsr_forward_depth`) and the backward that takes their gradients (`gsr_backward_planes`; an empty
 tensor is an unused gradient), behind `GaussianRasterizationSettings(depth_maps=True)`.
+`_C.rasterize_gaussians_backward_camera(<the same 20 arguments>)` -> that 8-tuple, then
+dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4) and dL_dcampos (3,) (`gsr_backward_camera`), behind a
+`viewmatrix`, `projmatrix` or `campos` that requires a gradient.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -53,7 +56,8 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
-                          rasterize_gaussians_backward, rasterize_gaussians_backward_planes,
+                          rasterize_gaussians_backward, rasterize_gaussians_backward_camera,
+                          rasterize_gaussians_backward_planes,
                           rasterize_gaussians_planes, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "

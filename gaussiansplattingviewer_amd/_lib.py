@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = (
     "gsr_ply_probe", "gsr_ply_load", "gsr_disparity_colors", "gsr_pack_image",
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
-    "gsr_backward_planes", "gsr_forward_surface",
+    "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -107,6 +107,14 @@ class GsrPlaneGradients(ctypes.Structure):
                 ("dL_dfinal_T", ctypes.c_void_p), ("dL_ddepths", ctypes.c_void_p)]
 
 
+CAMERA_GRADIENT_NAMES = ("dL_dviewmatrix", "dL_dprojmatrix", "dL_dcampos")
+
+
+class GsrCameraGradients(ctypes.Structure):
+    """gsr_camera_gradients: gsr_backward_camera's outputs, 16 / 16 / 3 floats (None = not wanted)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in CAMERA_GRADIENT_NAMES]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -165,6 +173,15 @@ def _declare(lib: ctypes.CDLL) -> None:
                                             ctypes.POINTER(GsrPlaneGradients),
                                             ctypes.POINTER(GsrGradients), vp]
         lib.gsr_backward_planes.restype = i32
+    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_camera_fn() says so)
+    if hasattr(lib, "gsr_backward_camera"):
+        lib.gsr_backward_camera.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                            ctypes.POINTER(GsrRasterSettings),
+                                            ctypes.POINTER(GsrBackwardInputs),
+                                            ctypes.POINTER(GsrPlaneGradients),
+                                            ctypes.POINTER(GsrCameraGradients),
+                                            ctypes.POINTER(GsrGradients), vp]
+        lib.gsr_backward_camera.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -248,6 +265,17 @@ def backward_planes_fn(lib: ctypes.CDLL):
         raise RuntimeError(
             f"{LIB_PATH} has no gsr_backward_planes: gradients of depth_map / inv_depth_map / "
             "final_T need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
+            "additive)")
+    return fn
+
+
+def backward_camera_fn(lib: ctypes.CDLL):
+    """gsr_backward_camera of a loaded library; RuntimeError if that build does not have it."""
+    fn = getattr(lib, "gsr_backward_camera", None)
+    if fn is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_backward_camera: gradients of viewmatrix / projmatrix / "
+            "campos need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
             "additive)")
     return fn
 

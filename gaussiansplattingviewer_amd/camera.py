@@ -135,3 +135,20 @@ def orbit_eye(i: int, n: int = 1000, radius: float = 4.0, height: float = 0.5):
     """Config C5 orbit: eye_i = (r sin t, 0.5, r cos t), t = 2 pi i / n (cf. main_test.py:392-426)."""
     t = 2.0 * math.pi * i / n
     return (radius * math.sin(t), height, radius * math.cos(t))
+
+
+def camera_tensors(view, proj_gl):
+    """`cuda_camera_inputs` in torch, differentiable: a (4, 4) GL view matrix tensor in math
+    layout (translation in [:3, 3]) and the GL projection (tensor or array, e.g.
+    `Camera.get_project_matrix()`) -> (viewmatrix, projmatrix, campos) as the rasterizer takes
+    them: rows 0 and 2 of the view negated, projmatrix = proj_gl @ view, both transposed to
+    upstream's column-major, and campos = inverse(view)[:3, 3], the eye of that view (the viewer
+    passes `Camera.position`, which is that eye for a look-at view).  Built from torch operations
+    on `view`'s dtype and device, so with the camera's gradients (gsr_backward_camera) a loss on
+    the rendered image reaches `view`, and through it whatever pose parameters made it."""
+    import torch
+    proj_gl = torch.as_tensor(proj_gl, dtype=view.dtype, device=view.device)
+    flip = torch.tensor([-1.0, 1.0, -1.0, 1.0], dtype=view.dtype, device=view.device)
+    v = view * flip[:, None]
+    campos = torch.linalg.inv(view)[:3, 3]
+    return v.t().contiguous(), (proj_gl @ v).t().contiguous(), campos

@@ -180,6 +180,8 @@ struct gsr_context {
     // sums into, and the radii of the per-Gaussian stage it rebuilds
     Buf<float> grad2d{bufs};
     Buf<int32_t> bwd_radii{bufs};
+    // gsr_backward_camera: the blocks' partial sums of the camera's 27 entries, [27][blocks]
+    Buf<float> cam_partials{bufs};
     // ... and the events around its three stages (rebuild, blend backward, per-Gaussian backward)
     // of the last backward run under gsr_set_timing (created by the first one; gsr_backward_times)
     hipEvent_t ev_bwd[4] = {};
@@ -1491,9 +1493,13 @@ int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
 // nothing of an earlier forward on this context is read; then backward.hip's two kernels.
 // pl: gsr_backward_planes' struct, or NULL (gsr_backward).  With one of its three plane gradients
 // the two kernels are backward.hip's planes instantiations; without, they are gsr_backward's.
+// cam: gsr_backward_camera's struct, or NULL.  With one of its three buffers the per-Gaussian
+// backward is the camera instantiation (with or without the planes) and k_camera_finish follows
+// it, inside the third timed stage; without, nothing differs from the call without it.
 static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                     const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
-                    gsr_gradients *gr, void *stream, const std::string &fn) {
+                    const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
+                    const std::string &fn) {
     if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
     if (st->tile_row_begin != 0 || st->tile_row_end != 0)
         return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
@@ -1519,7 +1525,25 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     std::lock_guard<std::mutex> lock(ctx->mu);
     hipStream_t s = static_cast<hipStream_t>(stream);
     GSR_TRY(order_stream(ctx, s));
-    if (P == 0) return GSR_OK;  // no Gaussian, no gradient
+    const bool camera =
+        cam && (cam->dL_dviewmatrix || cam->dL_dprojmatrix || cam->dL_dcampos);
+    if (P == 0) {  // no Gaussian, no gradient: the camera's buffers, of a fixed size, are zeros
+        if (camera) {
+            if (cam->dL_dviewmatrix)
+                GSR_HIP(hipMemsetAsync(cam->dL_dviewmatrix, 0, 16 * sizeof(float), s),
+                        "hipMemsetAsync(dL_dviewmatrix)");
+            if (cam->dL_dprojmatrix)
+                GSR_HIP(hipMemsetAsync(cam->dL_dprojmatrix, 0, 16 * sizeof(float), s),
+                        "hipMemsetAsync(dL_dprojmatrix)");
+            if (cam->dL_dcampos)
+                GSR_HIP(hipMemsetAsync(cam->dL_dcampos, 0, 3 * sizeof(float), s),
+                        "hipMemsetAsync(dL_dcampos)");
+        }
+        return GSR_OK;
+    }
+    if (camera)
+        GSR_TRY(grow(ctx, ctx->cam_partials,
+                     (size_t)kCameraSums * gsr_preprocess_blocks(P) * sizeof(float), s));
     GSR_TRY(grow(ctx, ctx->grad2d, (size_t)P * kGradRow * sizeof(float), s));
     GSR_TRY(grow(ctx, ctx->bwd_radii, (size_t)P * sizeof(int32_t), s));
 
@@ -1612,7 +1636,16 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     pb.dL_dscales = gr->dL_dscales;
     pb.dL_drotations = gr->dL_drotations;
     pb.dL_dcov3D = gr->dL_dcov3D;
-    if (planes) {
+    if (camera) {
+        // (an empty list leaves the rows zero: every product, and so every sum, is 0)
+        const GsrCameraBwdArgs ca{ctx->cam_partials.get(), cam->dL_dviewmatrix,
+                                  cam->dL_dprojmatrix, cam->dL_dcampos};
+        GSR_HIP(gsr_launch_preprocess_bwd_camera(pb, planes, planes ? dL_ddepths : nullptr, ca, s),
+                "per-Gaussian backward launch");
+        if (!planes && dL_ddepths)
+            GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
+                    "hipMemsetAsync(dL_ddepths)");
+    } else if (planes) {
         GSR_HIP(gsr_launch_preprocess_bwd_planes(pb, dL_ddepths, s),
                 "per-Gaussian backward launch");
     } else {
@@ -1628,13 +1661,19 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
 
 int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                  const gsr_backward_inputs *in, gsr_gradients *gr, void *stream) {
-    return backward(ctx, g, st, in, nullptr, gr, stream, "gsr_backward");
+    return backward(ctx, g, st, in, nullptr, nullptr, gr, stream, "gsr_backward");
 }
 
 int gsr_backward_planes(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         gsr_gradients *gr, void *stream) {
-    return backward(ctx, g, st, in, planes, gr, stream, "gsr_backward_planes");
+    return backward(ctx, g, st, in, planes, nullptr, gr, stream, "gsr_backward_planes");
+}
+
+int gsr_backward_camera(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                        const gsr_camera_gradients *camera, gsr_gradients *gr, void *stream) {
+    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_camera");
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

@@ -23,6 +23,13 @@
 //    gradients enter the recursion's start value and per-splat term, and a tenth sum per splat
 //    (dL/dz through the two features) goes to word 9 of the Gaussian's row and from there to
 //    dL_dmeans3D along the view matrix's z row.  Without the flag the bodies compile as before.
+//  * k_preprocess_bwd_camera, k_preprocess_bwd_planes_camera, k_camera_finish -- the per-Gaussian
+//    body with kCamera set (gsr_backward_camera): the factors of the camera's
+//    gradient the body computes on its way to dL_dmeans3D (dhom, dt, dA, J, the SH direction
+//    term) are kept, multiplied out to 27 products after the body and summed over the block
+//    (rows of 16 lanes by DPP, the 16 rows through LDS), one word per sum and block; the finish
+//    adds the blocks in double.  No atomics.  Without the flag the two kernels above compile as
+//    before (profiles/backward_camera_resources.txt).
 #include "gsr_internal.h"
 
 #include <type_traits>
@@ -298,16 +305,130 @@ __device__ __forceinline__ void store3(float *p, int64_t i, float x, float y, fl
 }
 
 
-// Both kernels are the statements of backward_gaussian.inc; the second adds the planes' term.
+// ---- the camera's gradient (gsr_backward_camera) ---------------------------------
+// What one Gaussian leaves of backward_gaussian.inc for the 27 sums: the factors, not the
+// products, so that only dh and dc live through the body's SH section.
+struct CameraTerms {
+    float dh[3];          // dL/d(hom.x, hom.y, hom.w)
+    float dc[3];          // dL/dcampos through the SH direction
+    float dt[3];          // dL/dt, t the view-space mean (the clamp's and the planes' terms in dt[2])
+    float dA0[3], dA1[3]; // dL/dA, A = J R
+    float J[4];           // J00, J02, J11, J12
+    float q[4];           // the world mean, 1
+};
+constexpr int kCamSums = kCameraSums;  // view matrix rows 0..2 (12), projection rows 0, 1, 3 (12), campos (3)
+
+// Sum k of the block's Gaussians, in the order the finish (k_camera_finish) maps back:
+//   k = 3 c + r      (k < 12)  dL/dvm[4 c + r], r < 3: dt_r q_c + (J^T dA)[r][c] for c < 3
+//   k = 12 + 3 c + j           dL/dpm[4 c + r], r = 0, 1, 3 for j = 0, 1, 2: dh_j q_c
+//   k = 24 + i                 dL/dcampos[i]
+// Called by every thread of the block (a thread without a kept Gaussian brings zeros): a row of 16
+// lanes by DPP, the block's 16 rows through LDS in a fixed order, then one word per sum to
+// partials[k * gridDim.x + blockIdx.x].
+__device__ __forceinline__ void camera_block_sums(const CameraTerms &t, float *partials) {
+    __shared__ float s_cam[16][kCamSums];
+    float v[kCamSums];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        v[3 * c] = t.dt[0] * t.q[c];
+        v[3 * c + 1] = t.dt[1] * t.q[c];
+        v[3 * c + 2] = t.dt[2] * t.q[c];
+        if (c < 3) {
+            v[3 * c] += t.J[0] * t.dA0[c];
+            v[3 * c + 1] += t.J[2] * t.dA1[c];
+            v[3 * c + 2] += t.J[1] * t.dA0[c] + t.J[3] * t.dA1[c];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v[12 + 3 * c + j] = t.dh[j] * t.q[c];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[24 + i] = t.dc[i];
+    const int row = threadIdx.x >> 4;
+#pragma unroll
+    for (int k = 0; k < kCamSums; ++k) {
+        const float sum = row_sum(v[k]);
+        if ((threadIdx.x & 15) == 0) s_cam[row][k] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCamSums) {
+        float sum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += s_cam[r][threadIdx.x];
+        partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = sum;
+    }
+}
+
+// One block per sum: the column of the blocks' partials in double, a thread's share in index
+// order, the block's 256 shares by a fixed tree; rounded once.  The same partials give the same
+// bits.  The entries the forward never reads (the view matrix's row 3, the projection's row 2:
+// nothing reads hom.z) are written as 0.
+__global__ __launch_bounds__(256) void k_camera_finish(const float *partials, uint32_t blocks,
+                                                       float *dL_dviewmatrix,
+                                                       float *dL_dprojmatrix, float *dL_dcampos) {
+    __shared__ double s_sum[256];
+    const uint32_t k = blockIdx.x;
+    const float *col = partials + (size_t)k * blocks;
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < blocks; i += 256) acc += (double)col[i];
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t n = 128; n > 0; n >>= 1) {
+        if (threadIdx.x < n) s_sum[threadIdx.x] += s_sum[threadIdx.x + n];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const float out = (float)s_sum[0];
+    if (k < 12) {
+        const uint32_t c = k / 3, r = k % 3;
+        if (dL_dviewmatrix) {
+            dL_dviewmatrix[4 * c + r] = out;
+            if (r == 0) dL_dviewmatrix[4 * c + 3] = 0.f;
+        }
+    } else if (k < 24) {
+        const uint32_t c = (k - 12) / 3, j = (k - 12) % 3;
+        if (dL_dprojmatrix) {
+            dL_dprojmatrix[4 * c + (j == 2 ? 3 : j)] = out;
+            if (j == 0) dL_dprojmatrix[4 * c + 2] = 0.f;
+        }
+    } else if (dL_dcampos) {
+        dL_dcampos[k - 24] = out;
+    }
+}
+
+// The four kernels are the statements of backward_gaussian.inc; the second adds the planes' term,
+// the camera pair keeps the camera's factors (the text as a lambda's body: its early returns leave
+// the lambda, not the kernel) and sums them over the block.
 __global__ __launch_bounds__(256) void k_preprocess_bwd(const GsrPreprocessBwdArgs a) {
-    constexpr bool kPlanes = false;
+    constexpr bool kPlanes = false, kCamera = false;
     [[maybe_unused]] float *const dL_ddepths = nullptr;
+    [[maybe_unused]] CameraTerms cam;
 #include "backward_gaussian.inc"
 }
 __global__ __launch_bounds__(256) void k_preprocess_bwd_planes(const GsrPreprocessBwdArgs a,
                                                                float *dL_ddepths) {
-    constexpr bool kPlanes = true;
+    constexpr bool kPlanes = true, kCamera = false;
+    [[maybe_unused]] CameraTerms cam;
 #include "backward_gaussian.inc"
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_camera(const GsrPreprocessBwdArgs a,
+                                                               float *partials) {
+    constexpr bool kPlanes = false, kCamera = true;
+    [[maybe_unused]] float *const dL_ddepths = nullptr;
+    CameraTerms cam{};
+    [&] {
+#include "backward_gaussian.inc"
+    }();
+    camera_block_sums(cam, partials);
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_planes_camera(const GsrPreprocessBwdArgs a,
+                                                                      float *dL_ddepths,
+                                                                      float *partials) {
+    constexpr bool kPlanes = true, kCamera = true;
+    CameraTerms cam{};
+    [&] {
+#include "backward_gaussian.inc"
+    }();
+    camera_block_sums(cam, partials);
 }
 
 }  // namespace
@@ -346,5 +467,26 @@ hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &args, fl
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
     hipLaunchKernelGGL(k_preprocess_bwd_planes, dim3((unsigned)gsr_preprocess_blocks(a.P)),
                        dim3(256), 0, s, a, dL_ddepths);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &args, bool planes,
+                                            float *dL_ddepths, const GsrCameraBwdArgs &c,
+                                            hipStream_t s) {
+    if (args.P <= 0 || !c.partials || (!c.dL_dviewmatrix && !c.dL_dprojmatrix && !c.dL_dcampos))
+        return hipErrorInvalidValue;
+    GsrPreprocessBwdArgs a = args;
+    a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
+                (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
+    const unsigned blocks = (unsigned)gsr_preprocess_blocks(a.P);
+    if (planes)
+        hipLaunchKernelGGL(k_preprocess_bwd_planes_camera, dim3(blocks), dim3(256), 0, s, a,
+                           dL_ddepths, c.partials);
+    else
+        hipLaunchKernelGGL(k_preprocess_bwd_camera, dim3(blocks), dim3(256), 0, s, a, c.partials);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_camera_finish, dim3(kCamSums), dim3(256), 0, s, c.partials, blocks,
+                       c.dL_dviewmatrix, c.dL_dprojmatrix, c.dL_dcampos);
     return hipGetLastError();
 }

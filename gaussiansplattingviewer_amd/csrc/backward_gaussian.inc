@@ -5,6 +5,11 @@
 // holds its registers line for line), where an inlined callee taking the arguments moved them.
 // kPlanes: word 9 of the row is dL/dz through the planes' features; it goes to dL_ddepths
 // (optional) and, z being the view matrix's z row applied to the mean, to dL_dmeans3D.
+// kCamera (k_preprocess_bwd_camera, k_preprocess_bwd_planes_camera): the factors of the camera's
+// gradient (gsr_backward_camera) go to `cam` (CameraTerms, zero on entry) on the way; the text is
+// then the body of a lambda, so each `return` below leaves the lambda with cam's zeros or what
+// was set so far and every thread of the block reaches the reduction after it.  Without the flag
+// cam is not touched and the kernels compile as before.
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.P) return;
     float *const sh_out = a.dL_dsh ? a.dL_dsh + idx * (int64_t)a.M * 3 : nullptr;
@@ -52,6 +57,7 @@
         dpx += pm[0] * dhx + pm[1] * dhy + pm[3] * dhw;
         dpy += pm[4] * dhx + pm[5] * dhy + pm[7] * dhw;
         dpz += pm[8] * dhx + pm[9] * dhy + pm[11] * dhw;
+        if constexpr (kCamera) cam.dh[0] = dhx, cam.dh[1] = dhy, cam.dh[2] = dhw;
     }
 
     // ---- the colour: rgb = max(sum_b basis_b(dir) sh_b + 0.5, 0), dir = (p - campos) / len -----
@@ -119,6 +125,11 @@
         dpx += (ddx - dx * dot) / len;
         dpy += (ddy - dy * dot) / len;
         dpz += (ddz - dz * dot) / len;
+        if constexpr (kCamera) {  // dir depends on p - campos: minus the mean's term
+            cam.dc[0] = -((ddx - dx * dot) / len);
+            cam.dc[1] = -((ddy - dy * dot) / len);
+            cam.dc[2] = -((ddz - dz * dot) / len);
+        }
     } else if (sh_out) {
         for (int i = 0; i < 3 * a.M; ++i) sh_out[i] = 0.f;
     }
@@ -208,6 +219,13 @@
         dpx += vm[2] * gz, dpy += vm[6] * gz, dpz += vm[10] * gz;
     }
     store3(a.dL_dmeans3D, idx, dpx, dpy, dpz);
+    if constexpr (kCamera) {
+        cam.q[0] = p.x, cam.q[1] = p.y, cam.q[2] = p.z, cam.q[3] = 1.0f;
+        cam.dt[0] = dtx, cam.dt[1] = dty, cam.dt[2] = dtz;
+        if constexpr (kPlanes) cam.dt[2] += gr[9];  // z = t.z
+        for (int c = 0; c < 3; ++c) cam.dA0[c] = dA0[c], cam.dA1[c] = dA1[c];
+        cam.J[0] = J00, cam.J[1] = J02, cam.J[2] = J11, cam.J[3] = J12;
+    }
 
     // ---- Sigma = N N^T, N = Rq diag(mod s) (the rotation as given, not renormalised) ------------
     if (a.cov3D_precomp) {

@@ -650,3 +650,17 @@ hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t 
 // dL_dmeans3D and writes it to dL_ddepths ([P], optional).
 hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &a, float *dL_ddepths,
                                             hipStream_t s);
+// gsr_backward_camera (k_preprocess_bwd_camera / k_preprocess_bwd_planes_camera, then
+// k_camera_finish): the per-Gaussian backward, with the planes' term if `planes`, that also sums
+// the camera's 27 gradient entries over the Gaussians.  partials: workspace of
+// kCameraSums x gsr_preprocess_blocks(P) floats, [sum][block], every word written before it is
+// read.  The three outputs (device, 16 / 16 / 3 floats, at least one given) are written, the
+// entries the forward never reads as 0.  No atomics: the same 2D gradient rows give the same bits.
+constexpr int kCameraSums = 27;
+struct GsrCameraBwdArgs {
+    float *partials;
+    float *dL_dviewmatrix, *dL_dprojmatrix, *dL_dcampos;
+};
+hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &a, bool planes,
+                                            float *dL_ddepths, const GsrCameraBwdArgs &c,
+                                            hipStream_t s);

@@ -31,6 +31,10 @@
 //                                          dL_dinv_depth_map, dL_dfinal_T) -> the same 8-tuple
 //     this package's own (GaussianRasterizationSettings.depth_maps): gsr_forward_depth with
 //     final_T, and gsr_backward_planes; an empty gradient tensor is an unused one.
+//   _C.rasterize_gaussians_backward_camera(<rasterize_gaussians_backward_planes' 20 arguments>)
+//       -> its 8-tuple, then dL_dviewmatrix [4,4], dL_dprojmatrix [4,4], dL_dcampos [3]
+//     this package's own: gsr_backward_camera.  The two matrices' gradients are in the inputs'
+//     layout (the 16 floats of the input, viewed (4, 4)).
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -214,7 +218,8 @@ using Backward8 = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch:
 
 // The backward of both entries.  planes (3 tensors: dL_ddepth_map, dL_dinv_depth_map,
 // dL_dfinal_T, each [H,W] or empty = unused), or nullptr: gsr_backward.  With a plane gradient
-// dL_dout_color may be empty.
+// dL_dout_color may be empty.  camera (3 tensors, written: dL_dviewmatrix [4,4], dL_dprojmatrix
+// [4,4], dL_dcampos [3]), or nullptr: with it the call is gsr_backward_camera.
 Backward8 backward_impl(
     const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
     const torch::Tensor &scales, const torch::Tensor &rotations, double scale_modifier,
@@ -222,7 +227,7 @@ Backward8 backward_impl(
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy,
     const torch::Tensor &dL_dout_color, const torch::Tensor &sh, int64_t degree,
     const torch::Tensor &campos, bool debug, const torch::Tensor &opacities,
-    const torch::Tensor *planes) {
+    const torch::Tensor *planes, torch::Tensor *camera = nullptr) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -256,6 +261,10 @@ Backward8 backward_impl(
     torch::Tensor d_colors = torch::zeros({P, 3}, f32), d_opacity = torch::zeros({P, 1}, f32);
     torch::Tensor d_cov3D = torch::zeros({P, 6}, f32), d_sh = torch::zeros({P, M, 3}, f32);
     torch::Tensor d_scales = torch::zeros({P, 3}, f32), d_rot = torch::zeros({P, 4}, f32);
+    if (camera) {  // (no Gaussian: zeros)
+        camera[0] = torch::zeros({4, 4}, f32), camera[1] = torch::zeros({4, 4}, f32);
+        camera[2] = torch::zeros({3}, f32);
+    }
     if (P != 0) {
         std::vector<torch::Tensor> keep;
         gsr_gaussians g{};
@@ -305,8 +314,15 @@ Backward8 backward_impl(
         int rc;
         {  // the rebuild waits for K (pinned memory), as the forward does
             pybind11::gil_scoped_release no_gil;
-            rc = planes ? gsr_backward_planes(ctx, &g, &st, &in, &pg, &gr, s)
-                        : gsr_backward(ctx, &g, &st, &in, &gr, s);
+            if (camera) {
+                const gsr_camera_gradients cg{camera[0].data_ptr<float>(),
+                                              camera[1].data_ptr<float>(),
+                                              camera[2].data_ptr<float>()};
+                rc = gsr_backward_camera(ctx, &g, &st, &in, planes ? &pg : nullptr, &cg, &gr, s);
+            } else {
+                rc = planes ? gsr_backward_planes(ctx, &g, &st, &in, &pg, &gr, s)
+                            : gsr_backward(ctx, &g, &st, &in, &gr, s);
+            }
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_backward failed (", rc, "): ", gsr_last_error());
     }
@@ -343,6 +359,27 @@ Backward8 rasterize_gaussians_backward_planes(
     return backward_impl(background, means3D, colors, scales, rotations, scale_modifier,
                          cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                          sh, degree, campos, debug, opacities, planes);
+}
+
+// rasterize_gaussians_backward_planes with the camera's gradients after its 8-tuple.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor>
+rasterize_gaussians_backward_camera(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T) {
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    torch::Tensor camera[3];
+    const Backward8 g = backward_impl(background, means3D, colors, scales, rotations,
+                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                      tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, debug,
+                                      opacities, planes, camera);
+    return std::tuple_cat(g, std::make_tuple(camera[0], camera[1], camera[2]));
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -396,6 +433,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, sh, sh_degree, campos, debug, "
           "dL_dout_color, dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T (empty = unused) -> "
           "rasterize_gaussians_backward's 8-tuple");
+    m.def("rasterize_gaussians_backward_camera", &rasterize_gaussians_backward_camera,
+          "rasterize_gaussians_backward_planes' 20 arguments -> its 8-tuple, then dL_dviewmatrix "
+          "(4, 4), dL_dprojmatrix (4, 4), dL_dcampos (3)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -14,7 +14,9 @@ The viewer renders under `torch.no_grad()` (renderer_cuda.py:214) and pays nothi
 image is differentiable: `_RasterizeGaussians.backward` returns the gradients of the splat
 composite (`gsr_backward`, include/gsr.h), as upstream's does for training code.  With
 `GaussianRasterizationSettings.depth_maps` the rasterizer also returns depth_map, inv_depth_map and
-final_T, differentiable too (`_RasterizeGaussiansPlanes`, `gsr_backward_planes`).
+final_T, differentiable too (`_RasterizeGaussiansPlanes`, `gsr_backward_planes`).  When
+`viewmatrix`, `projmatrix` or `campos` of the settings requires a gradient, the camera gets one as
+well (`_RasterizeGaussiansCamera`, `gsr_backward_camera`).
 """
 from __future__ import annotations
 
@@ -246,7 +248,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         tanfovx, tanfovy, dL_dout_color, sh, degree, campos,
                                         debug=False, *, conic=False, stream=None, slot=0,
                                         dL_ddepth_map=None, dL_dinv_depth_map=None,
-                                        dL_dfinal_T=None, depths=False) -> dict:
+                                        dL_dfinal_T=None, depths=False, camera=False) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -256,7 +258,10 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     With dL_ddepth_map, dL_dinv_depth_map or dL_dfinal_T ((H, W) each, None = unused), or
     depths=True, the call is `gsr_backward_planes`: the planes' gradients join the image's
     (dL_dout_color may then be None; H, W come from the first plane given), and depths=True adds
-    dL_ddepths (P,), dL/dz through the features z and 1 / z only."""
+    dL_ddepths (P,), dL/dz through the features z and 1 / z only.
+
+    camera=True: the call is `gsr_backward_camera` and adds dL_dviewmatrix (4, 4), dL_dprojmatrix
+    (4, 4), both in the inputs' (column-major) layout, and dL_dcampos (3,)."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
@@ -323,8 +328,21 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         stream = torch.cuda.current_stream(device).cuda_stream
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
+    cam = {}
+    if camera:
+        cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
+               "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     with torch.cuda.device(dev_index):
-        if plane_grads or depths:
+        if camera:
+            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
+                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
+            cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
+            _lib.check(_lib.backward_camera_fn(lib)(
+                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
+                ctypes.byref(planes) if plane_grads or depths else None, ctypes.byref(cg),
+                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_camera")
+            grads.update(cam)
+        elif plane_grads or depths:
             planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
                                             dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
             _lib.check(_lib.backward_planes_fn(lib)(
@@ -341,7 +359,16 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         cov3Ds_precomp, raster_settings: GaussianRasterizationSettings):
     """upstream rasterize_gaussians(...) -> (color, radii), through _RasterizeGaussians; with
     raster_settings.depth_maps -> (color, radii, depth_map, inv_depth_map, final_T), through
-    _RasterizeGaussiansPlanes."""
+    _RasterizeGaussiansPlanes.  When viewmatrix, projmatrix or campos of the settings requires a
+    gradient (and gradients are recorded), through _RasterizeGaussiansCamera, which returns the
+    same outputs and also differentiates with respect to the three."""
+    rs = raster_settings
+    if torch.is_grad_enabled() and any(
+            isinstance(t, torch.Tensor) and t.requires_grad
+            for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
+        return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities,
+                                               scales, rotations, cov3Ds_precomp, rs,
+                                               rs.viewmatrix, rs.projmatrix, rs.campos)
     if raster_settings.depth_maps:
         return _RasterizeGaussiansPlanes.apply(means3D, means2D, sh, colors_precomp, opacities,
                                                scales, rotations, cov3Ds_precomp, raster_settings)
@@ -523,6 +550,83 @@ class _RasterizeGaussiansPlanes(torch.autograd.Function):
                 d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
                 d_scales if has(scales) else None, d_rot if has(rotations) else None,
                 d_cov3D if has(cov3Ds) else None, None)
+
+
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """The two Functions above with the camera as tensor arguments: viewmatrix, projmatrix and
+    campos (those of the settings, which the forward reads) follow raster_settings, and backward
+    returns their gradients in the inputs' shape, dtype and device (`gsr_backward_camera`; each
+    the partial with the other two held fixed).  The forward is the very call of the Function it
+    stands in for -- (color, radii), or with depth_maps the 5-tuple -- so its outputs have those
+    bits.  An unused output's gradient travels as NULL; a shading raises in backward."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                cov3Ds_precomp, raster_settings, viewmatrix, projmatrix, campos):
+        rs = raster_settings
+        ctx.has_means2D = isinstance(means2D, torch.Tensor)
+        ctx.raster_settings = rs
+        ctx.set_materialize_grads(False)
+        none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
+        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
+                              none(rotations), none(cov3Ds_precomp), viewmatrix, projmatrix,
+                              campos)
+        # (inside a Function's forward no graph is recorded: the inner Function saves nothing)
+        inner = _RasterizeGaussiansPlanes if rs.depth_maps else _RasterizeGaussians
+        out = inner.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                          cov3Ds_precomp, rs)
+        ctx.mark_non_differentiable(out[1])
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth=None, grad_inv_depth=None,
+                 grad_final_T=None):
+        """Gradients in input order: the nine of `_RasterizeGaussians.backward`, then
+        viewmatrix's, projmatrix's and campos's."""
+        del grad_radii
+        rs = ctx.raster_settings
+        if rs.shading:
+            raise RuntimeError("gaussiansplattingviewer_amd differentiates the splat composite "
+                               f"only: no backward under shading {rs.shading}")
+        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, viewmatrix,
+         projmatrix, campos) = ctx.saved_tensors
+        grads = [None if t is None else t.contiguous()
+                 for t in (grad_color, grad_depth, grad_inv_depth, grad_final_T)]
+        if all(t is None for t in grads):  # nothing reaches the outputs
+            return (None,) * 12
+        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
+            g = rasterize_gaussians_backward_native(
+                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
+                cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
+                rs.sh_degree, campos, rs.debug, dL_ddepth_map=grads[1],
+                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], camera=True)
+            z = lambda n: g.get(n)  # noqa: E731
+            (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
+             d_proj, d_campos) = (
+                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
+                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"),
+                z("dL_dviewmatrix"), z("dL_dprojmatrix"), z("dL_dcampos"))
+        else:
+            from . import _C
+            e = torch.empty(0)
+            as_dev = lambda t: _as_dev(t.detach(), means3D.device, "")  # noqa: E731
+            (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
+             d_proj, d_campos) = _C.rasterize_gaussians_backward_camera(
+                rs.bg, means3D, colors_precomp, opacities, scales, rotations,
+                rs.scale_modifier, cov3Ds, as_dev(viewmatrix), as_dev(projmatrix), rs.tanfovx,
+                rs.tanfovy, sh, rs.sh_degree, as_dev(campos), rs.debug,
+                *(e if t is None else t for t in grads))
+        has = lambda t: t.numel() != 0  # noqa: E731
+        need = ctx.needs_input_grad
+        like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731
+        return (d_means3D, d_means2D if ctx.has_means2D else None,
+                d_sh.reshape(sh.shape) if has(sh) else None,
+                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
+                d_scales if has(scales) else None, d_rot if has(rotations) else None,
+                d_cov3D if has(cov3Ds) else None, None,
+                like(d_view, viewmatrix) if need[9] else None,
+                like(d_proj, projmatrix) if need[10] else None,
+                like(d_campos, campos) if need[11] else None)
 
 
 class GaussianRasterizer(torch.nn.Module):

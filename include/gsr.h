@@ -323,6 +323,47 @@ typedef struct {
 int gsr_backward_planes(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         gsr_gradients *grads, void *stream);
+/* gsr_backward_planes that also returns the gradients of the camera: the view matrix, the
+ * projection matrix and the camera position of gsr_raster_settings.  (Additive to ABI 4.)
+ * The three are independent arguments of the forward, so each gradient is the partial with the
+ * other two held fixed; a caller whose projmatrix and campos are functions of a pose chains them.
+ * With q = (x, y, z, 1) the world mean of a Gaussian the forward kept (radii > 0), vm and pm the
+ * column-major matrices and c = campos, the forward reads the camera in four places, and each
+ * gradient is the sum over the kept Gaussians of:
+ *   1. the projective divide, hom_r = sum_c pm[4c+r] q_c, of which hom.x, hom.y and hom.w are
+ *      used:  dL/dpm[4c+r] += dhom_r q_c for r = 0, 1, 3.  Nothing reads hom.z (the depth is the
+ *      view matrix's), so row 2 of dL_dprojmatrix is exactly 0;
+ *   2. the view transform, t_r = sum_c vm[4c+r] q_c, r < 3:  dL/dvm[4c+r] += dt_r q_c, with dt
+ *      through the Jacobian J of the EWA covariance, the 1.3 tan clamp as gsr_backward
+ *      differentiates it (on its flat side dt.x or dt.y is 0 and dt.z takes the clamped ratio
+ *      times it) and, with plane gradients, dL/dz through the features, because z = t_2;
+ *   3. the view rotation in A = J R, R[r][c] = vm[4c+r], c < 3:  dL/dR = J^T dL/dA, that is
+ *      dL/dvm[4c+0] += J00 dA0[c], dL/dvm[4c+1] += J11 dA1[c],
+ *      dL/dvm[4c+2] += J02 dA0[c] + J12 dA1[c];
+ *   4. the SH direction (p - c) / |p - c|:  dL/dc -= (dd - dir (dir . dd)) / len, minus the term
+ *      dL_dmeans3D gets; exactly 0 with colors_precomp.
+ * Entries the forward never reads get exactly 0: row 3 of the view matrix (vm[3], vm[7], vm[11],
+ * vm[15]) and row 2 of the projection.  Everything gsr_backward holds constant stays constant
+ * (the z <= 0.2 cull, det == 0, rect and tile membership, the depth order, the skips, the cap, the
+ * termination), and so do tanfovx, tanfovy and the focal lengths derived from them: the
+ * intrinsics get no gradient.
+ * The 27 sums are reduced without atomics (per block, then over the blocks in double, rounded
+ * once): given the same per-Gaussian 2D gradients they are bit-reproducible; those come from
+ * gsr_backward's float atomics, so the last bits may still differ from run to run.
+ * A NULL camera, or one with three NULL members, is gsr_backward_planes itself: the same kernels,
+ * the same arguments.  planes may be NULL as there.  Each buffer given is written, not accumulated
+ * into; with P == 0, or nothing on any list, it is zero-filled.  Everything else is
+ * gsr_backward_planes': whole frames only (a strip: GSR_E_INVALID, nothing written), a function
+ * of its inputs, exact zeros for culled Gaussians' own gradients, the debug stage checks, and
+ * timing through gsr_backward_times with the new work inside ms[2]. */
+typedef struct {
+    float *dL_dviewmatrix; /* device [16], the input's column-major layout, or NULL */
+    float *dL_dprojmatrix; /* device [16] or NULL */
+    float *dL_dcampos;     /* device [3]  or NULL */
+} gsr_camera_gradients;
+int gsr_backward_camera(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                        const gsr_camera_gradients *camera, gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

@@ -15,9 +15,14 @@ final_T beside the image's (k_blend_bwd_planes_q, k_preprocess_bwd_planes: ten s
 contribution); the forward timed is then gsr_forward_depth with final_T, the frame that backward
 belongs to.
 
+--camera: the backward is gsr_backward_camera, which also returns the gradients of viewmatrix,
+projmatrix and campos (k_preprocess_bwd_camera / k_preprocess_bwd_planes_camera and
+k_camera_finish, inside the third stage); with or without --planes.
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
+                                      [--camera]
 """
 import argparse
 import ctypes
@@ -63,9 +68,10 @@ def worker(a):
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
                                                    scene.scale, scene.rot, 1.0, None, view, proj,
                                                    tx, ty, dL, scene.sh, scene.deg, campos,
-                                                   **plane_grads)
+                                                   camera=bool(a.camera), **plane_grads)
 
-    out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes)}
+    out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
+           "camera": bool(a.camera)}
     if a.step == "forward":
         for _ in range(a.warmup):
             forward()
@@ -109,6 +115,8 @@ def main():
                          "per quadrant wave, blend.hip)")
     ap.add_argument("--planes", action="store_true",
                     help="gsr_backward_planes: colour plus the three planes' gradients")
+    ap.add_argument("--camera", action="store_true",
+                    help="gsr_backward_camera: also the gradients of the camera")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -117,7 +125,8 @@ def main():
     for step in ("forward", "backward"):  # a fresh process each, under its own time limit
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", a.config,
                             "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step] +
-                           (["--planes"] if a.planes else []),
+                           (["--planes"] if a.planes else []) +
+                           (["--camera"] if a.camera else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
