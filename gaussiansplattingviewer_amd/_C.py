@@ -48,6 +48,10 @@ tensor is an unused gradient), behind `GaussianRasterizationSettings(depth_maps=
 `_C.rasterize_gaussians_backward_camera(<the same 20 arguments>)` -> that 8-tuple, then
 dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4) and dL_dcampos (3,) (`gsr_backward_camera`), behind a
 `viewmatrix`, `projmatrix` or `campos` that requires a gradient.
+`_C.rasterize_gaussians_filtered(<the 19 arguments>, antialiasing)` -> rasterize_gaussians_planes'
+6-tuple and `_C.rasterize_gaussians_backward_filtered(<rasterize_gaussians_backward_camera's 20
+arguments>, antialiasing)` -> its 11-tuple (`gsr_forward_filtered`, `gsr_backward_filtered`), behind
+`GaussianRasterizationSettings(antialiasing=True)`.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -57,7 +61,8 @@ from __future__ import annotations
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
                           rasterize_gaussians_backward, rasterize_gaussians_backward_camera,
-                          rasterize_gaussians_backward_planes,
+                          rasterize_gaussians_backward_filtered,
+                          rasterize_gaussians_backward_planes, rasterize_gaussians_filtered,
                           rasterize_gaussians_planes, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "

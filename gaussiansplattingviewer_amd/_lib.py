@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
+    "gsr_forward_filtered", "gsr_backward_filtered",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -115,6 +116,11 @@ class GsrCameraGradients(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in CAMERA_GRADIENT_NAMES]
 
 
+class GsrFilterSettings(ctypes.Structure):
+    """gsr_filter_settings: gsr_forward_filtered's and gsr_backward_filtered's option."""
+    _fields_ = [("antialiasing", ctypes.c_int32)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -182,6 +188,23 @@ def _declare(lib: ctypes.CDLL) -> None:
                                             ctypes.POINTER(GsrCameraGradients),
                                             ctypes.POINTER(GsrGradients), vp]
         lib.gsr_backward_camera.restype = i32
+    # (an older build of ABI 4 loaded through GSR_LIB lacks them: filtered_fns() says so)
+    if hasattr(lib, "gsr_forward_filtered"):
+        lib.gsr_forward_filtered.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                             ctypes.POINTER(GsrRasterSettings),
+                                             ctypes.POINTER(GsrOutputs),
+                                             ctypes.POINTER(GsrDepthOutputs),
+                                             ctypes.POINTER(GsrSurfaceOutputs),
+                                             ctypes.POINTER(GsrFilterSettings), vp]
+        lib.gsr_forward_filtered.restype = i32
+        lib.gsr_backward_filtered.argtypes = [vp, ctypes.POINTER(GsrGaussians),
+                                              ctypes.POINTER(GsrRasterSettings),
+                                              ctypes.POINTER(GsrBackwardInputs),
+                                              ctypes.POINTER(GsrPlaneGradients),
+                                              ctypes.POINTER(GsrCameraGradients),
+                                              ctypes.POINTER(GsrFilterSettings),
+                                              ctypes.POINTER(GsrGradients), vp]
+        lib.gsr_backward_filtered.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -278,6 +301,18 @@ def backward_camera_fn(lib: ctypes.CDLL):
             "campos need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
             "additive)")
     return fn
+
+
+def filtered_fns(lib: ctypes.CDLL):
+    """(gsr_forward_filtered, gsr_backward_filtered) of a loaded library; RuntimeError if that
+    build does not have them."""
+    fw = getattr(lib, "gsr_forward_filtered", None)
+    bw = getattr(lib, "gsr_backward_filtered", None)
+    if fw is None or bw is None:
+        raise RuntimeError(
+            f"{LIB_PATH} has no gsr_forward_filtered / gsr_backward_filtered: antialiasing needs "
+            "a libgsr.so built from this tree (include/gsr.h declares them; ABI 4, additive)")
+    return fw, bw
 
 
 def check(rc: int, what: str) -> int:

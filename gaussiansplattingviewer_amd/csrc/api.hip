@@ -1165,7 +1165,8 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
             gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth,
-            bool no_blend = false, const gsr_surface_outputs *surface = nullptr) {
+            bool no_blend = false, const gsr_surface_outputs *surface = nullptr,
+            bool antialiasing = false) {
     Frame f;
     ctx->last.valid = false;
     // the planes of the call, set again after every setup_frame
@@ -1173,6 +1174,10 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
         if (surface) f.median_depth = surface->median_depth, f.median_id = surface->median_id;
         f.no_blend = no_blend;
+        // gsr_forward_filtered: the call's, not the context's; the preprocess runs outside the
+        // recorded chains (which read none of its opacity-dependent arguments), so plain and
+        // antialiased frames share their graphs
+        f.pa.antialiasing = antialiasing ? 1 : 0;
     };
     GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
     planes();
@@ -1482,6 +1487,28 @@ int gsr_forward_surface(gsr_context *ctx, const gsr_gaussians *g, const gsr_rast
                    surface);
 }
 
+// 0 or 1 from a gsr_filter_settings (NULL: 0), -1 for anything else.
+static int filter_antialiasing(const gsr_filter_settings *filter) {
+    if (!filter) return 0;
+    return filter->antialiasing == 0 || filter->antialiasing == 1 ? filter->antialiasing : -1;
+}
+
+int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                         gsr_outputs *out, const gsr_depth_outputs *depth,
+                         const gsr_surface_outputs *surface, const gsr_filter_settings *filter,
+                         void *stream) {
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_forward_filtered: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    if (!aa) return gsr_forward_surface(ctx, g, st, out, depth, surface, stream);
+    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
+    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth, false,
+                   surface, true);
+}
+
 int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                 gsr_outputs *out, void *stream) {
     return gsr_forward_shaded(ctx, g, st, out, GSR_SHADE_SPLAT, stream);
@@ -1499,7 +1526,7 @@ int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
 static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                     const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
                     const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
-                    const std::string &fn) {
+                    const std::string &fn, bool antialiasing = false) {
     if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
     if (st->tile_row_begin != 0 || st->tile_row_end != 0)
         return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
@@ -1563,7 +1590,8 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     };
     GSR_TRY(mark(0));
     ctx->tight = ctx->graphs = ctx->timing = 0;
-    const int rc = forward(ctx, g, st, &out, s, GSR_SHADE_SPLAT, nullptr, true);
+    const int rc = forward(ctx, g, st, &out, s, GSR_SHADE_SPLAT, nullptr, true, nullptr,
+                           antialiasing);
     ctx->tight = tight, ctx->graphs = graphs, ctx->timing = timing;
     GSR_TRY(rc);
 
@@ -1636,20 +1664,23 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     pb.dL_dscales = gr->dL_dscales;
     pb.dL_drotations = gr->dL_drotations;
     pb.dL_dcov3D = gr->dL_dcov3D;
+    // gsr_backward_filtered: the antialiased twins, which also read the opacities
+    const float *const aa_op = antialiasing ? g->opacities : nullptr;
     if (camera) {
         // (an empty list leaves the rows zero: every product, and so every sum, is 0)
         const GsrCameraBwdArgs ca{ctx->cam_partials.get(), cam->dL_dviewmatrix,
                                   cam->dL_dprojmatrix, cam->dL_dcampos};
-        GSR_HIP(gsr_launch_preprocess_bwd_camera(pb, planes, planes ? dL_ddepths : nullptr, ca, s),
+        GSR_HIP(gsr_launch_preprocess_bwd_camera(pb, planes, planes ? dL_ddepths : nullptr, ca, s,
+                                                 aa_op),
                 "per-Gaussian backward launch");
         if (!planes && dL_ddepths)
             GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
                     "hipMemsetAsync(dL_ddepths)");
     } else if (planes) {
-        GSR_HIP(gsr_launch_preprocess_bwd_planes(pb, dL_ddepths, s),
+        GSR_HIP(gsr_launch_preprocess_bwd_planes(pb, dL_ddepths, s, aa_op),
                 "per-Gaussian backward launch");
     } else {
-        GSR_HIP(gsr_launch_preprocess_bwd(pb, s), "per-Gaussian backward launch");
+        GSR_HIP(gsr_launch_preprocess_bwd(pb, s, aa_op), "per-Gaussian backward launch");
         if (dL_ddepths)  // no plane gradient: nothing reaches the features
             GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
                     "hipMemsetAsync(dL_ddepths)");
@@ -1674,6 +1705,18 @@ int gsr_backward_camera(gsr_context *ctx, const gsr_gaussians *g, const gsr_rast
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         const gsr_camera_gradients *camera, gsr_gradients *gr, void *stream) {
     return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_camera");
+}
+
+int gsr_backward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                          gsr_gradients *gr, void *stream) {
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_backward_filtered: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    if (!aa) return gsr_backward_camera(ctx, g, st, in, planes, camera, gr, stream);
+    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_filtered", true);
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

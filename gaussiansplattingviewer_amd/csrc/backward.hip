@@ -30,6 +30,10 @@
 //    (rows of 16 lanes by DPP, the 16 rows through LDS), one word per sum and block; the finish
 //    adds the blocks in double.  No atomics.  Without the flag the two kernels above compile as
 //    before (profiles/backward_camera_resources.txt).
+//  * k_preprocess_bwd_aa, ..._planes_aa, ..._camera_aa, ..._planes_camera_aa -- the per-Gaussian
+//    body with kAA set (gsr_backward_filtered): the antialiased forward's opacity
+//    factor and its gradient through the 2D covariance.  The four kernels above compile as
+//    before (profiles/antialias_resources.txt).
 #include "gsr_internal.h"
 
 #include <type_traits>
@@ -399,21 +403,24 @@ __global__ __launch_bounds__(256) void k_camera_finish(const float *partials, ui
 // the camera pair keeps the camera's factors (the text as a lambda's body: its early returns leave
 // the lambda, not the kernel) and sums them over the block.
 __global__ __launch_bounds__(256) void k_preprocess_bwd(const GsrPreprocessBwdArgs a) {
-    constexpr bool kPlanes = false, kCamera = false;
+    constexpr bool kPlanes = false, kCamera = false, kAA = false;
     [[maybe_unused]] float *const dL_ddepths = nullptr;
+    [[maybe_unused]] const float *const opacities = nullptr;
     [[maybe_unused]] CameraTerms cam;
 #include "backward_gaussian.inc"
 }
 __global__ __launch_bounds__(256) void k_preprocess_bwd_planes(const GsrPreprocessBwdArgs a,
                                                                float *dL_ddepths) {
-    constexpr bool kPlanes = true, kCamera = false;
+    constexpr bool kPlanes = true, kCamera = false, kAA = false;
+    [[maybe_unused]] const float *const opacities = nullptr;
     [[maybe_unused]] CameraTerms cam;
 #include "backward_gaussian.inc"
 }
 __global__ __launch_bounds__(256) void k_preprocess_bwd_camera(const GsrPreprocessBwdArgs a,
                                                                float *partials) {
-    constexpr bool kPlanes = false, kCamera = true;
+    constexpr bool kPlanes = false, kCamera = true, kAA = false;
     [[maybe_unused]] float *const dL_ddepths = nullptr;
+    [[maybe_unused]] const float *const opacities = nullptr;
     CameraTerms cam{};
     [&] {
 #include "backward_gaussian.inc"
@@ -423,7 +430,45 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_camera(const GsrPreproce
 __global__ __launch_bounds__(256) void k_preprocess_bwd_planes_camera(const GsrPreprocessBwdArgs a,
                                                                       float *dL_ddepths,
                                                                       float *partials) {
-    constexpr bool kPlanes = true, kCamera = true;
+    constexpr bool kPlanes = true, kCamera = true, kAA = false;
+    [[maybe_unused]] const float *const opacities = nullptr;
+    CameraTerms cam{};
+    [&] {
+#include "backward_gaussian.inc"
+    }();
+    camera_block_sums(cam, partials);
+}
+
+// The same four with kAA set (gsr_backward_filtered, antialiasing): the effective opacity's
+// factor s and its gradient through the 2D covariance; `opacities` is the forward's input.
+__global__ __launch_bounds__(256) void k_preprocess_bwd_aa(const GsrPreprocessBwdArgs a,
+                                                           const float *opacities) {
+    constexpr bool kPlanes = false, kCamera = false, kAA = true;
+    [[maybe_unused]] float *const dL_ddepths = nullptr;
+    [[maybe_unused]] CameraTerms cam;
+#include "backward_gaussian.inc"
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_planes_aa(const GsrPreprocessBwdArgs a,
+                                                                  float *dL_ddepths,
+                                                                  const float *opacities) {
+    constexpr bool kPlanes = true, kCamera = false, kAA = true;
+    [[maybe_unused]] CameraTerms cam;
+#include "backward_gaussian.inc"
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_camera_aa(const GsrPreprocessBwdArgs a,
+                                                                  float *partials,
+                                                                  const float *opacities) {
+    constexpr bool kPlanes = false, kCamera = true, kAA = true;
+    [[maybe_unused]] float *const dL_ddepths = nullptr;
+    CameraTerms cam{};
+    [&] {
+#include "backward_gaussian.inc"
+    }();
+    camera_block_sums(cam, partials);
+}
+__global__ __launch_bounds__(256) void k_preprocess_bwd_planes_camera_aa(
+    const GsrPreprocessBwdArgs a, float *dL_ddepths, float *partials, const float *opacities) {
+    constexpr bool kPlanes = true, kCamera = true, kAA = true;
     CameraTerms cam{};
     [&] {
 #include "backward_gaussian.inc"
@@ -449,37 +494,51 @@ hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneB
     return hipGetLastError();
 }
 
-hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &args, hipStream_t s) {
+hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &args, hipStream_t s,
+                                     const float *aa_opacities) {
     if (args.P == 0) return hipSuccess;
     GsrPreprocessBwdArgs a = args;
     a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
-    hipLaunchKernelGGL(k_preprocess_bwd, dim3((unsigned)gsr_preprocess_blocks(a.P)), dim3(256), 0,
-                       s, a);
+    const dim3 grid((unsigned)gsr_preprocess_blocks(a.P));
+    if (aa_opacities)
+        hipLaunchKernelGGL(k_preprocess_bwd_aa, grid, dim3(256), 0, s, a, aa_opacities);
+    else
+        hipLaunchKernelGGL(k_preprocess_bwd, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &args, float *dL_ddepths,
-                                            hipStream_t s) {
+                                            hipStream_t s, const float *aa_opacities) {
     if (args.P == 0) return hipSuccess;
     GsrPreprocessBwdArgs a = args;
     a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
-    hipLaunchKernelGGL(k_preprocess_bwd_planes, dim3((unsigned)gsr_preprocess_blocks(a.P)),
-                       dim3(256), 0, s, a, dL_ddepths);
+    const dim3 grid((unsigned)gsr_preprocess_blocks(a.P));
+    if (aa_opacities)
+        hipLaunchKernelGGL(k_preprocess_bwd_planes_aa, grid, dim3(256), 0, s, a, dL_ddepths,
+                           aa_opacities);
+    else
+        hipLaunchKernelGGL(k_preprocess_bwd_planes, grid, dim3(256), 0, s, a, dL_ddepths);
     return hipGetLastError();
 }
 
 hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &args, bool planes,
                                             float *dL_ddepths, const GsrCameraBwdArgs &c,
-                                            hipStream_t s) {
+                                            hipStream_t s, const float *aa_opacities) {
     if (args.P <= 0 || !c.partials || (!c.dL_dviewmatrix && !c.dL_dprojmatrix && !c.dL_dcampos))
         return hipErrorInvalidValue;
     GsrPreprocessBwdArgs a = args;
     a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
     const unsigned blocks = (unsigned)gsr_preprocess_blocks(a.P);
-    if (planes)
+    if (planes && aa_opacities)
+        hipLaunchKernelGGL(k_preprocess_bwd_planes_camera_aa, dim3(blocks), dim3(256), 0, s, a,
+                           dL_ddepths, c.partials, aa_opacities);
+    else if (aa_opacities)
+        hipLaunchKernelGGL(k_preprocess_bwd_camera_aa, dim3(blocks), dim3(256), 0, s, a,
+                           c.partials, aa_opacities);
+    else if (planes)
         hipLaunchKernelGGL(k_preprocess_bwd_planes_camera, dim3(blocks), dim3(256), 0, s, a,
                            dL_ddepths, c.partials);
     else

@@ -10,6 +10,12 @@
 // then the body of a lambda, so each `return` below leaves the lambda with cam's zeros or what
 // was set so far and every thread of the block reaches the reduction after it.  Without the flag
 // cam is not touched and the kernels compile as before.
+// kAA (the four k_preprocess_bwd*_aa kernels, gsr_backward_filtered): the forward's opacity was
+// o_eff = opacity s, s = sqrtf(fmaxf(0.000025f, rho)), rho = D0 / det with D0 the determinant
+// before the 0.3 dilation; gop is dL/do_eff.  dL_dopacity = gop s and, off the floor, dL/drho =
+// gop opacity / (2 s) joins the 2D covariance's gradient where the conic's becomes it.  Needs
+// `opacities` in scope.  Without the flag the four kernels compile as before
+// (profiles/antialias_resources.txt).
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.P) return;
     float *const sh_out = a.dL_dsh ? a.dL_dsh + idx * (int64_t)a.M * 3 : nullptr;
@@ -40,7 +46,8 @@
     // upstream's units: the gradient with respect to an offset added to the NDC centre
     const float gnx = gmx * (0.5f * (float)a.W), gny = gmy * (0.5f * (float)a.H);
     store3(a.dL_dmeans2D, idx, gnx, gny, 0.f);
-    if (a.dL_dopacity) a.dL_dopacity[idx] = gop;
+    if constexpr (!kAA)
+        if (a.dL_dopacity) a.dL_dopacity[idx] = gop;
     store3(a.dL_dcolors, idx, grgb[0], grgb[1], grgb[2]);
     store3(a.dL_dconic, idx, gca, gcb, gcc);
 
@@ -169,15 +176,32 @@
         VA0[i] = V[i][0] * A0[0] + V[i][1] * A0[1] + V[i][2] * A0[2];
         VA1[i] = V[i][0] * A1[0] + V[i][1] * A1[1] + V[i][2] * A1[2];
     }
-    const float ca = A0[0] * VA0[0] + A0[1] * VA0[1] + A0[2] * VA0[2] + 0.3f;
+    const float ca0 = A0[0] * VA0[0] + A0[1] * VA0[1] + A0[2] * VA0[2];  // before the dilation
+    const float ca = ca0 + 0.3f;
     const float cb = A0[0] * VA1[0] + A0[1] * VA1[1] + A0[2] * VA1[2];
-    const float cc = A1[0] * VA1[0] + A1[1] * VA1[1] + A1[2] * VA1[2] + 0.3f;
+    const float cc0 = A1[0] * VA1[0] + A1[1] * VA1[1] + A1[2] * VA1[2];
+    const float cc = cc0 + 0.3f;
     const float det = ca * cc - cb * cb;
     const float id2 = 1.0f / (det * det);
     // conic = (cc, -cb, ca) / det, det - ca cc = -cb^2
-    const float dca = (-cc * cc * gca + cb * cc * gcb - cb * cb * gcc) * id2;
-    const float dcc = (-cb * cb * gca + ca * cb * gcb - ca * ca * gcc) * id2;
-    const float dcb = (2.0f * cb * cc * gca - (ca * cc + cb * cb) * gcb + 2.0f * ca * cb * gcc) * id2;
+    float dca = (-cc * cc * gca + cb * cc * gcb - cb * cb * gcc) * id2;
+    float dcc = (-cb * cb * gca + ca * cb * gcb - ca * ca * gcc) * id2;
+    float dcb = (2.0f * cb * cc * gca - (ca * cc + cb * cb) * gcb + 2.0f * ca * cb * gcc) * id2;
+    if constexpr (kAA) {
+        const float det0 = ca0 * cc0 - cb * cb;
+        const float rho = det0 / det;
+        float s = sqrtf(0.000025f);
+        if (rho > 0.000025f) {  // off the floor (a gate): s = sqrt(rho)
+            s = sqrtf(rho);
+            const float grho = gop * opacities[idx] / (2.0f * s);
+            // rho = D0 / D: d/da' = (c' D - D0 c) / D^2, d/dc' = (a' D - D0 a) / D^2,
+            // d/db = -2 b (D - D0) / D^2 (b the one stored entry, as dcb)
+            dca += grho * (cc0 * det - det0 * cc) * id2;
+            dcc += grho * (ca0 * det - det0 * ca) * id2;
+            dcb += grho * (-2.0f * cb * (det - det0)) * id2;
+        }
+        if (a.dL_dopacity) a.dL_dopacity[idx] = gop * s;
+    }
     const float hb = 0.5f * dcb;  // each off-diagonal of the symmetric dL/dcov2
     // dL/dV = A^T G2 A (an off-diagonal of V stands for two entries: twice in dL/dcov3D)
     float GA0[3], GA1[3];  // G2 A

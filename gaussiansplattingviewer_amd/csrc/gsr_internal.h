@@ -128,8 +128,11 @@ __device__ __forceinline__ void compute_cov3d(float3 s, float mod, float4 q, flo
 
 // upstream forward.cu computeCov2D (twin: shaders/gau_vert.glsl:95-120).  `t` is the
 // view-space mean (transformPoint4x3(mean, viewmatrix), already computed by the caller).
+// pre (the antialiased preprocess, else NULL): the diagonal before the 0.3 dilation, a' and c'
+// ((a' + 0.3f) - 0.3f is not a'); the plain callers' code is what it was.
 __device__ __forceinline__ float3 compute_cov2d(float3 t, float fx, float fy, float tanfovx,
-                                                float tanfovy, const float c[6], const float *vm) {
+                                                float tanfovy, const float c[6], const float *vm,
+                                                float *pre = nullptr) {
     const float limx = 1.3f * tanfovx;
     const float limy = 1.3f * tanfovy;
     const float txtz = t.x / t.z;
@@ -145,6 +148,7 @@ __device__ __forceinline__ float3 compute_cov2d(float3 t, float fx, float fy, fl
     Mat3 Vt = mat3_transpose(Vrk);
     Mat3 A = mat3_mul(Tt, Vt);
     Mat3 cov = mat3_mul(A, T);
+    if (pre) pre[0] = cov.m[0][0], pre[1] = cov.m[1][1];
     cov.m[0][0] += 0.3f;
     cov.m[1][1] += 0.3f;
     return make_float3(cov.m[0][0], cov.m[0][1], cov.m[1][1]);
@@ -364,6 +368,9 @@ struct GsrPreprocessArgs {
     // optional debug outputs
     float *depths, *means2D, *conic_opacity, *rgb;
     uint32_t *tiles_touched;
+    // gsr_forward_filtered: 1 = the antialiased preprocess (k_preprocess_aa), whose record,
+    // cull data, spans and conic_opacity carry the effective opacity; the call's, not the context's
+    int antialiasing;
 };
 
 // k_preprocess blocks of 256 Gaussians: the count of GsrPreprocessArgs.block_pairs entries and
@@ -645,11 +652,15 @@ struct GsrPreprocessBwdArgs {
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dopacity, *dL_dcolors, *dL_dconic, *dL_dsh, *dL_dscales,
         *dL_drotations, *dL_dcov3D;
 };
-hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t s);
+// aa_opacities (each of the three launchers; NULL: the plain kernel): the forward's opacities
+// [P], with which the launch is the kernel's antialiased twin (k_preprocess_bwd*_aa) -- the rows'
+// word 5 is then dL/do_eff of gsr_forward_filtered's effective opacity.
+hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t s,
+                                     const float *aa_opacities = nullptr);
 // k_preprocess_bwd_planes: also reads word 9 of the rows, adds (vm[2], vm[6], vm[10]) times it to
 // dL_dmeans3D and writes it to dL_ddepths ([P], optional).
 hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &a, float *dL_ddepths,
-                                            hipStream_t s);
+                                            hipStream_t s, const float *aa_opacities = nullptr);
 // gsr_backward_camera (k_preprocess_bwd_camera / k_preprocess_bwd_planes_camera, then
 // k_camera_finish): the per-Gaussian backward, with the planes' term if `planes`, that also sums
 // the camera's 27 gradient entries over the Gaussians.  partials: workspace of
@@ -663,4 +674,4 @@ struct GsrCameraBwdArgs {
 };
 hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &a, bool planes,
                                             float *dL_ddepths, const GsrCameraBwdArgs &c,
-                                            hipStream_t s);
+                                            hipStream_t s, const float *aa_opacities = nullptr);

@@ -337,6 +337,10 @@ __device__ __forceinline__ void none_one(const GsrPreprocessArgs &a, int64_t idx
 // The second half: 2D covariance, conic, radius, tile rect, depth key, the blend's record (and
 // with tight binning the span word).  Returns the number of (Gaussian, strip tile) pairs of
 // Gaussian idx; tight_out: their number over the spans (without tight binning the same).
+// kAA (gsr_forward_filtered, antialiasing): the opacity of everything below -- the record, the
+// cull data and the spans, the conic_opacity extra -- is o_eff = opacity * sqrtf(fmaxf(0.000025f,
+// D0 / det)), D0 the determinant before the 0.3 dilation (include/gsr.h).  Nothing else moves.
+template <bool kAA>
 __device__ __forceinline__ uint32_t back_one(const GsrPreprocessArgs &a, int64_t idx,
                                              const Front &f, uint32_t &key_out,
                                              uint32_t &tight_out) {
@@ -348,8 +352,9 @@ __device__ __forceinline__ uint32_t back_one(const GsrPreprocessArgs &a, int64_t
     uint32_t key = 0xFFFFFFFFu;
     if (f.in_frustum) {
         const float3 p_view = f.p_view;
+        [[maybe_unused]] float pre[2];
         const float3 cov = compute_cov2d(p_view, a.focal_x, a.focal_y, a.tanfovx, a.tanfovy,
-                                         f.cov3d, a.viewmatrix);
+                                         f.cov3d, a.viewmatrix, kAA ? pre : nullptr);
         const float det = cov.x * cov.z - cov.y * cov.y;
         if (det != 0.0f) {
             const float det_inv = 1.f / det;
@@ -368,7 +373,11 @@ __device__ __forceinline__ uint32_t back_one(const GsrPreprocessArgs &a, int64_t
             // defines, its duplicateWithKeys skips radii <= 0 -- although get_rect of radius 0
             // still covers a tile; so a Gaussian with pairs always has a positive radius
             if (r_int > 0 && all_tiles != 0) {
-                const float opacity = f.opacity;
+                float opacity = f.opacity;
+                if constexpr (kAA) {
+                    const float det0 = pre[0] * pre[1] - cov.y * cov.y;
+                    opacity = opacity * sqrtf(fmaxf(0.000025f, det0 / det));
+                }
                 radius_out = r_int;
                 const uint32_t sy0 = max(rc.y0, a.row_begin), sy1 = min(rc.y1, a.row_end);
                 strip_tiles = sy1 > sy0 ? (rc.x1 - rc.x0) * (sy1 - sy0) : 0u;
@@ -425,13 +434,14 @@ struct SkipSmem {
 // K sizes the binning, bits(OR ^ AND) the depth sort's passes), and with a.block_kept (the
 // depth sort's compaction, strips) how many of its 256 Gaussians have pairs in the strip.
 // (A separate pass re-reading the rects and keys took 7 us at C3 and 42 us on a C4 strip.)
-template <bool kSkip>
-__global__ __launch_bounds__(256) void k_preprocess(const GsrPreprocessArgs a) {
+// (The body of the four kernels below; kAA: back_one's.)
+template <bool kSkip, bool kAA>
+__device__ __forceinline__ void preprocess_block(const GsrPreprocessArgs &a) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t key = 0xFFFFFFFFu;
     uint32_t pairs = 0u, tight = 0u;
     if (!kSkip) {
-        if (idx < a.P) pairs = back_one(a, idx, front_one(a, idx), key, tight);
+        if (idx < a.P) pairs = back_one<kAA>(a, idx, front_one(a, idx), key, tight);
     } else {
         __shared__ SkipSmem sk;
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -476,7 +486,7 @@ __global__ __launch_bounds__(256) void k_preprocess(const GsrPreprocessArgs a) {
             for (int i = 0; i < 6; ++i) g.cov3d[i] = sk.v[5 + i][t];
             g.opacity = sk.v[11][t];
             g.in_frustum = true;
-            pairs = back_one(a, (int64_t)sk.idx[t], g, key, tight);
+            pairs = back_one<kAA>(a, (int64_t)sk.idx[t], g, key, tight);
         }
     }
     const bool kept = pairs != 0u;  // has pairs in the strip <=> its depth key is kept
@@ -513,6 +523,16 @@ __global__ __launch_bounds__(256) void k_preprocess(const GsrPreprocessArgs a) {
                        min(min(s_red[2][0], s_red[2][1]), min(s_red[2][2], s_red[2][3])));
         if (a.block_kept) a.block_kept[blockIdx.x] = s_red[3][0] + s_red[3][1] + s_red[3][2] + s_red[3][3];
     }
+}
+
+template <bool kSkip>
+__global__ __launch_bounds__(256) void k_preprocess(const GsrPreprocessArgs a) {
+    preprocess_block<kSkip, false>(a);
+}
+// The antialiased preprocess (GsrPreprocessArgs.antialiasing), under a name of its own.
+template <bool kSkip>
+__global__ __launch_bounds__(256) void k_preprocess_aa(const GsrPreprocessArgs a) {
+    preprocess_block<kSkip, true>(a);
 }
 
 // One block, on the second stream after the preprocess (the kernel boundary makes its stores
@@ -724,7 +744,11 @@ inline unsigned grid_for(int64_t n) { return (unsigned)gsr_preprocess_blocks(n);
 
 hipError_t gsr_launch_preprocess(const GsrPreprocessArgs &a, hipStream_t s) {
     if (a.P == 0) return hipSuccess;
-    if (a.strip_skip)
+    if (a.antialiasing && a.strip_skip)
+        hipLaunchKernelGGL(k_preprocess_aa<true>, dim3(grid_for(a.P)), dim3(256), 0, s, a);
+    else if (a.antialiasing)
+        hipLaunchKernelGGL(k_preprocess_aa<false>, dim3(grid_for(a.P)), dim3(256), 0, s, a);
+    else if (a.strip_skip)
         hipLaunchKernelGGL(k_preprocess<true>, dim3(grid_for(a.P)), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(k_preprocess<false>, dim3(grid_for(a.P)), dim3(256), 0, s, a);

@@ -35,6 +35,12 @@
 //       -> its 8-tuple, then dL_dviewmatrix [4,4], dL_dprojmatrix [4,4], dL_dcampos [3]
 //     this package's own: gsr_backward_camera.  The two matrices' gradients are in the inputs'
 //     layout (the 16 floats of the input, viewed (4, 4)).
+//   _C.rasterize_gaussians_filtered(<rasterize_gaussians' 19 arguments>, antialiasing)
+//       -> rasterize_gaussians_planes' 6-tuple
+//   _C.rasterize_gaussians_backward_filtered(<rasterize_gaussians_backward_camera's 20
+//                                            arguments>, antialiasing) -> its 11-tuple
+//     this package's own (GaussianRasterizationSettings.antialiasing): gsr_forward_filtered and
+//     gsr_backward_filtered, the effective opacity of the 0.3-pixel dilation's compensation.
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -97,7 +103,7 @@ Forward6 forward_impl(
     double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
     int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
-    bool prefiltered, bool debug, int64_t shading, Planes *planes) {
+    bool prefiltered, bool debug, int64_t shading, Planes *planes, bool antialiasing = false) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -159,7 +165,9 @@ Forward6 forward_impl(
                 out.final_T = planes->final_T.data_ptr<float>();
                 gsr_depth_outputs d{planes->depth_map.data_ptr<float>(),
                                     planes->inv_depth_map.data_ptr<float>()};
-                rc = gsr_forward_depth(ctx, &g, &st, &out, &d, s);
+                const gsr_filter_settings fs{antialiasing ? 1 : 0};
+                rc = antialiasing ? gsr_forward_filtered(ctx, &g, &st, &out, &d, nullptr, &fs, s)
+                                  : gsr_forward_depth(ctx, &g, &st, &out, &d, s);
             } else {
                 rc = gsr_forward_shaded(ctx, &g, &st, &out, (int32_t)shading, s);
             }
@@ -227,7 +235,7 @@ Backward8 backward_impl(
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy,
     const torch::Tensor &dL_dout_color, const torch::Tensor &sh, int64_t degree,
     const torch::Tensor &campos, bool debug, const torch::Tensor &opacities,
-    const torch::Tensor *planes, torch::Tensor *camera = nullptr) {
+    const torch::Tensor *planes, torch::Tensor *camera = nullptr, bool antialiasing = false) {
     if (means3D.ndimension() != 2 || means3D.size(1) != 3)
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -318,7 +326,12 @@ Backward8 backward_impl(
                 const gsr_camera_gradients cg{camera[0].data_ptr<float>(),
                                               camera[1].data_ptr<float>(),
                                               camera[2].data_ptr<float>()};
-                rc = gsr_backward_camera(ctx, &g, &st, &in, planes ? &pg : nullptr, &cg, &gr, s);
+                const gsr_filter_settings fs{antialiasing ? 1 : 0};
+                rc = antialiasing
+                         ? gsr_backward_filtered(ctx, &g, &st, &in, planes ? &pg : nullptr, &cg,
+                                                 &fs, &gr, s)
+                         : gsr_backward_camera(ctx, &g, &st, &in, planes ? &pg : nullptr, &cg, &gr,
+                                               s);
             } else {
                 rc = planes ? gsr_backward_planes(ctx, &g, &st, &in, &pg, &gr, s)
                             : gsr_backward(ctx, &g, &st, &in, &gr, s);
@@ -382,6 +395,44 @@ rasterize_gaussians_backward_camera(
     return std::tuple_cat(g, std::make_tuple(camera[0], camera[1], camera[2]));
 }
 
+// rasterize_gaussians_planes with the antialiasing option (gsr_forward_filtered).
+Forward6 rasterize_gaussians_filtered(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
+    int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
+    bool prefiltered, bool debug, bool antialiasing) {
+    Planes pl;
+    Forward6 r = forward_impl(background, means3D, colors, opacity, scales, rotations,
+                              scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                              tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                              debug, GSR_SHADE_SPLAT, &pl, antialiasing);
+    return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), pl.depth_map,
+                           pl.inv_depth_map, pl.final_T);
+}
+
+// rasterize_gaussians_backward_camera with the antialiasing option (gsr_backward_filtered).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor>
+rasterize_gaussians_backward_filtered(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T, bool antialiasing) {
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    torch::Tensor camera[3];
+    const Backward8 g = backward_impl(background, means3D, colors, scales, rotations,
+                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                      tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, debug,
+                                      opacities, planes, camera, antialiasing);
+    return std::tuple_cat(g, std::make_tuple(camera[0], camera[1], camera[2]));
+}
+
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
                            const torch::Tensor &projmatrix) {
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -436,6 +487,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians_backward_camera", &rasterize_gaussians_backward_camera,
           "rasterize_gaussians_backward_planes' 20 arguments -> its 8-tuple, then dL_dviewmatrix "
           "(4, 4), dL_dprojmatrix (4, 4), dL_dcampos (3)");
+    m.def("rasterize_gaussians_filtered", &rasterize_gaussians_filtered,
+          "rasterize_gaussians' 19 arguments, then antialiasing -> rasterize_gaussians_planes' "
+          "6-tuple (gsr_forward_filtered)");
+    m.def("rasterize_gaussians_backward_filtered", &rasterize_gaussians_backward_filtered,
+          "rasterize_gaussians_backward_camera's 20 arguments, then antialiasing -> its 11-tuple "
+          "(gsr_backward_filtered)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -16,7 +16,9 @@ composite (`gsr_backward`, include/gsr.h), as upstream's does for training code.
 `GaussianRasterizationSettings.depth_maps` the rasterizer also returns depth_map, inv_depth_map and
 final_T, differentiable too (`_RasterizeGaussiansPlanes`, `gsr_backward_planes`).  When
 `viewmatrix`, `projmatrix` or `campos` of the settings requires a gradient, the camera gets one as
-well (`_RasterizeGaussiansCamera`, `gsr_backward_camera`).
+well (`_RasterizeGaussiansCamera`, `gsr_backward_camera`).  `GaussianRasterizationSettings(...,
+antialiasing=True)` (upstream's keyword) switches all three Functions to the compensated opacity
+(`gsr_forward_filtered` / `gsr_backward_filtered`).
 """
 from __future__ import annotations
 
@@ -53,20 +55,33 @@ class GaussianRasterizationSettings(_SettingsTuple):
     planes of gsr_forward_depth / gsr_outputs, differentiable like the image
     (gsr_backward_planes); the splat composite only.  It is an attribute of the instance, not an
     element of the tuple: `_fields`, `_field_defaults`, unpacking and comparison stay those of the
-    13-field tuple that callers and tests of the shading rely on; `_replace` carries it."""
+    13-field tuple that callers and tests of the shading rely on; `_replace` carries it.
+
+    antialiasing (upstream's name; keyword only here, default False, an attribute like
+    depth_maps): the Mip-Splatting compensation of the 0.3-pixel dilation -- every Gaussian is
+    drawn with opacity * sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))), forward and
+    backward (gsr_forward_filtered / gsr_backward_filtered in include/gsr.h).  The splat composite
+    only: RuntimeError with a shading.  Upstream's positional place for it is `shading` here."""
     depth_maps = False  # (instances made by _make)
+    antialiasing = False
 
     def __new__(cls, *args, depth_maps=False, **kwargs):
+        # (antialiasing travels in kwargs: the parameter list ends at depth_maps, as
+        # tests/test_plane_grad_reference.py pins it)
+        antialiasing = kwargs.pop("antialiasing", False)
         if len(args) == len(cls._fields) + 1:  # given by position, after shading
             *args, depth_maps = args
         self = super().__new__(cls, *args, **kwargs)
         self.depth_maps = bool(depth_maps)
+        self.antialiasing = bool(antialiasing)
         return self
 
     def _replace(self, **kwargs):
         depth_maps = kwargs.pop("depth_maps", self.depth_maps)
+        antialiasing = kwargs.pop("antialiasing", self.antialiasing)
         new = super()._replace(**kwargs)
         new.depth_maps = bool(depth_maps)
+        new.antialiasing = bool(antialiasing)
         return new
 
 
@@ -102,7 +117,8 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                                scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx,
                                tanfovy, image_height, image_width, sh, degree, campos, prefiltered,
                                debug, *, tile_rows=None, extras=(), stream=None, slot=0,
-                               out_color=None, radii=True, shading=0) -> ForwardResult:
+                               out_color=None, radii=True, shading=0,
+                               antialiasing=False) -> ForwardResult:
     """Same arguments, order and validation as upstream `_C.rasterize_gaussians`.
 
     Extensions (keyword-only, for the strip partition and the parity tests):
@@ -124,7 +140,11 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                    (ForwardResult.radii is None); Gaussians whose footprint bound misses the
                    strip skip the per-Gaussian work (a multi-GPU strip rank needs its image only);
       shading   -- _lib.GSR_SHADE_*: 0 the splat composite, 1 billboard, 2 flat ball, 3 gaussian
-                   ball (the GL backend's shadings, gsr_forward_shaded in include/gsr.h).
+                   ball (the GL backend's shadings, gsr_forward_shaded in include/gsr.h);
+      antialiasing -- True: the effective opacity of the 0.3-pixel dilation's compensation in
+                   place of the opacity (gsr_forward_filtered in include/gsr.h; the extra
+                   conic_opacity[:, 3] is then that opacity).  Splat composite only: RuntimeError
+                   with a shading.  False is the call without the argument.
     """
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -139,6 +159,9 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     if surface_planes and shading != _lib.GSR_SHADE_SPLAT:
         raise RuntimeError("median_depth / median_id come from the splat composite: not "
                            f"available with shading {shading}")
+    if antialiasing and shading != _lib.GSR_SHADE_SPLAT:
+        raise RuntimeError("antialiasing belongs to the splat composite: not available with "
+                           f"shading {shading}")
     device = _device_of(means3D)
     dev_index = device.index if device.index is not None else torch.cuda.current_device()
     P = int(means3D.size(0))
@@ -221,7 +244,16 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     with torch.cuda.device(dev_index):
-        if surface_planes:
+        if antialiasing:
+            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
+            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
+            _lib.check(_lib.filtered_fns(lib)[0](
+                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
+                ctypes.byref(planes) if depth_planes else None,
+                ctypes.byref(surface) if surface_planes else None,
+                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing))),
+                ctypes.c_void_p(stream)), "gsr_forward_filtered")
+        elif surface_planes:
             planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
             surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
             _lib.check(_lib.forward_surface_fn(lib)(
@@ -248,7 +280,8 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         tanfovx, tanfovy, dL_dout_color, sh, degree, campos,
                                         debug=False, *, conic=False, stream=None, slot=0,
                                         dL_ddepth_map=None, dL_dinv_depth_map=None,
-                                        dL_dfinal_T=None, depths=False, camera=False) -> dict:
+                                        dL_dfinal_T=None, depths=False, camera=False,
+                                        antialiasing=False) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -261,7 +294,10 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     dL_ddepths (P,), dL/dz through the features z and 1 / z only.
 
     camera=True: the call is `gsr_backward_camera` and adds dL_dviewmatrix (4, 4), dL_dprojmatrix
-    (4, 4), both in the inputs' (column-major) layout, and dL_dcampos (3,)."""
+    (4, 4), both in the inputs' (column-major) layout, and dL_dcampos (3,).
+
+    antialiasing=True: the call is `gsr_backward_filtered`, the backward of the forward with the
+    same argument, with whatever of the planes and the camera is asked for."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
@@ -333,7 +369,18 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     with torch.cuda.device(dev_index):
-        if camera:
+        if antialiasing:
+            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
+                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
+            cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
+            _lib.check(_lib.filtered_fns(lib)[1](
+                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
+                ctypes.byref(planes) if plane_grads or depths else None,
+                ctypes.byref(cg) if camera else None,
+                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing))),
+                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_filtered")
+            grads.update(cam)
+        elif camera:
             planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
                                             dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
             cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
@@ -419,11 +466,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         # debug (upstream __init__.py): the arguments are copied to the host first, and a
         # forward that raises leaves them in SNAPSHOT_FILE for replay_snapshot()
         cpu_args = _cpu_copy(args) if rs.debug else None
+        if rs.antialiasing and rs.shading:
+            raise RuntimeError("antialiasing belongs to the splat composite: not available with "
+                               f"shading {rs.shading}")
         try:
             if not _lib._native_shares_library():
                 # GSR_LIB (an A/B build): `_C` links the in-tree library, so render by ctypes
-                num_rendered, color, radii, _ = rasterize_gaussians_native(*args,
-                                                                           shading=rs.shading)
+                num_rendered, color, radii, _ = rasterize_gaussians_native(
+                    *args, shading=rs.shading, antialiasing=rs.antialiasing)
+            elif rs.antialiasing:  # (the planes it also returns are dropped)
+                num_rendered, color, radii, *_ = _C.rasterize_gaussians_filtered(*args, True)
             elif rs.shading:  # upstream's 19 arguments and the shading
                 num_rendered, color, radii, geom, binning, img = \
                     _C.rasterize_gaussians_shaded(*args, int(rs.shading))
@@ -458,11 +510,19 @@ class _RasterizeGaussians(torch.autograd.Function):
             g = rasterize_gaussians_backward_native(
                 rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
                 cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
-                rs.sh_degree, rs.campos, rs.debug)
+                rs.sh_degree, rs.campos, rs.debug, antialiasing=rs.antialiasing)
             z = lambda n: g.get(n)  # noqa: E731
             d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
                 z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
                 z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
+        elif rs.antialiasing:  # (the camera's three it also returns are dropped)
+            from . import _C
+            e = torch.empty(0)
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, *_ = \
+                _C.rasterize_gaussians_backward_filtered(
+                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
+                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
+                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug, grad_color, e, e, e, True)
         else:
             from . import _C
             e = torch.empty(0)
@@ -504,9 +564,13 @@ class _RasterizeGaussiansPlanes(torch.autograd.Function):
                 rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, none(sh), rs.sh_degree,
                 rs.campos, rs.prefiltered, rs.debug)
         if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
-            res = rasterize_gaussians_native(*args, extras=PLANE_NAMES)
+            res = rasterize_gaussians_native(*args, extras=PLANE_NAMES,
+                                             antialiasing=rs.antialiasing)
             color, radii = res.color, res.radii
             planes = tuple(res.extras[n] for n in PLANE_NAMES)
+        elif rs.antialiasing:
+            from . import _C
+            _, color, radii, *planes = _C.rasterize_gaussians_filtered(*args, True)
         else:
             from . import _C
             _, color, radii, *planes = _C.rasterize_gaussians_planes(*args)
@@ -530,11 +594,20 @@ class _RasterizeGaussiansPlanes(torch.autograd.Function):
                 rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
                 cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
                 rs.sh_degree, rs.campos, rs.debug, dL_ddepth_map=grads[1],
-                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3])
+                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], antialiasing=rs.antialiasing)
             z = lambda n: g.get(n)  # noqa: E731
             d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
                 z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
                 z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
+        elif rs.antialiasing:  # (the camera's three it also returns are dropped)
+            from . import _C
+            e = torch.empty(0)
+            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, *_ = \
+                _C.rasterize_gaussians_backward_filtered(
+                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
+                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
+                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug,
+                    *(e if t is None else t for t in grads), True)
         else:
             from . import _C
             e = torch.empty(0)
@@ -599,7 +672,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
                 cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
                 rs.sh_degree, campos, rs.debug, dL_ddepth_map=grads[1],
-                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], camera=True)
+                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], camera=True,
+                antialiasing=rs.antialiasing)
             z = lambda n: g.get(n)  # noqa: E731
             (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
              d_proj, d_campos) = (
@@ -611,11 +685,13 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
             e = torch.empty(0)
             as_dev = lambda t: _as_dev(t.detach(), means3D.device, "")  # noqa: E731
             (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
-             d_proj, d_campos) = _C.rasterize_gaussians_backward_camera(
+             d_proj, d_campos) = (
+                _C.rasterize_gaussians_backward_filtered if rs.antialiasing
+                else _C.rasterize_gaussians_backward_camera)(
                 rs.bg, means3D, colors_precomp, opacities, scales, rotations,
                 rs.scale_modifier, cov3Ds, as_dev(viewmatrix), as_dev(projmatrix), rs.tanfovx,
                 rs.tanfovy, sh, rs.sh_degree, as_dev(campos), rs.debug,
-                *(e if t is None else t for t in grads))
+                *(e if t is None else t for t in grads), *((True,) if rs.antialiasing else ()))
         has = lambda t: t.numel() != 0  # noqa: E731
         need = ctx.needs_input_grad
         like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731

@@ -82,15 +82,16 @@ def gaus_hip_from_cpu(gau, device="cuda") -> GaussianDataHIP:
 
 
 class _RendererOptions(type):
-    """HIPRenderer(w, h, ..., depth_maps=False, surface_maps=False): the keywords are taken at
-    construction, here, because `__init__`'s parameter list is pinned as it stands
+    """HIPRenderer(w, h, ..., depth_maps=False, surface_maps=False, antialiasing=False): the
+    keywords are taken at construction, here, because `__init__`'s parameter list is pinned as it stands
     (tests/test_shading_reference.py test_python_api_carries_the_shading compares it name for
     name)."""
 
-    def __call__(cls, *args, depth_maps=False, surface_maps=False, **kw):
+    def __call__(cls, *args, depth_maps=False, surface_maps=False, antialiasing=False, **kw):
         r = super().__call__(*args, **kw)
         r.depth_maps = bool(depth_maps)
         r.surface_maps = bool(surface_maps)
+        r.antialiasing = bool(antialiasing)
         return r
 
 
@@ -107,7 +108,12 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
     pass (gsr_forward_surface) in self.median_depth (float32) / self.median_id (int32), (rows, W):
     the view-space z and the Gaussian id of the splat at which the pixel's transmittance crosses
     0.5, 0.0 / -1 where nothing does; None under a GL shading.  pick(x, y) reads one id back.
-    Independent of depth_maps; renders through ctypes like it.  False: nothing changes."""
+    Independent of depth_maps; renders through ctypes like it.  False: nothing changes.
+
+    antialiasing (keyword, default False): draw() renders the splat composite with the
+    compensated opacity of a scene trained with upstream's --antialiasing
+    (GaussianRasterizationSettings.antialiasing, gsr_forward_filtered); the GL shadings have no
+    such option and render as without it.  Renders through ctypes.  False: nothing changes."""
 
     # GL render_mod -> gsr_forward_shaded's shading (gau_frag.glsl:15-38)
     GL_SHADINGS = {-2: _lib.GSR_SHADE_BILLBOARD, -3: _lib.GSR_SHADE_FLAT_BALL,
@@ -119,6 +125,7 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
         self.depth_maps = False  # (set by the constructor's depth_maps keyword)
         self.depth_map = self.inv_depth_map = self.final_T = None
         self.surface_maps = False  # (set by the constructor's surface_maps keyword)
+        self.antialiasing = False  # (set by the constructor's antialiasing keyword)
         self.median_depth = self.median_id = None
         self.device = torch.device(device)
         self.raster_settings = {
@@ -226,8 +233,9 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
             settings["sh_degree"] = 0
         rs = GaussianRasterizationSettings(**settings)
         planes = {}
+        aa = self.antialiasing and not rs.shading
         with torch.no_grad():
-            if self.depth_maps or self.surface_maps:
+            if self.depth_maps or self.surface_maps or aa:
                 extras = ()
                 if self.depth_maps and not rs.shading:
                     extras += ("depth_map", "inv_depth_map", "final_T")
@@ -237,7 +245,7 @@ class HIPRenderer(GaussianRenderBase, metaclass=_RendererOptions):
                     rs.bg, g.xyz, colors, g.opacity, g.scale, g.rot, rs.scale_modifier, None,
                     rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
                     rs.image_width, shs, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug,
-                    tile_rows=self.tile_rows, shading=rs.shading, extras=extras)
+                    tile_rows=self.tile_rows, shading=rs.shading, extras=extras, antialiasing=aa)
                 img, radii, planes = res.color, res.radii, res.extras
             elif self.tile_rows is None:
                 img, radii = GaussianRasterizer(raster_settings=rs)(

@@ -364,6 +364,63 @@ typedef struct {
 int gsr_backward_camera(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         const gsr_camera_gradients *camera, gsr_gradients *grads, void *stream);
+
+/* gsr_forward_surface and gsr_backward_camera with the antialiasing option of upstream's
+ * GaussianRasterizationSettings(antialiasing=...): the Mip-Splatting compensation of the 0.3-pixel
+ * screen-space dilation.  (Additive to ABI 4; no existing struct changes layout.)
+ * Every Gaussian's 2D covariance gets + 0.3 I (computeCov2D); without the option the opacity stays
+ * what it was, so a splat much smaller than a pixel is drawn with far more energy than it has.
+ * With (a', b, c') the 2D covariance before the dilation, h = 0.3f, a = a' + h, c = c' + h (the
+ * values the conic is built from), all in float32 and in this order:
+ *     D0  = a' * c' - b * b          (before the dilation)
+ *     D   = a  * c  - b * b          (the det the conic divides by)
+ *     rho = D0 / D
+ *     s   = sqrtf(fmaxf(0.000025f, rho))
+ *     o_eff = opacity * s
+ * With antialiasing == 1, o_eff takes the place of opacity everywhere downstream of the
+ * preprocess: the blend's record, the conic_opacity output (its fourth component, as upstream),
+ * the cull data and the span words (tight binning cuts to the alpha >= 1/255 ellipse of the
+ * effective opacity) and the blend cull.  Nothing else moves: radii, rects, tiles_touched,
+ * num_rendered, the depth keys, means2D, the conic's three components and rgb are the plain
+ * forward's bits.  Consequences:
+ *   - identity: an antialiased forward is, bit for bit in every output (image, final_T, n_contrib,
+ *     the depth and the median planes), the plain forward of the same scene whose opacities are
+ *     the antialiased run's conic_opacity[:, 3] -- except conic_opacity[:, 3] itself, which the
+ *     plain run passes through;
+ *   - the tight lists of an antialiased frame are in-order subsequences of the plain frame's;
+ *     num_rendered is equal;
+ *   - the floor is a gate: rho <= 0.000025f (which covers D0 <= 0 by rounding, a zero
+ *     cov3D_precomp and NaN) gives s = sqrtf(0.000025f);
+ *   - the option belongs to the call, not to the context: a plain frame after an antialiased one
+ *     on the same context has the plain bits, and the other way round.  The preprocess runs
+ *     outside the recorded frame graphs, so both kinds of frame share their graphs;
+ *   - the splat composite only: the GL shadings have no such option;
+ *   - strips, radii == NULL, debug, prefiltered and every option work as in the plain forward.
+ * The backward differentiates that forward as written; gates are constants.  With G = dL/do_eff
+ * (what the blend's backward accumulates, gsr_backward's dL_dopacity):
+ *     dL_dopacity = G s;
+ *   on the floor's flat side nothing more; otherwise dL/drho = G opacity / (2 s) and
+ *     drho/da' = (c' D - D0 c) / D^2,  drho/dc' = (a' D - D0 a) / D^2,
+ *     drho/db  = -2 b (D - D0) / D^2   (b the one stored off-diagonal entry)
+ * are added to the gradient of the 2D covariance where the conic's gradient becomes it, so
+ * dL_dcov3D, dL_dscales, dL_drotations, dL_dmeans3D (through J) and the camera's dL_dviewmatrix
+ * (through J and R) receive the term.  dL_dconic keeps its meaning (the gradient of the conic's
+ * three components); the planes' and the camera's gradients compose with the option; culled
+ * Gaussians still get exact zeros; the backward's rebuild runs the antialiased preprocess.
+ * A NULL filter, or antialiasing == 0, is gsr_forward_surface / gsr_backward_camera itself: the
+ * same kernels, the same arguments.  Any other value than 0 or 1: GSR_E_INVALID, nothing
+ * written.  (The struct leaves room for the dilation's size; 0.3 is a constant for now.) */
+typedef struct {
+    int32_t antialiasing; /* 0 or 1 */
+} gsr_filter_settings;
+int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                         gsr_outputs *out, const gsr_depth_outputs *depth,
+                         const gsr_surface_outputs *surface, const gsr_filter_settings *filter,
+                         void *stream);
+int gsr_backward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                          gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

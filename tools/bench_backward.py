@@ -19,10 +19,15 @@ belongs to.
 projmatrix and campos (k_preprocess_bwd_camera / k_preprocess_bwd_planes_camera and
 k_camera_finish, inside the third stage); with or without --planes.
 
+--antialiasing: forward and backward with the antialiasing option (gsr_forward_filtered,
+gsr_backward_filtered: k_preprocess_aa and the k_preprocess_bwd*_aa kernels); with or without
+--planes and --camera.  The forward step also reports preprocess_ms, the per-Gaussian stage of
+the forward as gsr_stage_times gives it, with and without the option.
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
-                                      [--camera]
+                                      [--camera] [--antialiasing]
 """
 import argparse
 import ctypes
@@ -54,6 +59,7 @@ def worker(a):
     color = torch.empty((3, scene.H, scene.W), device=dev)
     dL = torch.randn((3, scene.H, scene.W), device=dev)
     extras, plane_grads = (), {}
+    aa = {"antialiasing": True} if a.antialiasing else {}
     if a.planes:
         extras = ("depth_map", "inv_depth_map", "final_T")
         plane_grads = {f"dL_d{n}": torch.randn((scene.H, scene.W), device=dev) for n in extras}
@@ -62,16 +68,16 @@ def worker(a):
         return rasterize_gaussians_native(scene.bg, scene.xyz, None, scene.opacity, scene.scale,
                                           scene.rot, 1.0, None, view, proj, tx, ty, scene.H,
                                           scene.W, scene.sh, scene.deg, campos, False, False,
-                                          out_color=color, extras=extras)
+                                          out_color=color, extras=extras, **aa)
 
     def backward():
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
                                                    scene.scale, scene.rot, 1.0, None, view, proj,
                                                    tx, ty, dL, scene.sh, scene.deg, campos,
-                                                   camera=bool(a.camera), **plane_grads)
+                                                   camera=bool(a.camera), **plane_grads, **aa)
 
     out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
-           "camera": bool(a.camera)}
+           "camera": bool(a.camera), "antialiasing": bool(a.antialiasing)}
     if a.step == "forward":
         for _ in range(a.warmup):
             forward()
@@ -86,6 +92,15 @@ def worker(a):
         out.update(forward_ms=round(statistics.fmean(ms), 5),
                    forward_ms_min_max=[round(min(ms), 5), round(max(ms), 5)],
                    num_rendered=res.num_rendered)
+        # the per-Gaussian stage of the forward: the library's own stage events, the mean over
+        # these frames
+        _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
+        for _ in range(a.steps):
+            forward()
+        stage = (ctypes.c_float * 8)()
+        _lib.check(lib.gsr_stage_times(ctx, stage, 8), "gsr_stage_times")
+        _lib.check(lib.gsr_set_timing(ctx, 0), "gsr_set_timing")
+        out.update(preprocess_ms=round(float(stage[0]), 5))
     else:
         for _ in range(a.warmup):
             backward()
@@ -117,6 +132,8 @@ def main():
                     help="gsr_backward_planes: colour plus the three planes' gradients")
     ap.add_argument("--camera", action="store_true",
                     help="gsr_backward_camera: also the gradients of the camera")
+    ap.add_argument("--antialiasing", action="store_true",
+                    help="gsr_forward_filtered / gsr_backward_filtered with antialiasing = 1")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -126,7 +143,8 @@ def main():
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", a.config,
                             "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step] +
                            (["--planes"] if a.planes else []) +
-                           (["--camera"] if a.camera else []),
+                           (["--camera"] if a.camera else []) +
+                           (["--antialiasing"] if a.antialiasing else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
