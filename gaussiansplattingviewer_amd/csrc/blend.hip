@@ -8,11 +8,13 @@
 // tile's depth-sorted list 64 splats at a time, culls them against its own quadrant (the
 // splat's conservative alpha >= 1/255 ellipse from preprocess.hip cull_data: bounding box,
 // then the exact ellipse-vs-box minimum with a rounding bound), compacts the survivors into
-// LDS with a ballot, composites them two at a time, and stops as soon as its 64 pixels are
-// done.  At C3 a quadrant wave examines ~4.4 chunks (~280 list entries) and composites ~118
-// splats (a per-wave timeline, tools/lab/blend_trace.py); by the ISA and SQ_INSTS_VALU about two
-// thirds of its VALU is the compositing loop (33 VALU + 5 LDS reads per composited pair) and one
-// third the per-chunk gather, cull and staging.
+// LDS with a ballot, composites them two at a time, and stops at the pair after which its 64
+// pixels are done (kStopPairs below: the rest of the chunk's survivors would be composited at
+// weight 0 in every lane).  At C3, on tight lists, a quadrant wave examines 2.99 chunks (~190
+// list entries), stages 127.3 splats and composites 104.4 of them (a per-wave timeline,
+// tools/lab/blend_trace.py; profiles/r07b_blend_trace.txt); by the ISA about two thirds of its
+// VALU is the compositing loop (33 VALU + 5 LDS reads per composited pair, and the exit's one
+// compare) and one third the per-chunk gather, cull and staging.
 //
 // Skipping splats that provably cannot reach alpha >= 1/255 changes nothing: upstream skips
 // them too (`if (alpha < 1/255) continue`), and n_contrib -- upstream's running `contributor`
@@ -85,6 +87,17 @@ struct StagedSplat {
 // the depth keys once per pixel.  The terminating splat cannot qualify (alpha <= 0.99 and
 // T' < 1e-4 need T < 0.01), nor can a skipped one (T' = T), nor anything after the pixel is done
 // (T <= 0).  Without kMedian none of it is compiled.
+//
+// kStopPairs: after every kStopPairs composited pairs the wave asks whether any of its pixels
+// is still live and, if none is, leaves the pair loop and with it the chunk loop (no further
+// gather, cull or staging).  A done pixel has T <= 0: its weight is 0, -|T| is idempotent, and
+// neither last_contributor nor median_pos can change, so for finite inputs the composites
+// skipped change no bit of the colour, final_T, n_contrib, the depth planes or the median outputs.
+// 1 of 1, 2, 4, 8 by measurement (profiles/r07b_ab_blend_stop.txt): the test after every pair is
+// the loop's own back edge (one v_cmp, the scalar branch it already had) and the serial C3 blend
+// goes 113.5 -> 101-103 us; a test every 2, 4 or 8 pairs compiles to a second branch and a
+// recomputed LDS address per pair and gains less (108-110 us).
+constexpr int kStopPairs = 1;
 template <bool kFast, bool kContrib, bool kDepth, bool kMedian = false>
 __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
                                         const GsrDepthArgs &d,
@@ -287,7 +300,8 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
         // single-buffered: a software-pipelined form (the next pair's LDS reads in flight
         // during this pair) spilled past 64 VGPRs and was slower
         auto composite_all = [&](auto bound_tag) {
-            for (int k = 0; k < count; k += 2) {
+            int k = 0;  // (count >= 2 and even here)
+            do {
                 float4 zf = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pair's {z, 1 / z}
                 if constexpr (kDepth) zf = *reinterpret_cast<const float4 *>(&s_zf[k]);
                 if (kPair) {
@@ -302,7 +316,10 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
                     composite(a0, zf.x, zf.y, bound_tag);
                     composite(a1, zf.z, zf.w, bound_tag);
                 }
-            }
+                k += 2;
+                // the early exit (kStopPairs above): k and count are wave-uniform, the test is
+                // a compare of T into an SGPR pair and a scalar branch
+            } while (k < count && ((k / 2) % kStopPairs != 0 || live_any()));
         };
         // (the exact form always tests power > 0, as upstream writes it)
         if (!kFast || __ballot(npd) != 0ull)
@@ -347,11 +364,13 @@ __global__ __launch_bounds__(256, 8) void k_blend_q(const GsrBlendArgs a, uint32
 
 // The depth-accumulating form: 14 KiB of LDS per block; kDepthWaves waves per SIMD leave it the
 // registers for the two accumulators and the pair's features without scratch.
+// Without n_contrib the kernel has always fitted 72 VGPRs, 7 waves; its bound says so, since
+// under a bound of 6 some forms of the early exit's loop took a 73rd
+// (profiles/blend_stop_resources.txt).
 constexpr int kDepthWaves = 6;
 template <bool kFast, bool kContrib>
-__global__ __launch_bounds__(256, kDepthWaves) void k_blend_depth_q(const GsrBlendArgs a,
-                                                                    uint32_t n_tiles,
-                                                                    const GsrDepthArgs d) {
+__global__ __launch_bounds__(256, kContrib ? kDepthWaves : kDepthWaves + 1) void k_blend_depth_q(
+    const GsrBlendArgs a, uint32_t n_tiles, const GsrDepthArgs d) {
     blend_q<kFast, kContrib, true>(a, n_tiles, d);
 }
 

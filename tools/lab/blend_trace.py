@@ -1,12 +1,13 @@
 """Lab: per-wave timeline of the blend (not the product).
 
-  python tools/lab/blend_trace.py make            # writes build/lab_trace_src/blend.hip from
-                                                   # csrc/blend.hip with per-wave tracing, then
-                                                   # tools/lab/build.sh trace blend.hip <it>
+  python tools/lab/blend_trace.py make [SRC NAME] # writes build/lab_<NAME>_src/blend.hip from
+                                                   # SRC (csrc/blend.hip, NAME trace) with per-wave
+                                                   # tracing, then tools/lab/build.sh <NAME> blend.hip <it>
   GSR_LIB=.../libgsr_lab_trace.so python tools/lab/blend_trace.py run [--config c3]
 
 Each quadrant wave records {start, end} (s_memrealtime, 100 MHz), its hardware slot (HW_ID,
-XCC_ID) and its chunk / composite counts; `run` renders one serial frame and prints the
+XCC_ID) and its chunk count and the composites it executed (pad slots included; with the early exit fewer
+than it staged); `run` renders one serial frame and prints the
 kernel span, the active-wave curve and the tail (how long the last waves run with the chip
 mostly idle), plus the work distribution.
 """
@@ -21,8 +22,8 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def make():
-    src = open(os.path.join(REPO, "gaussiansplattingviewer_amd/csrc/blend.hip")).read()
+def make(src_path=None, name="trace"):
+    src = open(src_path or os.path.join(REPO, "gaussiansplattingviewer_amd/csrc/blend.hip")).read()
     patches = [
         ("namespace {\n", "namespace {\n__device__ uint4 g_trace[1 << 16];\n", 1),
         ("    StagedSplat *const s_spl = s_spl_q[quad];\n",
@@ -32,7 +33,9 @@ def make():
          "    uint32_t n_chunks = 0, n_comp = 0;\n", 1),
         ("    for (uint32_t start = range.x; start < range.y; start += 64) {\n",
          "    for (uint32_t start = range.x; start < range.y; start += 64) {\n        ++n_chunks;\n", 1),
-        ("            ++count;\n        }\n", "            ++count;\n        }\n        n_comp += count;\n", 1),
+        ("                    composite(a1, zf.z, zf.w, bound_tag);\n                }\n",
+         "                    composite(a1, zf.z, zf.w, bound_tag);\n                }\n"
+         "                n_comp += 2;\n", 1),
         ("    if (inside) {\n        const int row = py - a.y0;",
          "    if (lane == 0 && work < (1u << 16)) {\n"
          "        const uint32_t t_end = (uint32_t)__builtin_amdgcn_s_memrealtime();\n"
@@ -52,11 +55,11 @@ def make():
             '    if (clear) return hipMemset(p, 0, sizeof(uint4) << 16) == hipSuccess ? 0 : -1;\n'
             '    return hipMemcpy(dst, p, (size_t)n * 16, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;\n'
             '}\n')
-    out_dir = os.path.join(REPO, "build", "lab_trace_src")
+    out_dir = os.path.join(REPO, "build", f"lab_{name}_src")
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, "blend.hip")
     open(path, "w").write(src)
-    subprocess.run(["bash", os.path.join(REPO, "tools/lab/build.sh"), "trace", "blend.hip", path],
+    subprocess.run(["bash", os.path.join(REPO, "tools/lab/build.sh"), name, "blend.hip", path],
                    check=True, env=dict(os.environ, LAB_FLAGS="-I" + os.path.join(REPO, "gaussiansplattingviewer_amd/csrc")))
 
 
@@ -137,7 +140,7 @@ def run(cfg):
 
 if __name__ == "__main__":
     if sys.argv[1] == "make":
-        make()
+        make(*sys.argv[2:4])
     else:
         cfg = sys.argv[sys.argv.index("--config") + 1] if "--config" in sys.argv else "c3"
         run(cfg)
