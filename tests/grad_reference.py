@@ -21,6 +21,8 @@ is that both counts are 0 (test_grad_reference.py):
              within 1e-3 relative of 1e-4;
   project:   Gaussians with |t.x / t.z| or |t.y / t.z| within 1e-5 relative of 1.3 tan, or an
              SH sum + 0.5 within 1e-5 (absolute: the knee is 0, colours are O(1)) of 0.
+Scenes too large for that condition (frame_grad_scenes) ask composite for the pixels near a gate
+instead (its `band` argument) and zero their image gradients there.
 """
 from __future__ import annotations
 
@@ -146,10 +148,19 @@ def project(cam, radii, means3D, means2D, scales=None, rotations=None, cov3D=Non
     return full(px), full(conic), full(rgb), new_gates, near
 
 
-def composite(lists, means2D_px, conic, opacity, rgb, bg, W, H, gates=None):
+def composite(lists, means2D_px, conic, opacity, rgb, bg, W, H, gates=None, band=None):
     """The blend over given lists: lists = (ranges [T,2], point_list [K]) as integer arrays.
     Returns (color [3,H,W], gates, near_gate); gates holds, per tile, the float decisions
-    (contributing pairs, capped pairs) of this run."""
+    (contributing pairs, capped pairs) of this run.
+
+    band (a run that decides its own gates only): a fourth result, near_px [H,W] bool -- the pixel
+    has, up to its termination, a pair with alpha within `band` relative of 1/255, o G within
+    `band` relative of 0.99, power in (-0.1 band, 0] or T (1 - alpha) within 100 band relative of
+    1e-4: near_gate's four bands in their ratios (1 : 1 : 0.1 : 100), scaled.  near_gate itself
+    keeps its bands.  A caller zeroes its image gradients there (frame_grad_scenes)."""
+    if band is not None and gates is not None:
+        raise ValueError("band: only with this run's own gates")
+    near_px = np.zeros((H, W), bool)
     ranges = np.asarray(lists[0]).reshape(-1, 2).astype(np.int64)
     plist = np.asarray(lists[1]).astype(np.int64)
     dt = means2D_px.dtype
@@ -189,6 +200,12 @@ def composite(lists, means2D_px, conic, opacity, rgb, bg, W, H, gates=None):
                 near += int((before & (rel(alpha, A_MIN, 1e-5) | rel(oG, A_CAP, 1e-5) |
                                        ((power > -1e-6) & (power <= 0)) |
                                        (~skip & rel(test_T, T_MIN, 1e-3)))).sum())
+                if band is not None:
+                    hit = before & (rel(alpha, A_MIN, band) | rel(oG, A_CAP, band) |
+                                    ((power > -0.1 * band) & (power <= 0)) |
+                                    (~skip & rel(test_T, T_MIN, 100.0 * band)))
+                    near_px[y0:y0 + len(ys), x0:x0 + len(xs)] = \
+                        hit.any(1).reshape(len(ys), len(xs)).numpy()
         else:
             cap, contrib = gates[tile]
         new_gates[tile] = (cap, contrib)
@@ -199,6 +216,8 @@ def composite(lists, means2D_px, conic, opacity, rgb, bg, W, H, gates=None):
         w = a_c * T
         C = w @ rgb[ids] + Tn[:, -1:] * bgt[None, :]
         color[:, y0:y0 + len(ys), x0:x0 + len(xs)] = C.t().reshape(3, len(ys), len(xs))
+    if band is not None:
+        return color, new_gates, near, near_px
     return color, new_gates, near
 
 
