@@ -38,20 +38,18 @@ argument, `opacities`: upstream reads them out of geomBuffer, here nothing of th
 and `gsr_backward` (include/gsr.h, which states the semantics) rebuilds the state from the
 inputs.  `radii`, `num_rendered` and the three buffers are accepted and ignored.
 
-`_C.rasterize_gaussians_planes(<the 19 arguments>)` -> (num_rendered, color, radii, depth_map,
-inv_depth_map, final_T) and `_C.rasterize_gaussians_backward_planes(bg, means3D, colors_precomp,
-opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx,
-tanfovy, sh, sh_degree, campos, debug, dL_dout_color, dL_ddepth_map, dL_dinv_depth_map,
-dL_dfinal_T)` -> the same 8-tuple are this package's own: the forward with its per-pixel planes
-(`gsr_forward_depth`) and the backward that takes their gradients (`gsr_backward_planes`; an empty
-tensor is an unused gradient), behind `GaussianRasterizationSettings(depth_maps=True)`.
-`_C.rasterize_gaussians_backward_camera(<the same 20 arguments>)` -> that 8-tuple, then
-dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4) and dL_dcampos (3,) (`gsr_backward_camera`), behind a
-`viewmatrix`, `projmatrix` or `campos` that requires a gradient.
-`_C.rasterize_gaussians_filtered(<the 19 arguments>, antialiasing)` -> rasterize_gaussians_planes'
-6-tuple and `_C.rasterize_gaussians_backward_filtered(<rasterize_gaussians_backward_camera's 20
-arguments>, antialiasing)` -> its 11-tuple (`gsr_forward_filtered`, `gsr_backward_filtered`), behind
-`GaussianRasterizationSettings(antialiasing=True)`.
+`_C.rasterize_gaussians_ext(<the 19 arguments>, shading, planes, antialiasing)` ->
+(num_rendered, color, radii, depth_map, inv_depth_map, final_T) and
+`_C.rasterize_gaussians_backward_ext(bg, means3D, colors_precomp, opacities, scales, rotations,
+scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, sh, sh_degree, campos,
+debug, dL_dout_color, dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T, camera, antialiasing)` -> the
+same 8-tuple, then dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4) and dL_dcampos (3,) are this
+package's own, one general entry per direction behind `GaussianRasterizationSettings(depth_maps=
+True)`, `(antialiasing=True)` and a `viewmatrix`, `projmatrix` or `campos` that requires a
+gradient.  The forward is `gsr_forward_filtered` with the per-pixel planes only if `planes`
+(without, the three tensors are empty) and the filter only if `antialiasing`; a shading, or
+neither, is `gsr_forward_shaded`.  The backward is `gsr_backward_filtered` with NULL for what is
+not asked for: an empty tensor is an unused gradient, and without `camera` its three are empty.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -60,10 +58,8 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
-                          rasterize_gaussians_backward, rasterize_gaussians_backward_camera,
-                          rasterize_gaussians_backward_filtered,
-                          rasterize_gaussians_backward_planes, rasterize_gaussians_filtered,
-                          rasterize_gaussians_planes, rasterize_gaussians_shaded)
+                          rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
+                          rasterize_gaussians_ext, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

@@ -129,6 +129,20 @@ class GsrPlyInfo(ctypes.Structure):
     ]
 
 
+# The entries added to ABI 4 one by one: the structs between (ctx, gaussians, settings) and the
+# stream.
+_ADDITIVE = {
+    "gsr_forward_depth": (GsrOutputs, GsrDepthOutputs),
+    "gsr_forward_surface": (GsrOutputs, GsrDepthOutputs, GsrSurfaceOutputs),
+    "gsr_forward_filtered": (GsrOutputs, GsrDepthOutputs, GsrSurfaceOutputs, GsrFilterSettings),
+    "gsr_backward": (GsrBackwardInputs, GsrGradients),
+    "gsr_backward_planes": (GsrBackwardInputs, GsrPlaneGradients, GsrGradients),
+    "gsr_backward_camera": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                            GsrGradients),
+    "gsr_backward_filtered": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                              GsrFilterSettings, GsrGradients),
+}
+
 _lock = threading.Lock()
 _lib = None
 _contexts: dict[int, ctypes.c_void_p] = {}
@@ -147,64 +161,17 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gsr_forward_shaded.argtypes = [vp, ctypes.POINTER(GsrGaussians),
                                        ctypes.POINTER(GsrRasterSettings),
                                        ctypes.POINTER(GsrOutputs), ctypes.c_int32, vp]
-    # (an older build of ABI 4 loaded through GSR_LIB lacks it: forward_depth() says so)
-    if hasattr(lib, "gsr_forward_depth"):
-        lib.gsr_forward_depth.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                          ctypes.POINTER(GsrRasterSettings),
-                                          ctypes.POINTER(GsrOutputs),
-                                          ctypes.POINTER(GsrDepthOutputs), vp]
-        lib.gsr_forward_depth.restype = i32
-    # (an older build of ABI 4 loaded through GSR_LIB lacks it: forward_surface_fn() says so)
-    if hasattr(lib, "gsr_forward_surface"):
-        lib.gsr_forward_surface.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                            ctypes.POINTER(GsrRasterSettings),
-                                            ctypes.POINTER(GsrOutputs),
-                                            ctypes.POINTER(GsrDepthOutputs),
-                                            ctypes.POINTER(GsrSurfaceOutputs), vp]
-        lib.gsr_forward_surface.restype = i32
-    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_fn() says so)
+    # the additive entries (an older build of ABI 4 loaded through GSR_LIB lacks some: the
+    # accessors below say so): (ctx, gaussians, settings), the table's structs, the stream
+    for name, structs in _ADDITIVE.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes = [vp, ctypes.POINTER(GsrGaussians), ctypes.POINTER(GsrRasterSettings),
+                           *(ctypes.POINTER(t) for t in structs), vp]
+            fn.restype = i32
     if hasattr(lib, "gsr_backward"):
-        lib.gsr_backward.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                     ctypes.POINTER(GsrRasterSettings),
-                                     ctypes.POINTER(GsrBackwardInputs),
-                                     ctypes.POINTER(GsrGradients), vp]
-        lib.gsr_backward.restype = i32
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
-    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_planes_fn() says so)
-    if hasattr(lib, "gsr_backward_planes"):
-        lib.gsr_backward_planes.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                            ctypes.POINTER(GsrRasterSettings),
-                                            ctypes.POINTER(GsrBackwardInputs),
-                                            ctypes.POINTER(GsrPlaneGradients),
-                                            ctypes.POINTER(GsrGradients), vp]
-        lib.gsr_backward_planes.restype = i32
-    # (an older build of ABI 4 loaded through GSR_LIB lacks it: backward_camera_fn() says so)
-    if hasattr(lib, "gsr_backward_camera"):
-        lib.gsr_backward_camera.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                            ctypes.POINTER(GsrRasterSettings),
-                                            ctypes.POINTER(GsrBackwardInputs),
-                                            ctypes.POINTER(GsrPlaneGradients),
-                                            ctypes.POINTER(GsrCameraGradients),
-                                            ctypes.POINTER(GsrGradients), vp]
-        lib.gsr_backward_camera.restype = i32
-    # (an older build of ABI 4 loaded through GSR_LIB lacks them: filtered_fns() says so)
-    if hasattr(lib, "gsr_forward_filtered"):
-        lib.gsr_forward_filtered.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                             ctypes.POINTER(GsrRasterSettings),
-                                             ctypes.POINTER(GsrOutputs),
-                                             ctypes.POINTER(GsrDepthOutputs),
-                                             ctypes.POINTER(GsrSurfaceOutputs),
-                                             ctypes.POINTER(GsrFilterSettings), vp]
-        lib.gsr_forward_filtered.restype = i32
-        lib.gsr_backward_filtered.argtypes = [vp, ctypes.POINTER(GsrGaussians),
-                                              ctypes.POINTER(GsrRasterSettings),
-                                              ctypes.POINTER(GsrBackwardInputs),
-                                              ctypes.POINTER(GsrPlaneGradients),
-                                              ctypes.POINTER(GsrCameraGradients),
-                                              ctypes.POINTER(GsrFilterSettings),
-                                              ctypes.POINTER(GsrGradients), vp]
-        lib.gsr_backward_filtered.restype = i32
     lib.gsr_get_binning.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i64),
                                     ctypes.POINTER(ctypes.c_int32), vp]
     lib.gsr_mark_visible.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -251,68 +218,50 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         return lib
 
 
+def _optional_fn(lib, name: str, needs: str):
+    """An additive entry (or a tuple of them, `name` joined by " / ") of a loaded library;
+    RuntimeError if that build does not have it."""
+    names = name.split(" / ")
+    fns = tuple(getattr(lib, n, None) for n in names)
+    if None in fns:
+        one = len(names) == 1
+        raise RuntimeError(
+            f"{LIB_PATH} has no {name}: {needs} a libgsr.so built from this tree (include/gsr.h "
+            f"declares {'it' if one else 'them'}; ABI 4, additive)")
+    return fns[0] if len(fns) == 1 else fns
+
+
 def forward_depth_fn(lib: ctypes.CDLL):
     """gsr_forward_depth of a loaded library; RuntimeError if that build does not have it."""
-    fn = getattr(lib, "gsr_forward_depth", None)
-    if fn is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_forward_depth: the depth_map / inv_depth_map outputs need a "
-            "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
-    return fn
+    return _optional_fn(lib, "gsr_forward_depth", "the depth_map / inv_depth_map outputs need")
 
 
 def forward_surface_fn(lib: ctypes.CDLL):
     """gsr_forward_surface of a loaded library; RuntimeError if that build does not have it."""
-    fn = getattr(lib, "gsr_forward_surface", None)
-    if fn is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_forward_surface: the median_depth / median_id outputs need a "
-            "libgsr.so built from this tree (include/gsr.h declares it; ABI 4, additive)")
-    return fn
+    return _optional_fn(lib, "gsr_forward_surface", "the median_depth / median_id outputs need")
 
 
 def backward_fn(lib: ctypes.CDLL):
     """gsr_backward of a loaded library; RuntimeError if that build does not have it."""
-    fn = getattr(lib, "gsr_backward", None)
-    if fn is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_backward: gradients need a libgsr.so built from this tree "
-            "(include/gsr.h declares it; ABI 4, additive)")
-    return fn
+    return _optional_fn(lib, "gsr_backward", "gradients need")
 
 
 def backward_planes_fn(lib: ctypes.CDLL):
     """gsr_backward_planes of a loaded library; RuntimeError if that build does not have it."""
-    fn = getattr(lib, "gsr_backward_planes", None)
-    if fn is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_backward_planes: gradients of depth_map / inv_depth_map / "
-            "final_T need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
-            "additive)")
-    return fn
+    return _optional_fn(lib, "gsr_backward_planes",
+                        "gradients of depth_map / inv_depth_map / final_T need")
 
 
 def backward_camera_fn(lib: ctypes.CDLL):
     """gsr_backward_camera of a loaded library; RuntimeError if that build does not have it."""
-    fn = getattr(lib, "gsr_backward_camera", None)
-    if fn is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_backward_camera: gradients of viewmatrix / projmatrix / "
-            "campos need a libgsr.so built from this tree (include/gsr.h declares it; ABI 4, "
-            "additive)")
-    return fn
+    return _optional_fn(lib, "gsr_backward_camera",
+                        "gradients of viewmatrix / projmatrix / campos need")
 
 
 def filtered_fns(lib: ctypes.CDLL):
     """(gsr_forward_filtered, gsr_backward_filtered) of a loaded library; RuntimeError if that
     build does not have them."""
-    fw = getattr(lib, "gsr_forward_filtered", None)
-    bw = getattr(lib, "gsr_backward_filtered", None)
-    if fw is None or bw is None:
-        raise RuntimeError(
-            f"{LIB_PATH} has no gsr_forward_filtered / gsr_backward_filtered: antialiasing needs "
-            "a libgsr.so built from this tree (include/gsr.h declares them; ABI 4, additive)")
-    return fw, bw
+    return _optional_fn(lib, "gsr_forward_filtered / gsr_backward_filtered", "antialiasing needs")
 
 
 def check(rc: int, what: str) -> int:

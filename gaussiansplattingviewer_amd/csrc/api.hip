@@ -379,6 +379,20 @@ struct Frame {
     uint32_t id_mask = 0xFFFFFFFFu;
 };
 
+// What a call asks of its frame beyond the plain composite: every forward entry point, and
+// gsr_backward's rebuild, is forward() with one of these.  setup_frame copies it into the Frame,
+// so the overflow re-render carries the same state as the first attempt.
+struct FrameRequest {
+    int shading = GSR_SHADE_SPLAT;
+    const gsr_depth_outputs *depth = nullptr;      // NULL: no depth planes
+    const gsr_surface_outputs *surface = nullptr;  // NULL: no median planes
+    // gsr_forward_filtered: the call's, not the context's; the preprocess runs outside the
+    // recorded chains (which read none of its opacity-dependent arguments), so plain and
+    // antialiased frames share their graphs
+    bool antialiasing = false;
+    bool no_blend = false;
+};
+
 int stage_end(gsr_context *ctx, const Frame &f, int i) {
     if (f.tmode == 1 || (f.tmode == 2 && i >= 5))
         GSR_HIP(hipEventRecord(f.ev[i + 1], f.s), "hipEventRecord");
@@ -393,7 +407,7 @@ int stage_end(gsr_context *ctx, const Frame &f, int i) {
 // Arguments -> Frame (upstream's argument checks and messages, rasterize_points.cu /
 // __init__.py), workspace for P.
 int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                gsr_outputs *out, hipStream_t s, int shading, Frame &f) {
+                gsr_outputs *out, hipStream_t s, const FrameRequest &rq, Frame &f) {
     const int64_t P = g->P;
     const int W = st->image_width, H = st->image_height;
     if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, "gsr_forward: bad P");
@@ -426,7 +440,11 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
         return fail(GSR_E_INVALID, "gsr_forward: conic_opacity output must be 16-B aligned");
 
     f.s = s;
-    f.shading = shading;
+    f.shading = rq.shading;
+    if (rq.depth) f.depth_map = rq.depth->depth_map, f.inv_depth_map = rq.depth->inv_depth_map;
+    if (rq.surface)
+        f.median_depth = rq.surface->median_depth, f.median_id = rq.surface->median_id;
+    f.no_blend = rq.no_blend;
     f.P = P;
     f.W = W;
     f.H = H;
@@ -496,6 +514,7 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     pa.row_begin = f.rb;
     pa.row_end = f.re;
     pa.prefiltered = st->prefiltered;
+    pa.antialiasing = rq.antialiasing ? 1 : 0;
     pa.sh_vec4 = (g->shs && g->M == 16 && (reinterpret_cast<uintptr_t>(g->shs) & 15) == 0) ? 1 : 0;
     pa.rot_vec4 = (g->rotations && (reinterpret_cast<uintptr_t>(g->rotations) & 15) == 0) ? 1 : 0;
     pa.radii = out->radii;
@@ -532,7 +551,7 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     // strip ranks' footprint skip (preprocess.hip strip_reach) bounds upstream's rect, not the
     // ellipse, and reads no opacity.
     f.tight = ctx->tight && f.colpairs && !out->n_contrib && f.rows_tiles == f.gy &&
-              shading != GSR_SHADE_BILLBOARD;
+              rq.shading != GSR_SHADE_BILLBOARD;
     pa.strip_rc = f.tight ? ctx->strip_rc.get() : nullptr;
     pa.block_pairs = ctx->pair_count.get();
     pa.host_words = ctx->d_host_words;
@@ -1164,23 +1183,10 @@ int forward_graph(gsr_context *ctx, Frame &f, const gsr_raster_settings *st, gsr
 }
 
 int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-            gsr_outputs *out, hipStream_t s, int shading, const gsr_depth_outputs *depth,
-            bool no_blend = false, const gsr_surface_outputs *surface = nullptr,
-            bool antialiasing = false) {
+            gsr_outputs *out, hipStream_t s, const FrameRequest &rq) {
     Frame f;
     ctx->last.valid = false;
-    // the planes of the call, set again after every setup_frame
-    auto planes = [&]() {
-        if (depth) f.depth_map = depth->depth_map, f.inv_depth_map = depth->inv_depth_map;
-        if (surface) f.median_depth = surface->median_depth, f.median_id = surface->median_id;
-        f.no_blend = no_blend;
-        // gsr_forward_filtered: the call's, not the context's; the preprocess runs outside the
-        // recorded chains (which read none of its opacity-dependent arguments), so plain and
-        // antialiased frames share their graphs
-        f.pa.antialiasing = antialiasing ? 1 : 0;
-    };
-    GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
-    planes();
+    GSR_TRY(setup_frame(ctx, g, st, out, s, rq, f));
     if (ctx->second_stream && !ctx->aux)
         GSR_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, 0),
                 "hipStreamCreateWithPriority(second stream)");
@@ -1200,8 +1206,7 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         ++ctx->graph_overflows;
         ctx->list_cap = list_capacity((int64_t)f.KL, ctx->list_cap);
         GSR_TRY(reserve_K(ctx, ctx->list_cap, s));
-        GSR_TRY(setup_frame(ctx, g, st, out, s, shading, f));
-        planes();
+        GSR_TRY(setup_frame(ctx, g, st, out, s, rq, f));
         f.graph = false;
     }
 
@@ -1271,6 +1276,20 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
     GSR_TRY(frame_tail(ctx, f, st, out));
     finish_frame(ctx, f, out);
     return GSR_OK;
+}
+
+// Every public forward: the NULL check, the shading's range (gsr_forward_shaded's argument; the
+// others pass the splat), the context's lock, the stream's order, the frame.
+int forward_entry(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                  gsr_outputs *out, void *stream, const FrameRequest &rq) {
+    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    if (rq.shading < GSR_SHADE_SPLAT || rq.shading > GSR_SHADE_GAUSS_BALL)
+        return fail(GSR_E_INVALID, "gsr_forward_shaded: unknown shading " +
+                                       std::to_string(rq.shading) + " (GSR_SHADE_* 0..3)");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GSR_TRY(order_stream(ctx, s));
+    return forward(ctx, g, st, out, s, rq);
 }
 
 }  // namespace
@@ -1460,31 +1479,23 @@ int gsr_stage_times(gsr_context *ctx, float *ms, int n) {
 
 int gsr_forward_shaded(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                        gsr_outputs *out, int32_t shading, void *stream) {
-    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
-    if (shading < GSR_SHADE_SPLAT || shading > GSR_SHADE_GAUSS_BALL)
-        return fail(GSR_E_INVALID, "gsr_forward_shaded: unknown shading " +
-                                       std::to_string(shading) + " (GSR_SHADE_* 0..3)");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), shading, nullptr);
+    return forward_entry(ctx, g, st, out, stream, {shading});
+}
+
+int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                gsr_outputs *out, void *stream) {
+    return forward_entry(ctx, g, st, out, stream, {});
 }
 
 int gsr_forward_depth(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                       gsr_outputs *out, const gsr_depth_outputs *depth, void *stream) {
-    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth);
+    return forward_entry(ctx, g, st, out, stream, {GSR_SHADE_SPLAT, depth});
 }
 
 int gsr_forward_surface(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                         gsr_outputs *out, const gsr_depth_outputs *depth,
                         const gsr_surface_outputs *surface, void *stream) {
-    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth, false,
-                   surface);
+    return forward_entry(ctx, g, st, out, stream, {GSR_SHADE_SPLAT, depth, surface});
 }
 
 // 0 or 1 from a gsr_filter_settings (NULL: 0), -1 for anything else.
@@ -1502,16 +1513,7 @@ int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
         return fail(GSR_E_INVALID, "gsr_forward_filtered: antialiasing must be 0 or 1, got " +
                                        std::to_string(filter->antialiasing));
     if (!aa) return gsr_forward_surface(ctx, g, st, out, depth, surface, stream);
-    if (!ctx || !g || !st || !out) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    GSR_TRY(order_stream(ctx, static_cast<hipStream_t>(stream)));
-    return forward(ctx, g, st, out, static_cast<hipStream_t>(stream), GSR_SHADE_SPLAT, depth, false,
-                   surface, true);
-}
-
-int gsr_forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                gsr_outputs *out, void *stream) {
-    return gsr_forward_shaded(ctx, g, st, out, GSR_SHADE_SPLAT, stream);
+    return forward_entry(ctx, g, st, out, stream, {GSR_SHADE_SPLAT, depth, surface, true});
 }
 
 // The gradients of the splat composite.  Everything is rebuilt from the arguments -- the
@@ -1556,15 +1558,15 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         cam && (cam->dL_dviewmatrix || cam->dL_dprojmatrix || cam->dL_dcampos);
     if (P == 0) {  // no Gaussian, no gradient: the camera's buffers, of a fixed size, are zeros
         if (camera) {
-            if (cam->dL_dviewmatrix)
-                GSR_HIP(hipMemsetAsync(cam->dL_dviewmatrix, 0, 16 * sizeof(float), s),
-                        "hipMemsetAsync(dL_dviewmatrix)");
-            if (cam->dL_dprojmatrix)
-                GSR_HIP(hipMemsetAsync(cam->dL_dprojmatrix, 0, 16 * sizeof(float), s),
-                        "hipMemsetAsync(dL_dprojmatrix)");
-            if (cam->dL_dcampos)
-                GSR_HIP(hipMemsetAsync(cam->dL_dcampos, 0, 3 * sizeof(float), s),
-                        "hipMemsetAsync(dL_dcampos)");
+            const struct {
+                float *p;
+                size_t n;
+                const char *what;
+            } sums[] = {{cam->dL_dviewmatrix, 16, "hipMemsetAsync(dL_dviewmatrix)"},
+                        {cam->dL_dprojmatrix, 16, "hipMemsetAsync(dL_dprojmatrix)"},
+                        {cam->dL_dcampos, 3, "hipMemsetAsync(dL_dcampos)"}};
+            for (const auto &m : sums)
+                if (m.p) GSR_HIP(hipMemsetAsync(m.p, 0, m.n * sizeof(float), s), m.what);
         }
         return GSR_OK;
     }
@@ -1590,8 +1592,10 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     };
     GSR_TRY(mark(0));
     ctx->tight = ctx->graphs = ctx->timing = 0;
-    const int rc = forward(ctx, g, st, &out, s, GSR_SHADE_SPLAT, nullptr, true, nullptr,
-                           antialiasing);
+    FrameRequest rebuild;
+    rebuild.antialiasing = antialiasing;
+    rebuild.no_blend = true;
+    const int rc = forward(ctx, g, st, &out, s, rebuild);
     ctx->tight = tight, ctx->graphs = graphs, ctx->timing = timing;
     GSR_TRY(rc);
 
@@ -1664,27 +1668,21 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     pb.dL_dscales = gr->dL_dscales;
     pb.dL_drotations = gr->dL_drotations;
     pb.dL_dcov3D = gr->dL_dcov3D;
-    // gsr_backward_filtered: the antialiased twins, which also read the opacities
-    const float *const aa_op = antialiasing ? g->opacities : nullptr;
+    GsrPreprocessBwdExtras extras;
+    extras.planes = planes;
+    extras.dL_ddepths = dL_ddepths;
+    // (an empty list leaves the rows zero: every product, and so every sum of the camera's, is 0)
+    GsrCameraBwdArgs ca{};
     if (camera) {
-        // (an empty list leaves the rows zero: every product, and so every sum, is 0)
-        const GsrCameraBwdArgs ca{ctx->cam_partials.get(), cam->dL_dviewmatrix,
-                                  cam->dL_dprojmatrix, cam->dL_dcampos};
-        GSR_HIP(gsr_launch_preprocess_bwd_camera(pb, planes, planes ? dL_ddepths : nullptr, ca, s,
-                                                 aa_op),
-                "per-Gaussian backward launch");
-        if (!planes && dL_ddepths)
-            GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
-                    "hipMemsetAsync(dL_ddepths)");
-    } else if (planes) {
-        GSR_HIP(gsr_launch_preprocess_bwd_planes(pb, dL_ddepths, s, aa_op),
-                "per-Gaussian backward launch");
-    } else {
-        GSR_HIP(gsr_launch_preprocess_bwd(pb, s, aa_op), "per-Gaussian backward launch");
-        if (dL_ddepths)  // no plane gradient: nothing reaches the features
-            GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
-                    "hipMemsetAsync(dL_ddepths)");
+        ca = {ctx->cam_partials.get(), cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos};
+        extras.camera = &ca;
     }
+    // gsr_backward_filtered: the antialiased twins, which also read the opacities
+    extras.aa_opacities = antialiasing ? g->opacities : nullptr;
+    GSR_HIP(gsr_launch_preprocess_bwd(pb, extras, s), "per-Gaussian backward launch");
+    if (!planes && dL_ddepths)  // no plane gradient: nothing reaches the features
+        GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
+                "hipMemsetAsync(dL_ddepths)");
     GSR_TRY(mark(3));
     ctx->bwd_timed = timing != 0;
     return stage_check("stage per-Gaussian backward");

@@ -494,58 +494,34 @@ hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneB
     return hipGetLastError();
 }
 
-hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &args, hipStream_t s,
-                                     const float *aa_opacities) {
-    if (args.P == 0) return hipSuccess;
-    GsrPreprocessBwdArgs a = args;
-    a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
-    const dim3 grid((unsigned)gsr_preprocess_blocks(a.P));
-    if (aa_opacities)
-        hipLaunchKernelGGL(k_preprocess_bwd_aa, grid, dim3(256), 0, s, a, aa_opacities);
-    else
-        hipLaunchKernelGGL(k_preprocess_bwd, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &args, float *dL_ddepths,
-                                            hipStream_t s, const float *aa_opacities) {
-    if (args.P == 0) return hipSuccess;
-    GsrPreprocessBwdArgs a = args;
-    a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
-    const dim3 grid((unsigned)gsr_preprocess_blocks(a.P));
-    if (aa_opacities)
-        hipLaunchKernelGGL(k_preprocess_bwd_planes_aa, grid, dim3(256), 0, s, a, dL_ddepths,
-                           aa_opacities);
-    else
-        hipLaunchKernelGGL(k_preprocess_bwd_planes, grid, dim3(256), 0, s, a, dL_ddepths);
-    return hipGetLastError();
-}
-
-hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &args, bool planes,
-                                            float *dL_ddepths, const GsrCameraBwdArgs &c,
-                                            hipStream_t s, const float *aa_opacities) {
-    if (args.P <= 0 || !c.partials || (!c.dL_dviewmatrix && !c.dL_dprojmatrix && !c.dL_dcampos))
+hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &args,
+                                     const GsrPreprocessBwdExtras &x, hipStream_t s) {
+    const GsrCameraBwdArgs *const c = x.camera;
+    if (c && (!c->partials || (!c->dL_dviewmatrix && !c->dL_dprojmatrix && !c->dL_dcampos)))
         return hipErrorInvalidValue;
+    if (args.P == 0) return hipSuccess;
     GsrPreprocessBwdArgs a = args;
     a.sh_vec4 = a.shs && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(a.dL_dsh) & 15) == 0;
     const unsigned blocks = (unsigned)gsr_preprocess_blocks(a.P);
-    if (planes && aa_opacities)
-        hipLaunchKernelGGL(k_preprocess_bwd_planes_camera_aa, dim3(blocks), dim3(256), 0, s, a,
-                           dL_ddepths, c.partials, aa_opacities);
-    else if (aa_opacities)
-        hipLaunchKernelGGL(k_preprocess_bwd_camera_aa, dim3(blocks), dim3(256), 0, s, a,
-                           c.partials, aa_opacities);
-    else if (planes)
-        hipLaunchKernelGGL(k_preprocess_bwd_planes_camera, dim3(blocks), dim3(256), 0, s, a,
-                           dL_ddepths, c.partials);
-    else
-        hipLaunchKernelGGL(k_preprocess_bwd_camera, dim3(blocks), dim3(256), 0, s, a, c.partials);
+    const float *const op = x.aa_opacities;
+    float *const part = c ? c->partials : nullptr;
+    auto launch = [&](auto kernel, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, a, more...);
+    };
+    switch ((x.planes ? 1 : 0) | (c ? 2 : 0) | (op ? 4 : 0)) {
+        case 0: launch(k_preprocess_bwd); break;
+        case 1: launch(k_preprocess_bwd_planes, x.dL_ddepths); break;
+        case 2: launch(k_preprocess_bwd_camera, part); break;
+        case 3: launch(k_preprocess_bwd_planes_camera, x.dL_ddepths, part); break;
+        case 4: launch(k_preprocess_bwd_aa, op); break;
+        case 5: launch(k_preprocess_bwd_planes_aa, x.dL_ddepths, op); break;
+        case 6: launch(k_preprocess_bwd_camera_aa, part, op); break;
+        case 7: launch(k_preprocess_bwd_planes_camera_aa, x.dL_ddepths, part, op); break;
+    }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_camera_finish, dim3(kCamSums), dim3(256), 0, s, c.partials, blocks,
-                       c.dL_dviewmatrix, c.dL_dprojmatrix, c.dL_dcampos);
+    if (e != hipSuccess || !c) return e;
+    hipLaunchKernelGGL(k_camera_finish, dim3(kCamSums), dim3(256), 0, s, part, blocks,
+                       c->dL_dviewmatrix, c->dL_dprojmatrix, c->dL_dcampos);
     return hipGetLastError();
 }

@@ -652,26 +652,29 @@ struct GsrPreprocessBwdArgs {
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dopacity, *dL_dcolors, *dL_dconic, *dL_dsh, *dL_dscales,
         *dL_drotations, *dL_dcov3D;
 };
-// aa_opacities (each of the three launchers; NULL: the plain kernel): the forward's opacities
-// [P], with which the launch is the kernel's antialiased twin (k_preprocess_bwd*_aa) -- the rows'
-// word 5 is then dL/do_eff of gsr_forward_filtered's effective opacity.
-hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a, hipStream_t s,
-                                     const float *aa_opacities = nullptr);
-// k_preprocess_bwd_planes: also reads word 9 of the rows, adds (vm[2], vm[6], vm[10]) times it to
-// dL_dmeans3D and writes it to dL_ddepths ([P], optional).
-hipError_t gsr_launch_preprocess_bwd_planes(const GsrPreprocessBwdArgs &a, float *dL_ddepths,
-                                            hipStream_t s, const float *aa_opacities = nullptr);
-// gsr_backward_camera (k_preprocess_bwd_camera / k_preprocess_bwd_planes_camera, then
-// k_camera_finish): the per-Gaussian backward, with the planes' term if `planes`, that also sums
-// the camera's 27 gradient entries over the Gaussians.  partials: workspace of
-// kCameraSums x gsr_preprocess_blocks(P) floats, [sum][block], every word written before it is
-// read.  The three outputs (device, 16 / 16 / 3 floats, at least one given) are written, the
-// entries the forward never reads as 0.  No atomics: the same 2D gradient rows give the same bits.
+// gsr_backward_camera: the sums of the camera's 27 gradient entries over the Gaussians.  partials:
+// workspace of kCameraSums x gsr_preprocess_blocks(P) floats, [sum][block], every word written
+// before it is read.  The three outputs (device, 16 / 16 / 3 floats, at least one given) are
+// written, the entries the forward never reads as 0.  No atomics: the same 2D gradient rows give
+// the same bits.
 constexpr int kCameraSums = 27;
 struct GsrCameraBwdArgs {
     float *partials;
     float *dL_dviewmatrix, *dL_dprojmatrix, *dL_dcampos;
 };
-hipError_t gsr_launch_preprocess_bwd_camera(const GsrPreprocessBwdArgs &a, bool planes,
-                                            float *dL_ddepths, const GsrCameraBwdArgs &c,
-                                            hipStream_t s, const float *aa_opacities = nullptr);
+// What a per-Gaussian backward adds to the plain one; the three flags pick one of the eight
+// k_preprocess_bwd* kernels.
+struct GsrPreprocessBwdExtras {
+    // the planes' term: also reads word 9 of the rows, adds (vm[2], vm[6], vm[10]) times it to
+    // dL_dmeans3D and writes it to dL_ddepths ([P], optional; not read without `planes`)
+    bool planes = false;
+    float *dL_ddepths = nullptr;
+    // NULL, or the camera instantiation, which k_camera_finish follows
+    const GsrCameraBwdArgs *camera = nullptr;
+    // NULL, or the forward's opacities [P]: the antialiased twin (k_preprocess_bwd*_aa) -- the
+    // rows' word 5 is then dL/do_eff of gsr_forward_filtered's effective opacity
+    const float *aa_opacities = nullptr;
+};
+// hipErrorInvalidValue for a camera without partials or without an output; P == 0 launches nothing.
+hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a,
+                                     const GsrPreprocessBwdExtras &x, hipStream_t s);

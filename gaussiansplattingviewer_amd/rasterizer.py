@@ -105,6 +105,43 @@ def _as_dev(t, device, shape_hint: str):
     return t.contiguous()
 
 
+def _scene_structs(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
+                   cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree,
+                   campos, prefiltered, debug):
+    """The inputs both directions share, as the library takes them: (device, device index, P,
+    gsr_gaussians, gsr_raster_settings of a whole frame, the device tensors the two point into:
+    hold them while the structs are in use)."""
+    device = _device_of(means3D)
+    dev_index = device.index if device.index is not None else torch.cuda.current_device()
+    P = int(means3D.size(0))
+    means3D = _as_dev(means3D, device, "P,3")
+    opacities = _as_dev(opacities, device, "P,1")
+    scales = _as_dev(scales, device, "P,3")
+    rotations = _as_dev(rotations, device, "P,4")
+    cov3D_precomp = _as_dev(cov3D_precomp, device, "P,6")
+    colors_precomp = _as_dev(colors_precomp, device, "P,3")
+    sh = _as_dev(sh, device, "P,M,3")
+    bg = _as_dev(bg, device, "3")
+    viewmatrix = _as_dev(viewmatrix, device, "4,4")
+    projmatrix = _as_dev(projmatrix, device, "4,4")
+    campos = _as_dev(campos, device, "3")
+    M = 0
+    if sh is not None:
+        M = int(sh.size(1)) if sh.ndimension() == 3 else int(sh.numel() // max(P, 1) // 3)
+    g = _lib.GsrGaussians(P=P, D=int(degree), M=M, scale_modifier=float(scale_modifier),
+                          means3D=_lib.ptr(means3D), scales=_lib.ptr(scales),
+                          rotations=_lib.ptr(rotations), opacities=_lib.ptr(opacities),
+                          shs=_lib.ptr(sh), colors_precomp=_lib.ptr(colors_precomp),
+                          cov3D_precomp=_lib.ptr(cov3D_precomp))
+    st = _lib.GsrRasterSettings(image_width=W, image_height=H, tanfovx=float(tanfovx),
+                                tanfovy=float(tanfovy), viewmatrix=_lib.ptr(viewmatrix),
+                                projmatrix=_lib.ptr(projmatrix), campos=_lib.ptr(campos),
+                                bg=_lib.ptr(bg), tile_row_begin=0, tile_row_end=0,
+                                prefiltered=int(bool(prefiltered)), debug=int(bool(debug)))
+    return device, dev_index, P, g, st, (means3D, opacities, scales, rotations, cov3D_precomp,
+                                         colors_precomp, sh, bg, viewmatrix, projmatrix, campos)
+
+
 class ForwardResult(NamedTuple):
     """Everything one native forward produced (color/radii plus optional intermediates)."""
     num_rendered: int
@@ -162,25 +199,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     if antialiasing and shading != _lib.GSR_SHADE_SPLAT:
         raise RuntimeError("antialiasing belongs to the splat composite: not available with "
                            f"shading {shading}")
-    device = _device_of(means3D)
-    dev_index = device.index if device.index is not None else torch.cuda.current_device()
-    P = int(means3D.size(0))
     H, W = int(image_height), int(image_width)
-    means3D = _as_dev(means3D, device, "P,3")
-    opacities = _as_dev(opacities, device, "P,1")
-    scales = _as_dev(scales, device, "P,3")
-    rotations = _as_dev(rotations, device, "P,4")
-    cov3D_precomp = _as_dev(cov3D_precomp, device, "P,6")
-    colors_precomp = _as_dev(colors_precomp, device, "P,3")
-    sh = _as_dev(sh, device, "P,M,3")
-    bg = _as_dev(bg, device, "3")
-    viewmatrix = _as_dev(viewmatrix, device, "4,4")
-    projmatrix = _as_dev(projmatrix, device, "4,4")
-    campos = _as_dev(campos, device, "3")
-
-    M = 0
-    if sh is not None:
-        M = int(sh.size(1)) if sh.ndimension() == 3 else int(sh.numel() // max(P, 1) // 3)
+    device, dev_index, P, g, st, held = _scene_structs(
+        bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,
+        viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, debug)
 
     gy = (H + 15) // 16
     if tile_rows is None:
@@ -224,16 +246,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
         else:
             raise ValueError(f"unknown extra output {name!r}")
 
-    g = _lib.GsrGaussians(P=P, D=int(degree), M=M, scale_modifier=float(scale_modifier),
-                          means3D=_lib.ptr(means3D), scales=_lib.ptr(scales),
-                          rotations=_lib.ptr(rotations), opacities=_lib.ptr(opacities),
-                          shs=_lib.ptr(sh), colors_precomp=_lib.ptr(colors_precomp),
-                          cov3D_precomp=_lib.ptr(cov3D_precomp))
-    st = _lib.GsrRasterSettings(image_width=W, image_height=H, tanfovx=float(tanfovx),
-                                tanfovy=float(tanfovy), viewmatrix=_lib.ptr(viewmatrix),
-                                projmatrix=_lib.ptr(projmatrix), campos=_lib.ptr(campos),
-                                bg=_lib.ptr(bg), tile_row_begin=rb, tile_row_end=re,
-                                prefiltered=int(bool(prefiltered)), debug=int(bool(debug)))
+    st.tile_row_begin, st.tile_row_end = rb, re
     out = _lib.GsrOutputs(color=color.data_ptr(),
                           radii=radii.data_ptr() if P and radii is not None else None)
     for name, t in ext.items():
@@ -243,35 +256,22 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
         stream = torch.cuda.current_stream(device).cuda_stream
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
+    head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out))
     with torch.cuda.device(dev_index):
-        if antialiasing:
+        if shading != _lib.GSR_SHADE_SPLAT:
+            _lib.check(lib.gsr_forward_shaded(*head, int(shading), ctypes.c_void_p(stream)),
+                       "gsr_forward_shaded")
+        elif not (depth_planes or surface_planes or antialiasing):
+            _lib.check(lib.gsr_forward(*head, ctypes.c_void_p(stream)), "gsr_forward")
+        else:  # NULL for each struct the call does without
             planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
             surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
             _lib.check(_lib.filtered_fns(lib)[0](
-                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
-                ctypes.byref(planes) if depth_planes else None,
+                *head, ctypes.byref(planes) if depth_planes else None,
                 ctypes.byref(surface) if surface_planes else None,
-                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing))),
+                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
+                if antialiasing else None,
                 ctypes.c_void_p(stream)), "gsr_forward_filtered")
-        elif surface_planes:
-            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
-            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
-            _lib.check(_lib.forward_surface_fn(lib)(
-                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
-                ctypes.byref(planes) if depth_planes else None, ctypes.byref(surface),
-                ctypes.c_void_p(stream)), "gsr_forward_surface")
-        elif depth_planes:
-            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
-            _lib.check(_lib.forward_depth_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st),
-                                                  ctypes.byref(out), ctypes.byref(planes),
-                                                  ctypes.c_void_p(stream)), "gsr_forward_depth")
-        elif shading == _lib.GSR_SHADE_SPLAT:
-            _lib.check(lib.gsr_forward(ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out),
-                                       ctypes.c_void_p(stream)), "gsr_forward")
-        else:
-            _lib.check(lib.gsr_forward_shaded(ctx, ctypes.byref(g), ctypes.byref(st),
-                                              ctypes.byref(out), int(shading),
-                                              ctypes.c_void_p(stream)), "gsr_forward_shaded")
     return ForwardResult(int(out.num_rendered), color, radii, ext)
 
 
@@ -288,16 +288,19 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     upstream's units, z = 0), dL_dopacity (P, 1), dL_dcolors, dL_dcov3D, dL_dsh (with SHs),
     dL_dscales and dL_drotations (with scales and rotations); conic=True adds dL_dconic (P, 3).
 
-    With dL_ddepth_map, dL_dinv_depth_map or dL_dfinal_T ((H, W) each, None = unused), or
-    depths=True, the call is `gsr_backward_planes`: the planes' gradients join the image's
-    (dL_dout_color may then be None; H, W come from the first plane given), and depths=True adds
-    dL_ddepths (P,), dL/dz through the features z and 1 / z only.
+    With anything below the call is `gsr_backward_filtered`, with NULL for what is not asked for
+    (which makes it `gsr_backward_planes` or `gsr_backward_camera`, include/gsr.h).
 
-    camera=True: the call is `gsr_backward_camera` and adds dL_dviewmatrix (4, 4), dL_dprojmatrix
-    (4, 4), both in the inputs' (column-major) layout, and dL_dcampos (3,).
+    dL_ddepth_map, dL_dinv_depth_map or dL_dfinal_T ((H, W) each, None = unused), or depths=True:
+    the planes' gradients join the image's (dL_dout_color may then be None; H, W come from the
+    first plane given), and depths=True adds dL_ddepths (P,), dL/dz through the features z and
+    1 / z only.
 
-    antialiasing=True: the call is `gsr_backward_filtered`, the backward of the forward with the
-    same argument, with whatever of the planes and the camera is asked for."""
+    camera=True adds dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4), both in the inputs'
+    (column-major) layout, and dL_dcampos (3,).
+
+    antialiasing=True: the backward of the forward with the same argument, with whatever of the
+    planes and the camera is asked for."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
@@ -308,9 +311,6 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     if dL_dout_color is not None and (dL_dout_color.ndimension() != 3 or
                                       dL_dout_color.size(0) != 3):
         raise RuntimeError("dL_dout_color must have dimensions (3, H, W)")
-    device = _device_of(means3D)
-    dev_index = device.index if device.index is not None else torch.cuda.current_device()
-    P = int(means3D.size(0))
     if dL_dout_color is not None:
         H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     else:
@@ -319,42 +319,21 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     for n, t in plane_grads.items():
         if t.ndimension() != 2 or tuple(t.shape) != (H, W):
             raise RuntimeError(f"{n} must have dimensions (H, W) = ({H}, {W})")
-    means3D = _as_dev(means3D, device, "P,3")
-    opacities = _as_dev(opacities, device, "P,1")
-    scales = _as_dev(scales, device, "P,3")
-    rotations = _as_dev(rotations, device, "P,4")
-    cov3D_precomp = _as_dev(cov3D_precomp, device, "P,6")
-    colors_precomp = _as_dev(colors_precomp, device, "P,3")
-    sh = _as_dev(sh, device, "P,M,3")
-    bg = _as_dev(bg, device, "3")
-    viewmatrix = _as_dev(viewmatrix, device, "4,4")
-    projmatrix = _as_dev(projmatrix, device, "4,4")
-    campos = _as_dev(campos, device, "3")
+    device, dev_index, P, g, st, held = _scene_structs(
+        bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,
+        viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, False, debug)
     dL = _as_dev(dL_dout_color, device, "3,H,W")
-    M = 0
-    if sh is not None:
-        M = int(sh.size(1)) if sh.ndimension() == 3 else int(sh.numel() // max(P, 1) // 3)
     f32 = dict(dtype=torch.float32, device=device)
     grads = {"dL_dmeans3D": torch.zeros((P, 3), **f32), "dL_dmeans2D": torch.zeros((P, 3), **f32),
              "dL_dopacity": torch.zeros((P, 1), **f32), "dL_dcolors": torch.zeros((P, 3), **f32),
              "dL_dcov3D": torch.zeros((P, 6), **f32)}
     if conic:
         grads["dL_dconic"] = torch.zeros((P, 3), **f32)
-    if sh is not None:
-        grads["dL_dsh"] = torch.zeros((P, M, 3), **f32)
-    if scales is not None:
+    if g.shs:
+        grads["dL_dsh"] = torch.zeros((P, g.M, 3), **f32)
+    if g.scales:
         grads["dL_dscales"] = torch.zeros((P, 3), **f32)
         grads["dL_drotations"] = torch.zeros((P, 4), **f32)
-    g = _lib.GsrGaussians(P=P, D=int(degree), M=M, scale_modifier=float(scale_modifier),
-                          means3D=_lib.ptr(means3D), scales=_lib.ptr(scales),
-                          rotations=_lib.ptr(rotations), opacities=_lib.ptr(opacities),
-                          shs=_lib.ptr(sh), colors_precomp=_lib.ptr(colors_precomp),
-                          cov3D_precomp=_lib.ptr(cov3D_precomp))
-    st = _lib.GsrRasterSettings(image_width=W, image_height=H, tanfovx=float(tanfovx),
-                                tanfovy=float(tanfovy), viewmatrix=_lib.ptr(viewmatrix),
-                                projmatrix=_lib.ptr(projmatrix), campos=_lib.ptr(campos),
-                                bg=_lib.ptr(bg), tile_row_begin=0, tile_row_end=0,
-                                prefiltered=0, debug=int(bool(debug)))
     inp = _lib.GsrBackwardInputs(dL_dcolor=_lib.ptr(dL))
     out = _lib.GsrGradients(**{n: _lib.ptr(t) for n, t in grads.items()})
     plane_grads = {n: _as_dev(t, device, "H,W") for n, t in plane_grads.items()}
@@ -368,37 +347,22 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     if camera:
         cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
+    head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
     with torch.cuda.device(dev_index):
-        if antialiasing:
+        if not (plane_grads or depths or camera or antialiasing):
+            _lib.check(_lib.backward_fn(lib)(*head, ctypes.byref(out), ctypes.c_void_p(stream)),
+                       "gsr_backward")
+        else:  # NULL for each struct the call does without
             planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
                                             dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
             cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
             _lib.check(_lib.filtered_fns(lib)[1](
-                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
-                ctypes.byref(planes) if plane_grads or depths else None,
+                *head, ctypes.byref(planes) if plane_grads or depths else None,
                 ctypes.byref(cg) if camera else None,
-                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing))),
+                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
+                if antialiasing else None,
                 ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_filtered")
             grads.update(cam)
-        elif camera:
-            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
-                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
-            cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
-            _lib.check(_lib.backward_camera_fn(lib)(
-                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp),
-                ctypes.byref(planes) if plane_grads or depths else None, ctypes.byref(cg),
-                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_camera")
-            grads.update(cam)
-        elif plane_grads or depths:
-            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
-                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
-            _lib.check(_lib.backward_planes_fn(lib)(
-                ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp), ctypes.byref(planes),
-                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_planes")
-        else:
-            _lib.check(_lib.backward_fn(lib)(ctx, ctypes.byref(g), ctypes.byref(st),
-                                             ctypes.byref(inp), ctypes.byref(out),
-                                             ctypes.c_void_p(stream)), "gsr_backward")
     return grads
 
 
@@ -444,6 +408,103 @@ def replay_snapshot(path: str = SNAPSHOT_FILE, device=None):
     return _C.rasterize_gaussians(*args)
 
 
+PLANE_NAMES = ("depth_map", "inv_depth_map", "final_T")
+
+
+def _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """`_C.rasterize_gaussians`'s 19 arguments; absent inputs travel as empty tensors, as
+    upstream's __init__.py passes them."""
+    none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
+    return (rs.bg, means3D, none(colors_precomp), opacities, none(scales), none(rotations),
+            rs.scale_modifier, none(cov3Ds_precomp), rs.viewmatrix, rs.projmatrix, rs.tanfovx,
+            rs.tanfovy, rs.image_height, rs.image_width, none(sh), rs.sh_degree, rs.campos,
+            rs.prefiltered, rs.debug)
+
+
+def _saved(args):
+    """The tensors of `_pack`'s tuple a backward needs: means3D, sh, colors_precomp, opacities,
+    scales, rotations, cov3Ds_precomp."""
+    return args[1], args[14], args[2], args[3], args[4], args[5], args[7]
+
+
+def _forward(args, rs, planes: bool):
+    """One frame of `_pack`'s arguments -> (num_rendered, color, radii, planes): PLANE_NAMES'
+    tensors, or () without `planes`.  Through `_C`: upstream's entry for the plain frame, its
+    shaded twin, the general entry for the rest; under GSR_LIB (an A/B build: `_C` links the
+    in-tree library) by ctypes."""
+    if not _lib._native_shares_library():
+        res = rasterize_gaussians_native(*args, extras=PLANE_NAMES if planes else (),
+                                         shading=rs.shading, antialiasing=rs.antialiasing)
+        return (res.num_rendered, res.color, res.radii,
+                tuple(res.extras[n] for n in PLANE_NAMES) if planes else ())
+    from . import _C
+    if planes or rs.antialiasing:
+        num_rendered, color, radii, *maps = _C.rasterize_gaussians_ext(
+            *args, int(rs.shading), planes, bool(rs.antialiasing))
+        return num_rendered, color, radii, tuple(maps) if planes else ()
+    if rs.shading:  # upstream's 19 arguments and the shading
+        num_rendered, color, radii, *_ = _C.rasterize_gaussians_shaded(*args, int(rs.shading))
+    else:
+        num_rendered, color, radii, *_ = _C.rasterize_gaussians(*args)
+    return num_rendered, color, radii, ()
+
+
+_GRADIENT_ORDER = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D",
+                   "dL_dsh", "dL_dscales", "dL_drotations") + _lib.CAMERA_GRADIENT_NAMES
+
+
+def _backward(rs, saved, grads, camera=None):
+    """The gradients of one frame.  saved: `_saved`'s seven; grads: those of (color, depth_map,
+    inv_depth_map, final_T), None = unused; camera: None, or the (viewmatrix, projmatrix, campos)
+    to differentiate by, which the frame was rendered with.  Returns `_GRADIENT_ORDER`'s eleven,
+    the camera's three None without `camera`.  Through `_C`: upstream's entry when only the
+    image's gradient is asked for, else the general one; under GSR_LIB by ctypes."""
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
+    viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if not _lib._native_shares_library():
+        g = rasterize_gaussians_backward_native(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
+            cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree,
+            campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
+            dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing)
+        return tuple(g.get(n) for n in _GRADIENT_ORDER)
+    from . import _C
+    e = torch.empty(0)
+    if camera is None and not rs.antialiasing and all(t is None for t in grads[1:]):
+        # (radii, num_rendered and the three buffers: accepted and ignored)
+        return _C.rasterize_gaussians_backward(
+            rs.bg, means3D, e, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds,
+            viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree, campos, e,
+            0, e, e, rs.debug, opacities) + (None,) * 3
+    if camera is not None:
+        viewmatrix, projmatrix, campos = (_as_dev(t.detach(), means3D.device, "")
+                                          for t in camera)
+    g = _C.rasterize_gaussians_backward_ext(
+        rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
+        viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
+        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing))
+    return g if camera is not None else g[:8] + (None,) * 3
+
+
+def _input_grads(has_means2D, saved, g):
+    """`_backward`'s result as a Function's nine: the gradients in input order (means3D, means2D,
+    sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, None); None for absent
+    inputs.  means2D's is upstream's screen-space gradient, (P, 3) with z = 0 (densification
+    reads it)."""
+    _, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
+    d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = g[:8]
+    has = lambda t: t.numel() != 0  # noqa: E731
+    return (d_means3D, d_means2D if has_means2D else None,
+            d_sh.reshape(sh.shape) if has(sh) else None,
+            d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
+            d_scales if has(scales) else None, d_rot if has(rotations) else None,
+            d_cov3D if has(cov3Ds) else None, None)
+
+
+def _contiguous(grads):
+    return [None if t is None else t.contiguous() for t in grads]
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """upstream `_RasterizeGaussians`: packs the settings into `_C.rasterize_gaussians`'s
     argument tuple and keeps (color, radii) of its 6-tuple; `backward` hands the saved inputs and
@@ -453,16 +514,11 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                 cov3Ds_precomp, raster_settings):
-        from . import _C
         # means2D only carries screen-space gradients, as upstream
         ctx.has_means2D = isinstance(means2D, torch.Tensor)
         rs = raster_settings
-        # absent inputs travel as empty tensors, as upstream's __init__.py passes them
-        none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
-        args = (rs.bg, means3D, none(colors_precomp), opacities, none(scales), none(rotations),
-                rs.scale_modifier, none(cov3Ds_precomp), rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, none(sh), rs.sh_degree,
-                rs.campos, rs.prefiltered, rs.debug)
+        args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
+                     cov3Ds_precomp)
         # debug (upstream __init__.py): the arguments are copied to the host first, and a
         # forward that raises leaves them in SNAPSHOT_FILE for replay_snapshot()
         cpu_args = _cpu_copy(args) if rs.debug else None
@@ -470,17 +526,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise RuntimeError("antialiasing belongs to the splat composite: not available with "
                                f"shading {rs.shading}")
         try:
-            if not _lib._native_shares_library():
-                # GSR_LIB (an A/B build): `_C` links the in-tree library, so render by ctypes
-                num_rendered, color, radii, _ = rasterize_gaussians_native(
-                    *args, shading=rs.shading, antialiasing=rs.antialiasing)
-            elif rs.antialiasing:  # (the planes it also returns are dropped)
-                num_rendered, color, radii, *_ = _C.rasterize_gaussians_filtered(*args, True)
-            elif rs.shading:  # upstream's 19 arguments and the shading
-                num_rendered, color, radii, geom, binning, img = \
-                    _C.rasterize_gaussians_shaded(*args, int(rs.shading))
-            else:
-                num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(*args)
+            num_rendered, color, radii, _ = _forward(args, rs, False)
         except Exception:
             if cpu_args is not None:
                 torch.save(cpu_args, SNAPSHOT_FILE)
@@ -489,57 +535,20 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         ctx.num_rendered = num_rendered
         ctx.raster_settings = rs
-        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
-                              none(rotations), none(cov3Ds_precomp), radii)
+        ctx.save_for_backward(*_saved(args))
         ctx.mark_non_differentiable(radii)
         return color, radii
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii):
-        """Gradients in input order (means3D, means2D, sh, colors_precomp, opacities, scales,
-        rotations, cov3Ds_precomp, None); None for absent inputs.  means2D's is upstream's
-        screen-space gradient, (P, 3) with z = 0 (densification reads it)."""
+        """Gradients in input order (`_input_grads`)."""
         del grad_radii
         rs = ctx.raster_settings
         if rs.shading:
             raise RuntimeError("gaussiansplattingviewer_amd differentiates the splat composite "
                                f"only: no backward under shading {rs.shading}")
-        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, radii = ctx.saved_tensors
-        grad_color = grad_color.contiguous()
-        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
-            g = rasterize_gaussians_backward_native(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
-                cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
-                rs.sh_degree, rs.campos, rs.debug, antialiasing=rs.antialiasing)
-            z = lambda n: g.get(n)  # noqa: E731
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
-                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
-                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
-        elif rs.antialiasing:  # (the camera's three it also returns are dropped)
-            from . import _C
-            e = torch.empty(0)
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, *_ = \
-                _C.rasterize_gaussians_backward_filtered(
-                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
-                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug, grad_color, e, e, e, True)
-        else:
-            from . import _C
-            e = torch.empty(0)
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = \
-                _C.rasterize_gaussians_backward(
-                    rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier,
-                    cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh,
-                    rs.sh_degree, rs.campos, e, ctx.num_rendered, e, e, rs.debug, opacities)
-        has = lambda t: t.numel() != 0  # noqa: E731
-        return (d_means3D, d_means2D if ctx.has_means2D else None,
-                d_sh.reshape(sh.shape) if has(sh) else None,
-                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
-                d_scales if has(scales) else None, d_rot if has(rotations) else None,
-                d_cov3D if has(cov3Ds) else None, None)
-
-
-PLANE_NAMES = ("depth_map", "inv_depth_map", "final_T")
+        g = _backward(rs, ctx.saved_tensors, (grad_color.contiguous(), None, None, None))
+        return _input_grads(ctx.has_means2D, ctx.saved_tensors, g)
 
 
 class _RasterizeGaussiansPlanes(torch.autograd.Function):
@@ -558,71 +567,22 @@ class _RasterizeGaussiansPlanes(torch.autograd.Function):
             raise RuntimeError("depth_map / inv_depth_map come from the splat composite: not "
                                f"available with shading {rs.shading}")
         ctx.has_means2D = isinstance(means2D, torch.Tensor)
-        none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
-        args = (rs.bg, means3D, none(colors_precomp), opacities, none(scales), none(rotations),
-                rs.scale_modifier, none(cov3Ds_precomp), rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, none(sh), rs.sh_degree,
-                rs.campos, rs.prefiltered, rs.debug)
-        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
-            res = rasterize_gaussians_native(*args, extras=PLANE_NAMES,
-                                             antialiasing=rs.antialiasing)
-            color, radii = res.color, res.radii
-            planes = tuple(res.extras[n] for n in PLANE_NAMES)
-        elif rs.antialiasing:
-            from . import _C
-            _, color, radii, *planes = _C.rasterize_gaussians_filtered(*args, True)
-        else:
-            from . import _C
-            _, color, radii, *planes = _C.rasterize_gaussians_planes(*args)
+        args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
+                     cov3Ds_precomp)
+        _, color, radii, planes = _forward(args, rs, True)
         ctx.raster_settings = rs
-        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
-                              none(rotations), none(cov3Ds_precomp))
+        ctx.save_for_backward(*_saved(args))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not zeros
         return (color, radii, *planes)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_inv_depth, grad_final_T):
-        """Gradients in input order, as `_RasterizeGaussians.backward`."""
+        """Gradients in input order (`_input_grads`)."""
         del grad_radii
-        rs = ctx.raster_settings
-        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = ctx.saved_tensors
-        grads = [None if t is None else t.contiguous()
-                 for t in (grad_color, grad_depth, grad_inv_depth, grad_final_T)]
-        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
-            g = rasterize_gaussians_backward_native(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
-                cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
-                rs.sh_degree, rs.campos, rs.debug, dL_ddepth_map=grads[1],
-                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], antialiasing=rs.antialiasing)
-            z = lambda n: g.get(n)  # noqa: E731
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = (
-                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
-                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"))
-        elif rs.antialiasing:  # (the camera's three it also returns are dropped)
-            from . import _C
-            e = torch.empty(0)
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, *_ = \
-                _C.rasterize_gaussians_backward_filtered(
-                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
-                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug,
-                    *(e if t is None else t for t in grads), True)
-        else:
-            from . import _C
-            e = torch.empty(0)
-            d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot = \
-                _C.rasterize_gaussians_backward_planes(
-                    rs.bg, means3D, colors_precomp, opacities, scales, rotations,
-                    rs.scale_modifier, cov3Ds, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                    rs.tanfovy, sh, rs.sh_degree, rs.campos, rs.debug,
-                    *(e if t is None else t for t in grads))
-        has = lambda t: t.numel() != 0  # noqa: E731
-        return (d_means3D, d_means2D if ctx.has_means2D else None,
-                d_sh.reshape(sh.shape) if has(sh) else None,
-                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
-                d_scales if has(scales) else None, d_rot if has(rotations) else None,
-                d_cov3D if has(cov3Ds) else None, None)
+        g = _backward(ctx.raster_settings, ctx.saved_tensors,
+                      _contiguous((grad_color, grad_depth, grad_inv_depth, grad_final_T)))
+        return _input_grads(ctx.has_means2D, ctx.saved_tensors, g)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -640,10 +600,9 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         ctx.has_means2D = isinstance(means2D, torch.Tensor)
         ctx.raster_settings = rs
         ctx.set_materialize_grads(False)
-        none = lambda t: torch.empty(0) if t is None else t  # noqa: E731
-        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), opacities, none(scales),
-                              none(rotations), none(cov3Ds_precomp), viewmatrix, projmatrix,
-                              campos)
+        args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
+                     cov3Ds_precomp)
+        ctx.save_for_backward(*_saved(args), viewmatrix, projmatrix, campos)
         # (inside a Function's forward no graph is recorded: the inner Function saves nothing)
         inner = _RasterizeGaussiansPlanes if rs.depth_maps else _RasterizeGaussians
         out = inner.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
@@ -654,55 +613,24 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth=None, grad_inv_depth=None,
                  grad_final_T=None):
-        """Gradients in input order: the nine of `_RasterizeGaussians.backward`, then
-        viewmatrix's, projmatrix's and campos's."""
+        """Gradients in input order: the nine of `_input_grads`, then viewmatrix's, projmatrix's
+        and campos's."""
         del grad_radii
         rs = ctx.raster_settings
         if rs.shading:
             raise RuntimeError("gaussiansplattingviewer_amd differentiates the splat composite "
                                f"only: no backward under shading {rs.shading}")
-        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds, viewmatrix,
-         projmatrix, campos) = ctx.saved_tensors
-        grads = [None if t is None else t.contiguous()
-                 for t in (grad_color, grad_depth, grad_inv_depth, grad_final_T)]
+        *saved, viewmatrix, projmatrix, campos = ctx.saved_tensors
+        grads = _contiguous((grad_color, grad_depth, grad_inv_depth, grad_final_T))
         if all(t is None for t in grads):  # nothing reaches the outputs
             return (None,) * 12
-        if not _lib._native_shares_library():  # GSR_LIB (an A/B build): by ctypes
-            g = rasterize_gaussians_backward_native(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
-                cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh,
-                rs.sh_degree, campos, rs.debug, dL_ddepth_map=grads[1],
-                dL_dinv_depth_map=grads[2], dL_dfinal_T=grads[3], camera=True,
-                antialiasing=rs.antialiasing)
-            z = lambda n: g.get(n)  # noqa: E731
-            (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
-             d_proj, d_campos) = (
-                z("dL_dmeans2D"), z("dL_dcolors"), z("dL_dopacity"), z("dL_dmeans3D"),
-                z("dL_dcov3D"), z("dL_dsh"), z("dL_dscales"), z("dL_drotations"),
-                z("dL_dviewmatrix"), z("dL_dprojmatrix"), z("dL_dcampos"))
-        else:
-            from . import _C
-            e = torch.empty(0)
-            as_dev = lambda t: _as_dev(t.detach(), means3D.device, "")  # noqa: E731
-            (d_means2D, d_colors, d_opacity, d_means3D, d_cov3D, d_sh, d_scales, d_rot, d_view,
-             d_proj, d_campos) = (
-                _C.rasterize_gaussians_backward_filtered if rs.antialiasing
-                else _C.rasterize_gaussians_backward_camera)(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations,
-                rs.scale_modifier, cov3Ds, as_dev(viewmatrix), as_dev(projmatrix), rs.tanfovx,
-                rs.tanfovy, sh, rs.sh_degree, as_dev(campos), rs.debug,
-                *(e if t is None else t for t in grads), *((True,) if rs.antialiasing else ()))
-        has = lambda t: t.numel() != 0  # noqa: E731
+        g = _backward(rs, saved, grads, camera=(viewmatrix, projmatrix, campos))
         need = ctx.needs_input_grad
         like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731
-        return (d_means3D, d_means2D if ctx.has_means2D else None,
-                d_sh.reshape(sh.shape) if has(sh) else None,
-                d_colors if has(colors_precomp) else None, d_opacity.view_as(opacities),
-                d_scales if has(scales) else None, d_rot if has(rotations) else None,
-                d_cov3D if has(cov3Ds) else None, None,
-                like(d_view, viewmatrix) if need[9] else None,
-                like(d_proj, projmatrix) if need[10] else None,
-                like(d_campos, campos) if need[11] else None)
+        return (*_input_grads(ctx.has_means2D, saved, g),
+                like(g[8], viewmatrix) if need[9] else None,
+                like(g[9], projmatrix) if need[10] else None,
+                like(g[10], campos) if need[11] else None)
 
 
 class GaussianRasterizer(torch.nn.Module):

@@ -221,3 +221,123 @@ def test_rasterizer_reaches_native_entry_with_upstream_args(monkeypatch):
     assert a[14] is sh and a[12:14] == (H, W) and a[15] == 3
     assert a[2].numel() == 0 and a[7].numel() == 0  # colors_precomp, cov3D_precomp absent
     assert tuple(c2.shape) == (3, H, W) and tuple(r2.shape) == (P,)
+
+
+def _fake_C(monkeypatch, seen):
+    """Replace the `_C` entries the Functions call by fakes that record their arguments and
+    return tensors of the right shapes (no GPU in the CPU suite)."""
+    from gaussiansplattingviewer_amd import _C
+
+    def forward(name, n_args):
+        def fake(*args):
+            assert len(args) == n_args
+            seen.setdefault(name, []).append(args)
+            P, (H, W) = args[1].shape[0], args[12:14]
+            planes = n_args == 22 and args[20]
+            maps = [torch.full((H, W), float(i)) if planes else torch.empty(0) for i in range(3)]
+            return (7, torch.zeros(3, H, W), torch.ones(P, dtype=torch.int32), *maps)
+        return fake
+
+    def backward(name, n_args, means3D_at, sh_at):
+        def fake(*args):
+            assert len(args) == n_args
+            seen.setdefault(name, []).append(args)
+            P, M = args[means3D_at].shape[0], args[sh_at].shape[1]
+            g = tuple(torch.full(s, float(i)) for i, s in enumerate(
+                ((P, 3), (P, 3), (P, 1), (P, 3), (P, 6), (P, M, 3), (P, 3), (P, 4))))
+            if n_args == 22 and name.endswith("_ext"):
+                camera = args[20]
+                g += tuple(torch.full(s, 9.0) if camera else torch.empty(0)
+                           for s in ((4, 4), (4, 4), (3,)))
+            return g
+        return fake
+
+    monkeypatch.setattr(_C, "rasterize_gaussians", forward("rasterize_gaussians", 19))
+    monkeypatch.setattr(_C, "rasterize_gaussians_ext", forward("rasterize_gaussians_ext", 22))
+    monkeypatch.setattr(_C, "rasterize_gaussians_backward",
+                        backward("rasterize_gaussians_backward", 22, 1, 13))
+    monkeypatch.setattr(_C, "rasterize_gaussians_backward_ext",
+                        backward("rasterize_gaussians_backward_ext", 22, 1, 12))
+
+
+@pytest.mark.parametrize("depth_maps,antialiasing,camera", [
+    (False, False, False), (True, False, False), (False, True, False), (True, True, False),
+    (False, False, True), (True, True, True)])
+def test_functions_route_to_the_general_entries(depth_maps, antialiasing, camera, monkeypatch):
+    """GaussianRasterizer's three Functions reach `_C` with the request spelt out: the general
+    forward with (shading, planes, antialiasing) and the general backward with (camera,
+    antialiasing), gradients that are None as empty tensors; a plain frame still reaches upstream's
+    `_C.rasterize_gaussians` with its 19 arguments and upstream's backward."""
+    seen = {}
+    _fake_C(monkeypatch, seen)
+    P, H, W = 5, 4, 6
+    xyz, op = torch.zeros(P, 3, requires_grad=True), torch.ones(P, 1, requires_grad=True)
+    sc, rot = torch.ones(P, 3, requires_grad=True), torch.ones(P, 4, requires_grad=True)
+    sh = torch.zeros(P, 16, 3, requires_grad=True)
+    view, campos = torch.eye(4, requires_grad=camera), torch.zeros(3)
+    rs = GaussianRasterizationSettings(H, W, 0.5, 0.4, torch.zeros(3), 1.0, view, torch.eye(4), 3,
+                                       campos, False, False, depth_maps=depth_maps,
+                                       antialiasing=antialiasing)
+    out = GaussianRasterizer(rs)(means3D=xyz, means2D=None, opacities=op, shs=sh,
+                                 colors_precomp=None, scales=sc, rotations=rot,
+                                 cov3D_precomp=None)
+    assert len(out) == (5 if depth_maps else 2)
+    if depth_maps or antialiasing:
+        assert "rasterize_gaussians" not in seen
+        (a,) = seen["rasterize_gaussians_ext"]
+        assert a[19:] == (0, depth_maps, antialiasing)
+        assert a[1] is xyz and a[14] is sh and a[12:14] == (H, W) and a[2].numel() == 0
+    else:
+        assert "rasterize_gaussians_ext" not in seen
+        (a,) = seen["rasterize_gaussians"]
+        assert len(a) == 19 and a[1] is xyz and a[14] is sh and a[7].numel() == 0
+    if depth_maps:
+        assert [float(out[2 + i].detach()[0, 0]) for i in range(3)] == [0.0, 1.0, 2.0]
+    # the loss reads the image, and with depth_maps the first plane alone
+    loss = out[0].sum() + (out[2].sum() if depth_maps else 0.0)
+    loss.backward()
+    if depth_maps or antialiasing or camera:
+        assert "rasterize_gaussians_backward" not in seen
+        (b,) = seen["rasterize_gaussians_backward_ext"]
+        assert b[20:] == (camera, antialiasing)
+        assert tuple(b[16].shape) == (3, H, W)
+        assert tuple(b[17].shape) == ((H, W) if depth_maps else (0,))
+        assert b[18].numel() == 0 and b[19].numel() == 0
+        assert b[3] is not None and tuple(b[3].shape) == (P, 1) and b[15] is False
+    else:
+        assert "rasterize_gaussians_backward_ext" not in seen
+        (b,) = seen["rasterize_gaussians_backward"]
+        assert tuple(b[12].shape) == (3, H, W) and tuple(b[21].shape) == (P, 1)
+    # the fake's i-th tensor is filled with i: (means2D, colors, opacity, means3D, cov3D, sh, ...)
+    assert (xyz.grad == 3).all() and (op.grad == 2).all() and (sh.grad == 5).all()
+    assert (sc.grad == 6).all() and (rot.grad == 7).all()
+    if camera:
+        assert tuple(view.grad.shape) == (4, 4) and (view.grad == 9).all()
+    else:
+        assert view.grad is None
+
+
+ACCESSORS = {"forward_depth_fn": ("gsr_forward_depth",),
+             "forward_surface_fn": ("gsr_forward_surface",),
+             "backward_fn": ("gsr_backward",),
+             "backward_planes_fn": ("gsr_backward_planes",),
+             "backward_camera_fn": ("gsr_backward_camera",),
+             "filtered_fns": ("gsr_forward_filtered", "gsr_backward_filtered")}
+
+
+@pytest.mark.parametrize("accessor", sorted(ACCESSORS))
+def test_additive_entry_accessors(accessor):
+    """Each accessor returns the loaded library's own attribute(s), and says which symbol an
+    older build lacks."""
+    lib = _lib.load_library()
+    symbols = ACCESSORS[accessor]
+    got = getattr(_lib, accessor)(lib)
+    want = tuple(getattr(lib, s) for s in symbols)
+    assert (got if len(symbols) > 1 else (got,)) == want
+    for fn in want:
+        assert fn.restype is ctypes.c_int and fn.argtypes[0] is ctypes.c_void_p
+
+    class Old:  # (a build of ABI 4 from before the additions)
+        pass
+    with pytest.raises(RuntimeError, match=f"no {symbols[0]}"):
+        getattr(_lib, accessor)(Old())
