@@ -15,6 +15,12 @@ colors, cov6, W, H, dL, special).
   wide   4112 x 24 px = 257 x 2 tiles (more than 256 tile columns: the per-pair binning form, whose
          point list holds plain ids in row-major tile order), the lower row 8 px high; P = 3,000
          small Gaussians over the width
+  tall   24 x 4112 px = 2 x 257 tiles, the transpose of wide (more than 256 tile rows: the per-pair
+         form again, now for its rows), the right column 8 px wide; pixel y up to 4111 in the
+         blend and its backward; P = 3,000 small Gaussians over the height.  The camera keeps its
+         vertical field of view, so a pixel is 1 / 1696 world units here: the centres' spread and
+         the sizes are wide's in pixels (14 px either side of the short axis' centre), the sizes
+         1 .. 4 px
 
 The seeds are chosen so that grad_reference.project finds no Gaussian within rounding of a gate
 (asserted).  The composite's gates cannot be kept clear at this size -- `frame` has about 7 M
@@ -41,8 +47,8 @@ from gaussiansplattingviewer_amd.camera import cuda_camera_inputs, static_camera
 from gpu_helpers import run_oracle, scene_inputs
 
 F32 = np.float32
-NAMES = ("frame", "wall", "wide")
-SEEDS = {"frame": 1, "wall": 2, "wide": 3}
+NAMES = ("frame", "wall", "wide", "tall")
+SEEDS = {"frame": 1, "wall": 2, "wide": 3, "tall": 0}
 AA_SCENES = ("frame",)  # the scenes a test runs antialiased
 BIG = 4                 # frame: the large, faint Gaussians
 FRONT = 120             # wall: the near layer
@@ -50,12 +56,12 @@ FRONT = 120             # wall: the near layer
 # ---- the mask band: measured, not chosen ----------------------------------------------------------
 # ALPHA_F32_SPREAD: the largest relative difference in alpha = o G between a float32 and a float64
 # evaluation of grad_reference.composite's formula on the oracle's float32 records, over all (pixel,
-# splat) pairs of the three scenes with alpha within a factor 2 of 1/255, measured on the CPU
+# splat) pairs of the four scenes with alpha within a factor 2 of 1/255, measured on the CPU
 # (alpha_spread; test_frame_grad_reference.py re-measures it and holds the constant to within a
 # factor 2).  BAND = 8 x that, the project's margin for the kernel's rounding, which is of this
 # class; the power and T gates keep grad_reference's ratios to it (0.1 x and 100 x).
-#                                  frame     wall      wide
-ALPHA_F32_SPREAD = 1.3e-5        # 1.3e-5    1.2e-6    1.2e-6
+#                                  frame     wall      wide      tall
+ALPHA_F32_SPREAD = 1.3e-5        # 1.3e-5    1.2e-6    1.2e-6    2.6e-6
 BAND = gr.BOUND_FACTOR * ALPHA_F32_SPREAD
 MASK_CAP = 0.10           # at most this share of a scene's pixels masked ...
 QUADRANT_KEEP = 0.5       # ... and every quadrant keeps at least this share of its pixels inside
@@ -92,6 +98,11 @@ def build(name):
         W, H, D, bg = 4112, 24, 3, (0.2, 0.4, 0.6)
         tx = float(cuda_camera_inputs(static_camera(W, H))[3])  # tan of half the horizontal fov
         g = grad_scenes._gaussians(rng, 3000, 4.0 * tx, 1.4, 0.01, 0.04, 0.1, 0.9)
+    elif name == "tall":
+        W, H, D, bg = 24, 4112, 3, (0.2, 0.4, 0.6)
+        ty = float(cuda_camera_inputs(static_camera(W, H))[4])  # tan of half the vertical fov
+        u = 8.0 * ty / H  # world units per pixel at the origin's depth
+        g = grad_scenes._gaussians(rng, 3000, 14.0 * u, 4.0 * ty, 1.0 * u, 4.0 * u, 0.1, 0.9)
     else:
         raise KeyError(name)
     s = scene_inputs(g, static_camera(W, H), D, bg=bg, scale_modifier=1.0)
@@ -349,9 +360,11 @@ def reference(sc, kind, dtype=torch.float64, gates=None):
 
 
 # (scene, tile column, tile row, quadrant) of the localised image gradients: the single inside
-# quadrant of frame's bottom-right tile, a quadrant of a middle tile, and one in tile column 256
-# of wide
-PLACEMENTS = (("frame", 12, 8, 0), ("frame", 6, 4, 3), ("wide", 256, 0, 3))
+# quadrant of frame's bottom-right tile, a quadrant of a middle tile, one in tile column 256
+# of wide, and of tall one in the first tile row, one in a middle row of the 8 px wide right
+# column and one in the last, tile row 256
+PLACEMENTS = (("frame", 12, 8, 0), ("frame", 6, 4, 3), ("wide", 256, 0, 3),
+              ("tall", 0, 0, 1), ("tall", 1, 128, 2), ("tall", 0, 256, 3))
 
 
 def localized_reference(sc, tile_x, tile_y, quad, dtype=torch.float64, gates=None):
@@ -390,6 +403,10 @@ F32_SPREAD = {
     ("wide", "colour"): {"means3D": 8.4e-5, "means2D": 4.6e-4, "means2D_px": 6.7e-5,
                          "conic": 7.5e-6, "opacity": 3.1e-5, "rgb": 3.5e-5, "shs": 3.2e-5,
                          "scales": 2.8e-5, "rotations": 2.0e-5},
+    # (pixel distances at y up to 4111, as wide's at x)
+    ("tall", "colour"): {"means3D": 9.7e-5, "means2D": 1.1e-4, "means2D_px": 1.1e-4,
+                         "conic": 7.0e-5, "opacity": 7.1e-5, "rgb": 4.1e-5, "shs": 3.9e-5,
+                         "scales": 5.5e-5, "rotations": 4.9e-5},
     # colour + the three planes + the camera, camera_grad_reference.scene_gradients
     ("frame", "all"): {"means3D": 2.1e-6, "means2D": 1.7e-6, "opacity": 7.5e-7, "shs": 7.8e-7,
                        "scales": 1.0e-6, "rotations": 4.3e-6, "viewmatrix": 9.5e-8,
@@ -405,6 +422,9 @@ F32_SPREAD = {
     ("wide", "local"): {"means3D": 3.2e-5, "means2D": 3.3e-5, "means2D_px": 1.3e-5,
                         "conic": 2.3e-5, "opacity": 5.4e-6, "rgb": 8.7e-6, "shs": 8.7e-6,
                         "scales": 2.3e-5, "rotations": 2.4e-5},
+    ("tall", "local"): {"means3D": 1.6e-4, "means2D": 2.7e-4, "means2D_px": 1.8e-4,
+                        "conic": 1.5e-4, "opacity": 3.7e-5, "rgb": 5.1e-5, "shs": 5.1e-5,
+                        "scales": 1.5e-4, "rotations": 7.7e-5},
 }
 for _t in F32_SPREAD.values():
     if "rgb" in _t:

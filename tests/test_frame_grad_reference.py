@@ -40,6 +40,22 @@ def test_wide_holds_what_it_says():
     assert len(fs.outside_quadrants(sc)) == 2 * 257
 
 
+def test_tall_holds_what_it_says():
+    """The transpose of wide: 257 tile rows (the per-pair form for its rows), every tile with a
+    list, the right column's outer quadrants outside the image, a placement in the first, a
+    middle and the last tile row."""
+    sc = fs.get("tall")
+    orc = fs.oracle_of(sc)
+    r = orc["ranges"].astype(np.int64)
+    assert (sc["W"], sc["H"]) == (24, 4112) and (sc["H"] + 15) // 16 == 257 and len(r) == 514
+    assert (r[:, 1] > r[:, 0]).all()
+    out = fs.outside_quadrants(sc)
+    assert len(out) == 2 * 257 and {t % 2 for t, _ in out} == {1} and {q for _, q in out} == {1, 3}
+    rows = sorted(p[2] for p in fs.PLACEMENTS if p[0] == "tall")
+    assert rows[0] == 0 and 0 < rows[1] < 256 and rows[2] == 256
+    assert all((16 * tx + 8 * (q & 1) < sc["W"]) for n, tx, _, q in fs.PLACEMENTS if n == "tall")
+
+
 def test_wall_holds_what_it_says():
     """Where its waves stop, from the float64 contribution masks (fs.stops)."""
     sc = fs.get("wall")

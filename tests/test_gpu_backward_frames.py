@@ -1,7 +1,8 @@
 """The backward pass (gsr_backward and its planes, camera and antialiasing forms) on
 the device at frame scale, against float64 autograd on the scenes of frame_grad_scenes: many waves
 adding to one gradient row, quadrants wholly outside the image, waves that stop before the end of
-their list, the per-pair binning form (more than 256 tile columns), the rebuild's depth sort forms,
+their list, the per-pair binning form (more than 256 tile columns, more than 256 tile rows with
+pixel y up to 4111), the rebuild's depth sort forms,
 scratch buffers that shrink and grow again, the camera's sums over many live blocks.
 
 Per gradient tensor e = max|g_gpu - g_ref64| / max|g_ref64| (the camera's three: cam_err) must
@@ -12,9 +13,10 @@ gradients are zero at every pixel with a decision within frame_grad_scenes.BAND 
 a pixel adds nothing whichever way the device decides.
 
   1 the three checks of test_gpu_backward.py (blend alone, per-Gaussian alone, end to end by
-    ctypes; by `_C` on frame) on frame, wall and wide
+    ctypes; by `_C` on frame) on frame, wall, wide and tall
   2 an image gradient in one 8 x 8 quadrant: exact zeros for every Gaussian outside that tile's
-    list, the others within the bound relative to that quadrant's own largest gradient
+    list, the others within the bound relative to that quadrant's own largest gradient (tall: in
+    the first, a middle and the last tile row)
   3 wall: exact zeros from the blend for the Gaussians no pixel composites
   4 frame with planes, camera and antialiasing at once, then without antialiasing
   5 frame, colour + planes, under every depth sort form, without the blend cull, without the
