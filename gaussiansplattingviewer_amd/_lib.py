@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "gsr_tile_row_pairs", "gsr_frame_graph_stats", "gsr_get_option",
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
-    "gsr_forward_filtered", "gsr_backward_filtered",
+    "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -121,6 +121,11 @@ class GsrFilterSettings(ctypes.Structure):
     _fields_ = [("antialiasing", ctypes.c_int32)]
 
 
+class GsrBackwardOrder(ctypes.Structure):
+    """gsr_backward_order: gsr_backward_ordered's choice of how the sums over pixels are formed."""
+    _fields_ = [("deterministic", ctypes.c_int32)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -141,6 +146,8 @@ _ADDITIVE = {
                             GsrGradients),
     "gsr_backward_filtered": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
                               GsrFilterSettings, GsrGradients),
+    "gsr_backward_ordered": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                             GsrFilterSettings, GsrBackwardOrder, GsrGradients),
 }
 
 _lock = threading.Lock()
@@ -262,6 +269,11 @@ def filtered_fns(lib: ctypes.CDLL):
     """(gsr_forward_filtered, gsr_backward_filtered) of a loaded library; RuntimeError if that
     build does not have them."""
     return _optional_fn(lib, "gsr_forward_filtered / gsr_backward_filtered", "antialiasing needs")
+
+
+def backward_ordered_fn(lib: ctypes.CDLL):
+    """gsr_backward_ordered of a loaded library; RuntimeError if that build does not have it."""
+    return _optional_fn(lib, "gsr_backward_ordered", "a deterministic backward needs")
 
 
 def check(rc: int, what: str) -> int:

@@ -182,6 +182,12 @@ struct gsr_context {
     Buf<int32_t> bwd_radii{bufs};
     // gsr_backward_camera: the blocks' partial sums of the camera's 27 entries, [27][blocks]
     Buf<float> cam_partials{bufs};
+    // gsr_backward_ordered, deterministic (gsr_internal.h GsrDetBwdArgs): the Gaussians' first
+    // pairs (and the scan's block totals), the slots' sums (4 K x 9 or 10 floats, never zeroed) and
+    // their marks (4 K bytes, zeroed by every call); grown on demand, freed with the context
+    Buf<uint64_t> det_slab{bufs}, det_partials{bufs};
+    Buf<float> det_sums{bufs};
+    Buf<uint8_t> det_marks{bufs};
     // ... and the events around its three stages (rebuild, blend backward, per-Gaussian backward)
     // of the last backward run under gsr_set_timing (created by the first one; gsr_backward_times)
     hipEvent_t ev_bwd[4] = {};
@@ -1525,10 +1531,14 @@ int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
 // cam: gsr_backward_camera's struct, or NULL.  With one of its three buffers the per-Gaussian
 // backward is the camera instantiation (with or without the planes) and k_camera_finish follows
 // it, inside the third timed stage; without, nothing differs from the call without it.
+// deterministic: gsr_backward_ordered's mode -- the blend's backward stores every
+// (Gaussian, tile, quadrant)'s sums to a slot of its own and a gather fills the 2D gradient rows in
+// a fixed order, both inside the second timed stage; nothing else of the call differs.
 static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                     const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
                     const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
-                    const std::string &fn, bool antialiasing = false) {
+                    const std::string &fn, bool antialiasing = false,
+                    bool deterministic = false) {
     if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
     if (st->tile_row_begin != 0 || st->tile_row_end != 0)
         return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
@@ -1575,6 +1585,10 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
                      (size_t)kCameraSums * gsr_preprocess_blocks(P) * sizeof(float), s));
     GSR_TRY(grow(ctx, ctx->grad2d, (size_t)P * kGradRow * sizeof(float), s));
     GSR_TRY(grow(ctx, ctx->bwd_radii, (size_t)P * sizeof(int32_t), s));
+    if (deterministic) {
+        GSR_TRY(grow(ctx, ctx->det_slab, (size_t)P * sizeof(uint64_t), s));
+        GSR_TRY(grow(ctx, ctx->det_partials, (size_t)gsr_slab_blocks(P) * sizeof(uint64_t), s));
+    }
 
     // the rebuild: a forward without its blend, with upstream's lists, launched directly and
     // untimed; the context's options are the caller's again afterwards
@@ -1606,10 +1620,33 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         GSR_HIP(hipGetLastError(), what);
         return GSR_OK;
     };
-    GSR_TRY(mark(1));
-    GSR_HIP(hipMemsetAsync(ctx->grad2d.get(), 0, (size_t)P * kGradRow * sizeof(float), s),
-            "hipMemsetAsync(grad2d)");
     const gsr_context::LastFrame &l = ctx->last;
+    GsrDetBwdArgs da{};
+    if (deterministic) {
+        // the slots: one per (list entry, quadrant); the lists are upstream's, K = num_rendered
+        const uint64_t K = (uint64_t)l.list;
+        if (l.tight || l.list != l.K)
+            return fail(GSR_E_STATE, fn + ": the rebuild left tight lists");
+        if (K >= (1ull << 30))
+            return fail(GSR_E_INVALID, fn + ": deterministic needs num_rendered < 2^30, got " +
+                                           std::to_string(K));
+        const size_t sums = planes ? 10 : 9;
+        GSR_TRY(grow(ctx, ctx->det_marks, std::max<size_t>(4 * K, 1), s));
+        GSR_TRY(grow(ctx, ctx->det_sums, std::max<size_t>(4 * K * sums * sizeof(float), 1), s));
+        da = {ctx->strip_rect.get(), ctx->det_slab.get(), ctx->det_sums.get(),
+              ctx->det_marks.get(), (uint32_t)K};
+    }
+    GSR_TRY(mark(1));
+    if (deterministic) {
+        if (da.K > 0)
+            GSR_HIP(hipMemsetAsync(da.marks, 0, 4 * (size_t)da.K, s), "hipMemsetAsync(marks)");
+        GSR_HIP(gsr_launch_slab_scan(da.strip_rect, P, ctx->det_partials.get(),
+                                     ctx->det_slab.get(), s),
+                "slab scan launch");
+    } else {
+        GSR_HIP(hipMemsetAsync(ctx->grad2d.get(), 0, (size_t)P * kGradRow * sizeof(float), s),
+                "hipMemsetAsync(grad2d)");
+    }
     GsrBlendBwdArgs ba{};
     ba.ranges = ctx->ranges_local.get();
     ba.point_list = l.point_list;
@@ -1624,16 +1661,23 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     ba.cull = ctx->cull;
     ba.grad2d = ctx->grad2d.get();
     if (l.list > 0) {
-        if (planes) {
-            // z by Gaussian id from the rebuild's depth keys, as launch_blend hands them to the
-            // forward's planes: written by the rebuild's preprocess on s and only read since
-            const GsrPlaneBwdArgs pa{ctx->sort_keys.get(), pl->dL_ddepth_map,
-                                     pl->dL_dinv_depth_map, pl->dL_dfinal_T};
+        // z by Gaussian id from the rebuild's depth keys, as launch_blend hands them to the
+        // forward's planes: written by the rebuild's preprocess on s and only read since
+        GsrPlaneBwdArgs pa{};
+        if (planes)
+            pa = {ctx->sort_keys.get(), pl->dL_ddepth_map, pl->dL_dinv_depth_map,
+                  pl->dL_dfinal_T};
+        if (deterministic)
+            GSR_HIP(gsr_launch_blend_bwd_det(ba, planes ? &pa : nullptr, da, s),
+                    "blend backward launch");
+        else if (planes)
             GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s), "blend backward launch");
-        } else {
+        else
             GSR_HIP(gsr_launch_blend_bwd(ba, s), "blend backward launch");
-        }
     }
+    if (deterministic)  // every word of every row, zeros where nothing was stored
+        GSR_HIP(gsr_launch_grad_rows_gather(da, P, planes, ctx->grad2d.get(), s),
+                "gradient rows gather launch");
     GSR_TRY(mark(2));
     GSR_TRY(stage_check("stage blend backward"));
 
@@ -1715,6 +1759,23 @@ int gsr_backward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ra
                                        std::to_string(filter->antialiasing));
     if (!aa) return gsr_backward_camera(ctx, g, st, in, planes, camera, gr, stream);
     return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_filtered", true);
+}
+
+int gsr_backward_ordered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                         const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                         const gsr_backward_order *order, gsr_gradients *gr, void *stream) {
+    const int det = order ? order->deterministic : 0;
+    if (det != 0 && det != 1)
+        return fail(GSR_E_INVALID, "gsr_backward_ordered: deterministic must be 0 or 1, got " +
+                                       std::to_string(det));
+    if (!det) return gsr_backward_filtered(ctx, g, st, in, planes, camera, filter, gr, stream);
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_backward_ordered: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_ordered", aa != 0,
+                    true);
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

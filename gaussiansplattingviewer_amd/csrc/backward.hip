@@ -34,6 +34,12 @@
 //    body with kAA set (gsr_backward_filtered): the antialiased forward's opacity
 //    factor and its gradient through the 2D covariance.  The four kernels above compile as
 //    before (profiles/antialias_resources.txt).
+//  * k_blend_bwd_det_q, k_blend_bwd_planes_det_q, k_slab_*, k_grad_rows_gather -- the deterministic
+//    mode (gsr_backward_ordered): the blend's body with kDet set stores each (splat,
+//    quadrant)'s sums to a slot of its own, addressed from the Gaussian's tile rect and the scan of
+//    the rects' sizes, and marks it; the gather adds a Gaussian's marked slots in a fixed order, in
+//    double, into its row.  No atomics, no zeroing but the marks'.  The kernels above compile as
+//    before (profiles/backward_deterministic_resources.txt).
 #include "gsr_internal.h"
 
 #include <type_traits>
@@ -77,14 +83,21 @@ struct BwdSplatT<true> {
 
 // The body of both blend backward kernels.  kPlanes: p holds the planes' gradients and the depth
 // keys; a.dL_dcolor may be NULL.  Without it p is not read.
-template <bool kPlanes>
-__device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p) {
+// kDet (gsr_backward_ordered): the flush stores the sums to the (Gaussian, tile,
+// quadrant)'s own slot of d and marks it, instead of adding them to a.grad2d; without it d is not
+// read.
+template <bool kPlanes, bool kDet = false>
+__device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
+                                          const GsrDetBwdArgs &d = GsrDetBwdArgs{}) {
     using BwdSplat = BwdSplatT<kPlanes>;
     // per (splat, quadrant): the words 0..8 of a gradient row, and word 9 (dL/dz) with the planes
     constexpr int kSums = kPlanes ? 10 : 9;
     __shared__ BwdSplat s_spl_q[4][64];
     __shared__ uint32_t s_id_q[4][64];
     __shared__ float s_red_q[4][64 * kSums];
+    // kDet: the staged splat's slot (pair * 4 + quad), kNoSlot for one that must not be stored
+    constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+    __shared__ uint32_t s_slot_q[kDet ? 4 : 1][kDet ? 64 : 1];
 
     const uint32_t tile = blockIdx.x;
     if (tile >= a.n_tiles) return;
@@ -93,6 +106,7 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
     BwdSplat *const s_spl = s_spl_q[quad];
     uint32_t *const s_id = s_id_q[quad];
     float *const s_red = s_red_q[quad];
+    [[maybe_unused]] uint32_t *const s_slot = s_slot_q[kDet ? quad : 0];
     const uint32_t tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
     const int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
@@ -105,7 +119,7 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
 
     // Stages chunk `start` (the forward's gather, cull and in-order compaction); returns the
     // number of staged splats.  with_z (kPlanes, the back-to-front pass): also z by Gaussian id
-    // from the depth keys and 1 / z, once per staged splat.
+    // from the depth keys and 1 / z, once per staged splat; kDet: also the splat's slot.
     auto stage = [&](uint32_t start, auto with_z) {
         const uint32_t idx = start + (uint32_t)lane;
         const bool valid = idx < range.y;
@@ -131,6 +145,16 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
                 if constexpr (decltype(with_z)::value) {
                     const float z = __uint_as_float(p.z_bits[id]);
                     s_spl[slot].zf = make_float2(z, 1.0f / z);
+                }
+            }
+            if constexpr (kDet) {
+                if constexpr (decltype(with_z)::value) {
+                    const uint2 rc = d.strip_rect[id];
+                    const uint32_t cx = tx - (rc.x & 0xFFFFu), w = rc.x >> 16;
+                    const uint32_t cy = ty - (rc.y & 0xFFFFu), rows = rc.y >> 16;
+                    const uint64_t pair = d.slab[id] + (uint64_t)cy * w + cx;
+                    const bool ok = cx < w && cy < rows && pair < (uint64_t)d.K;
+                    s_slot[slot] = ok ? (uint32_t)pair * 4u + quad : kNoSlot;
                 }
             }
         }
@@ -181,7 +205,7 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
     float rr = g0 * a.bg[0] + g1 * a.bg[1] + g2 * a.bg[2];
     if constexpr (kPlanes) rr += gT;
     for (uint32_t c = chunks; c-- > 0u;) {
-        const int count = stage(range.x + 64u * c, std::bool_constant<kPlanes>{});
+        const int count = stage(range.x + 64u * c, std::bool_constant<kPlanes || kDet>{});
         // groups of 16 slots, back to front: lane 16 r + j keeps row r's share of the nine sums
         // of the splat in slot 16 kg + j
         for (int kg = (count - 1) >> 4; kg >= 0; --kg) {
@@ -250,7 +274,16 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
                 if ((touched >> slot) & 1u) {
                     const float *q4 = s_red + slot * 4 * kSums + word;
                     const float sum = (q4[0] + q4[kSums]) + (q4[2 * kSums] + q4[3 * kSums]);
-                    atomicAdd(&a.grad2d[(size_t)s_id[k_lo + slot] * kGradRow + word], sum);
+                    if constexpr (kDet) {
+                        // a plain store: the slot is this wave's alone, and written once
+                        const uint32_t to = s_slot[k_lo + slot];
+                        if (to != kNoSlot) {
+                            d.sums[(size_t)to * kSums + word] = sum;
+                            if (word == 0) d.marks[to] = 1;
+                        }
+                    } else {
+                        atomicAdd(&a.grad2d[(size_t)s_id[k_lo + slot] * kGradRow + word], sum);
+                    }
                 }
             }
         }
@@ -263,6 +296,122 @@ __global__ __launch_bounds__(256) void k_blend_bwd_q(const GsrBlendBwdArgs a) {
 __global__ __launch_bounds__(256) void k_blend_bwd_planes_q(const GsrBlendBwdArgs a,
                                                             const GsrPlaneBwdArgs p) {
     blend_bwd<true>(a, p);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_det_q(const GsrBlendBwdArgs a,
+                                                         const GsrDetBwdArgs d) {
+    blend_bwd<false, true>(a, GsrPlaneBwdArgs{}, d);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_det_q(const GsrBlendBwdArgs a,
+                                                                const GsrPlaneBwdArgs p,
+                                                                const GsrDetBwdArgs d) {
+    blend_bwd<true, true>(a, p, d);
+}
+
+// ---- the deterministic mode's slab scan and gather ------------------------------
+constexpr int kSlabPer = 4;                    // Gaussians per thread
+constexpr int kSlabBlock = 256 * kSlabPer;     // ... per block
+__device__ __forceinline__ uint32_t rect_tiles(uint2 rc) { return (rc.x >> 16) * (rc.y >> 16); }
+
+// The inclusive scan of v over the block's 256 threads (s_scan: 256 words), then a barrier.
+__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t *s_scan) {
+    s_scan[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t n = 1; n < 256; n <<= 1) {
+        const uint64_t add = threadIdx.x >= n ? s_scan[threadIdx.x - n] : 0ull;
+        __syncthreads();
+        s_scan[threadIdx.x] += add;
+        __syncthreads();
+    }
+    return s_scan[threadIdx.x];
+}
+
+// partials[b] = the rect tiles of block b's kSlabBlock Gaussians
+__global__ __launch_bounds__(256) void k_slab_reduce(const uint2 *__restrict__ strip_rect,
+                                                     int64_t P, uint64_t *partials) {
+    __shared__ uint64_t s_scan[256];
+    const int64_t i0 = (int64_t)blockIdx.x * kSlabBlock + (int64_t)threadIdx.x * kSlabPer;
+    uint64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < kSlabPer; ++j)
+        if (i0 + j < P) v += rect_tiles(strip_rect[i0 + j]);
+    const uint64_t incl = block_scan_incl(v, s_scan);
+    if (threadIdx.x == 255) partials[blockIdx.x] = incl;
+}
+// partials -> their exclusive scan, in place: one block, 256 entries at a time
+__global__ __launch_bounds__(256) void k_slab_scan_partials(uint64_t *partials, uint32_t blocks) {
+    __shared__ uint64_t s_scan[256];
+    uint64_t base = 0;
+    for (uint32_t b0 = 0; b0 < blocks; b0 += 256) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint64_t v = b < blocks ? partials[b] : 0ull;
+        const uint64_t incl = block_scan_incl(v, s_scan);
+        if (b < blocks) partials[b] = base + incl - v;
+        base += s_scan[255];
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(256) void k_slab_apply(const uint2 *__restrict__ strip_rect,
+                                                    int64_t P, const uint64_t *partials,
+                                                    uint64_t *slab) {
+    __shared__ uint64_t s_scan[256];
+    const int64_t i0 = (int64_t)blockIdx.x * kSlabBlock + (int64_t)threadIdx.x * kSlabPer;
+    uint32_t n[kSlabPer];
+    uint64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < kSlabPer; ++j) {
+        n[j] = i0 + j < P ? rect_tiles(strip_rect[i0 + j]) : 0u;
+        v += n[j];
+    }
+    uint64_t at = partials[blockIdx.x] + block_scan_incl(v, s_scan) - v;
+#pragma unroll
+    for (int j = 0; j < kSlabPer; ++j) {
+        if (i0 + j < P) slab[i0 + j] = at;
+        at += n[j];
+    }
+}
+
+// v of lane (lane ^ kMask), for the gather's tree (every lane of the wave active)
+template <int kMask>
+__device__ __forceinline__ double xor_d(double v) {
+    const int lo = __shfl_xor(__double2loint(v), kMask, 64);
+    const int hi = __shfl_xor(__double2hiint(v), kMask, 64);
+    return __hiloint2double(hi, lo);
+}
+
+// One row of 16 lanes per Gaussian (gsr_internal.h, gsr_launch_grad_rows_gather).
+template <int kSums>
+__global__ __launch_bounds__(256) void k_grad_rows_gather(const GsrDetBwdArgs d, int64_t P,
+                                                          float *grad2d) {
+    const int64_t id = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const uint32_t j = threadIdx.x & 15u;
+    uint64_t first = 0, slots = 0;
+    if (id < P) {
+        slots = 4ull * rect_tiles(d.strip_rect[id]);
+        first = 4ull * d.slab[id];
+        // (the rebuild's rects end at K; anything else is not read)
+        if (first + slots > 4ull * d.K) slots = 0;
+    }
+    double acc[kSums];
+#pragma unroll
+    for (int w = 0; w < kSums; ++w) acc[w] = 0.0;
+    for (uint64_t t = j; t < slots; t += 16) {
+        const uint64_t slot = first + t;
+        if (d.marks[slot] == 0) continue;
+        const float *src = d.sums + slot * kSums;
+#pragma unroll
+        for (int w = 0; w < kSums; ++w) acc[w] += (double)src[w];
+    }
+    float out = 0.0f;
+#pragma unroll
+    for (int w = 0; w < kSums; ++w) {
+        double v = acc[w];
+        v += xor_d<1>(v);
+        v += xor_d<2>(v);
+        v += xor_d<4>(v);
+        v += xor_d<8>(v);
+        out = j == (uint32_t)w ? (float)v : out;
+    }
+    if (id < P) grad2d[id * kGradRow + j] = out;
 }
 
 // ---- per Gaussian ------------------------------------------------------------------------------
@@ -491,6 +640,44 @@ hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneB
         return hipErrorInvalidValue;
     if (a.n_tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
+                                    const GsrDetBwdArgs &d, hipStream_t s) {
+    if (p && (!p->z_bits || (!p->dL_ddepth_map && !p->dL_dinv_depth_map && !p->dL_dfinal_T)))
+        return hipErrorInvalidValue;
+    if (!p && !a.dL_dcolor) return hipErrorInvalidValue;
+    if (!d.strip_rect || !d.slab || !d.sums || !d.marks || d.K >= (1u << 30))
+        return hipErrorInvalidValue;
+    if (a.n_tiles == 0) return hipSuccess;
+    if (p)
+        hipLaunchKernelGGL(k_blend_bwd_planes_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, *p, d);
+    else
+        hipLaunchKernelGGL(k_blend_bwd_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, d);
+    return hipGetLastError();
+}
+
+int64_t gsr_slab_blocks(int64_t P) { return (P + kSlabBlock - 1) / kSlabBlock; }
+
+hipError_t gsr_launch_slab_scan(const uint2 *strip_rect, int64_t P, uint64_t *partials,
+                                uint64_t *slab, hipStream_t s) {
+    if (P <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)gsr_slab_blocks(P);
+    hipLaunchKernelGGL(k_slab_reduce, dim3(blocks), dim3(256), 0, s, strip_rect, P, partials);
+    hipLaunchKernelGGL(k_slab_scan_partials, dim3(1), dim3(256), 0, s, partials, blocks);
+    hipLaunchKernelGGL(k_slab_apply, dim3(blocks), dim3(256), 0, s, strip_rect, P, partials, slab);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_grad_rows_gather(const GsrDetBwdArgs &d, int64_t P, bool planes,
+                                       float *grad2d, hipStream_t s) {
+    if (P <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((P + 15) / 16);
+    if (planes)
+        hipLaunchKernelGGL(k_grad_rows_gather<10>, dim3(blocks), dim3(256), 0, s, d, P, grad2d);
+    else
+        hipLaunchKernelGGL(k_grad_rows_gather<9>, dim3(blocks), dim3(256), 0, s, d, P, grad2d);
     return hipGetLastError();
 }
 

@@ -637,6 +637,38 @@ struct GsrPlaneBwdArgs {
 };
 hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
                                        hipStream_t s);
+// gsr_backward_ordered, deterministic (k_blend_bwd_det_q, k_blend_bwd_planes_det_q; DESIGN.md
+// 3k): no sum is added to a.grad2d.  In upstream's (untight) lists a Gaussian is listed in exactly
+// the tiles of its rect, so every (Gaussian, tile, quadrant) owns a slot,
+//   pair = slab[id] + (ty - row0) * w + (tx - x0),   slot = pair * 4 + quad,
+// with {x0 | w << 16, row0 | rows << 16} = strip_rect[id] of the whole frame and slab the exclusive
+// scan of w * rows in id order (its total is K, the list's length).  The wave stores its kSums
+// words (9, or 10 with the planes) to sums[slot * kSums ...] and sets marks[slot] = 1; marks
+// ([4 K] bytes) is zeroed by the caller, sums ([4 K * kSums] floats) needs no zeroing: a slot
+// without its mark is never read.  A staged splat whose tile lies outside its rect, or whose pair
+// is not below K, is not stored (it cannot happen with the rebuild's lists).  K < 2^30.
+struct GsrDetBwdArgs {
+    const uint2 *strip_rect;  // [P], the rebuild's
+    const uint64_t *slab;     // [P]
+    float *sums;
+    uint8_t *marks;
+    uint32_t K;
+};
+hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
+                                    const GsrDetBwdArgs &d, hipStream_t s);
+// slab[i] = sum over j < i of w_j * rows_j (strip_rect, 0 for a Gaussian without a rect), 64-bit;
+// partials: workspace of gsr_slab_blocks(P) uint64.  P == 0 launches nothing.
+int64_t gsr_slab_blocks(int64_t P);
+hipError_t gsr_launch_slab_scan(const uint2 *strip_rect, int64_t P, uint64_t *partials,
+                                uint64_t *slab, hipStream_t s);
+// k_grad_rows_gather: every word of grad2d's P rows from the slots.  A row of 16 lanes per
+// Gaussian: lane j adds the marked slots j, j + 16, ... of the Gaussian's 4 w rows slots in that
+// order (tile row-major within the rect, then quadrant), each sum from +0.0 in double; the 16 lanes
+// are combined by the fixed tree (xor 1, 2, 4, 8) and rounded once.  Words kSums..15 and the rows
+// of Gaussians without a rect or a mark are zeros: no memset of grad2d.  The order is a function
+// of the rect and the marks alone.
+hipError_t gsr_launch_grad_rows_gather(const GsrDetBwdArgs &d, int64_t P, bool planes,
+                                       float *grad2d, hipStream_t s);
 struct GsrPreprocessBwdArgs {
     int64_t P;
     int D, M;

@@ -33,12 +33,15 @@
 //                                       scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
 //                                       tanfovx, tanfovy, sh, sh_degree, campos, debug,
 //                                       dL_dout_color, dL_ddepth_map, dL_dinv_depth_map,
-//                                       dL_dfinal_T, camera, antialiasing)
+//                                       dL_dfinal_T, camera, antialiasing,
+//                                       deterministic = False)
 //       -> rasterize_gaussians_backward's 8-tuple, then dL_dviewmatrix [4,4], dL_dprojmatrix
 //          [4,4], dL_dcampos [3] (empty without `camera`)
 //     this package's own, every backward in one entry: gsr_backward_filtered, with the plane
 //     gradients only if one of the three is not empty (an empty gradient tensor is an unused
-//     one), the camera's only if `camera`, a filter only if `antialiasing`.  The two matrices'
+//     one), the camera's only if `camera`, a filter only if `antialiasing`; with
+//     `deterministic` gsr_backward_ordered, whose gradients have the same bits on every call
+//     (the trailing argument may be left out: the 22-argument call is unchanged).  The two matrices'
 //     gradients are in the inputs' layout (the 16 floats of the input, viewed (4, 4)).
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
@@ -253,7 +256,7 @@ Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tenso
 // which takes no plane gradient and is gsr_backward itself.
 Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
                          const torch::Tensor (&planes)[3], bool camera, bool antialiasing,
-                         bool upstream = false) {
+                         bool upstream = false, bool deterministic = false) {
     Scene sc(in);
     const bool has_color = dL_dout_color.defined() && dL_dout_color.numel() != 0;
     int64_t H = 0, W = 0;
@@ -296,6 +299,7 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         if (camera)
             cg = {d_view.data_ptr<float>(), d_proj.data_ptr<float>(), d_campos.data_ptr<float>()};
         const gsr_filter_settings fs{1};
+        const gsr_backward_order order{1};
         gsr_gradients gr{};
         gr.dL_dmeans3D = d_means3D.data_ptr<float>();
         gr.dL_dmeans2D = d_means2D.data_ptr<float>();
@@ -313,10 +317,16 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         int rc;
         {  // the rebuild waits for K (pinned memory), as the forward does
             pybind11::gil_scoped_release no_gil;
-            rc = upstream ? gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s)
-                          : gsr_backward_filtered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
-                                                  camera ? &cg : nullptr,
-                                                  antialiasing ? &fs : nullptr, &gr, s);
+            if (upstream)
+                rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
+            else if (deterministic)  // gsr_backward_ordered: bit-reproducible sums
+                rc = gsr_backward_ordered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
+                                          camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
+                                          &order, &gr, s);
+            else
+                rc = gsr_backward_filtered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
+                                           camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
+                                           &gr, s);
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_backward failed (", rc, "): ", gsr_last_error());
     }
@@ -354,12 +364,12 @@ Backward11 rasterize_gaussians_backward_ext(
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
     int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
     const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
-    const torch::Tensor &dL_dfinal_T, bool camera, bool antialiasing) {
+    const torch::Tensor &dL_dfinal_T, bool camera, bool antialiasing, bool deterministic) {
     const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
     return backward_impl({background, means3D, colors, opacities, scales, rotations,
                           scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                           sh, degree, campos, false, debug},
-                         dL_dout_color, planes, camera, antialiasing);
+                         dL_dout_color, planes, camera, antialiasing, false, deterministic);
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -413,8 +423,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, "
           "cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, sh, sh_degree, campos, debug, "
           "dL_dout_color, dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T (empty = unused), camera, "
-          "antialiasing -> rasterize_gaussians_backward's 8-tuple, then dL_dviewmatrix (4, 4), "
-          "dL_dprojmatrix (4, 4), dL_dcampos (3), empty without `camera`");
+          "antialiasing, deterministic = False (gsr_backward_ordered: the same bits on every "
+          "call) -> rasterize_gaussians_backward's 8-tuple, then dL_dviewmatrix (4, 4), "
+          "dL_dprojmatrix (4, 4), dL_dcampos (3), empty without `camera`",
+          pybind11::arg("bg"), pybind11::arg("means3D"), pybind11::arg("colors_precomp"),
+          pybind11::arg("opacities"), pybind11::arg("scales"), pybind11::arg("rotations"),
+          pybind11::arg("scale_modifier"), pybind11::arg("cov3D_precomp"),
+          pybind11::arg("viewmatrix"), pybind11::arg("projmatrix"), pybind11::arg("tanfovx"),
+          pybind11::arg("tanfovy"), pybind11::arg("sh"), pybind11::arg("sh_degree"),
+          pybind11::arg("campos"), pybind11::arg("debug"), pybind11::arg("dL_dout_color"),
+          pybind11::arg("dL_ddepth_map"), pybind11::arg("dL_dinv_depth_map"),
+          pybind11::arg("dL_dfinal_T"), pybind11::arg("camera"), pybind11::arg("antialiasing"),
+          pybind11::arg("deterministic") = false);
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -18,7 +18,9 @@ final_T, differentiable too (`_RasterizeGaussiansPlanes`, `gsr_backward_planes`)
 `viewmatrix`, `projmatrix` or `campos` of the settings requires a gradient, the camera gets one as
 well (`_RasterizeGaussiansCamera`, `gsr_backward_camera`).  `GaussianRasterizationSettings(...,
 antialiasing=True)` (upstream's keyword) switches all three Functions to the compensated opacity
-(`gsr_forward_filtered` / `gsr_backward_filtered`).
+(`gsr_forward_filtered` / `gsr_backward_filtered`).  `GaussianRasterizationSettings(...,
+deterministic=True)`, or `torch.use_deterministic_algorithms(True)` with the setting left at None,
+makes every backward bit-reproducible (`gsr_backward_ordered`).
 """
 from __future__ import annotations
 
@@ -61,27 +63,39 @@ class GaussianRasterizationSettings(_SettingsTuple):
     depth_maps): the Mip-Splatting compensation of the 0.3-pixel dilation -- every Gaussian is
     drawn with opacity * sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))), forward and
     backward (gsr_forward_filtered / gsr_backward_filtered in include/gsr.h).  The splat composite
-    only: RuntimeError with a shading.  Upstream's positional place for it is `shading` here."""
+    only: RuntimeError with a shading.  Upstream's positional place for it is `shading` here.
+
+    deterministic (not upstream's; keyword only, default None, an attribute like antialiasing): the
+    backward whose gradients, the camera's included, have the same bits on every call with the
+    same inputs (gsr_backward_ordered in include/gsr.h: no float atomics; it costs workspace, 144
+    to 160 B per (Gaussian, tile) pair).  True and False force the mode; None follows
+    torch.are_deterministic_algorithms_enabled() when the backward runs.  The forward is
+    reproducible either way."""
     depth_maps = False  # (instances made by _make)
     antialiasing = False
+    deterministic = None
 
     def __new__(cls, *args, depth_maps=False, **kwargs):
-        # (antialiasing travels in kwargs: the parameter list ends at depth_maps, as
-        # tests/test_plane_grad_reference.py pins it)
+        # (antialiasing and deterministic travel in kwargs: the parameter list ends at depth_maps,
+        # as tests/test_plane_grad_reference.py pins it)
         antialiasing = kwargs.pop("antialiasing", False)
+        deterministic = kwargs.pop("deterministic", None)
         if len(args) == len(cls._fields) + 1:  # given by position, after shading
             *args, depth_maps = args
         self = super().__new__(cls, *args, **kwargs)
         self.depth_maps = bool(depth_maps)
         self.antialiasing = bool(antialiasing)
+        self.deterministic = None if deterministic is None else bool(deterministic)
         return self
 
     def _replace(self, **kwargs):
         depth_maps = kwargs.pop("depth_maps", self.depth_maps)
         antialiasing = kwargs.pop("antialiasing", self.antialiasing)
+        deterministic = kwargs.pop("deterministic", self.deterministic)
         new = super()._replace(**kwargs)
         new.depth_maps = bool(depth_maps)
         new.antialiasing = bool(antialiasing)
+        new.deterministic = None if deterministic is None else bool(deterministic)
         return new
 
 
@@ -281,7 +295,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         debug=False, *, conic=False, stream=None, slot=0,
                                         dL_ddepth_map=None, dL_dinv_depth_map=None,
                                         dL_dfinal_T=None, depths=False, camera=False,
-                                        antialiasing=False) -> dict:
+                                        antialiasing=False, deterministic=False) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -300,7 +314,10 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     (column-major) layout, and dL_dcampos (3,).
 
     antialiasing=True: the backward of the forward with the same argument, with whatever of the
-    planes and the camera is asked for."""
+    planes and the camera is asked for.
+
+    deterministic=True: the call is `gsr_backward_ordered` in its deterministic mode -- the same
+    gradients up to the rounding of the sums over pixels, with the same bits on every call."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
@@ -349,19 +366,26 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
     with torch.cuda.device(dev_index):
-        if not (plane_grads or depths or camera or antialiasing):
+        if not (plane_grads or depths or camera or antialiasing or deterministic):
             _lib.check(_lib.backward_fn(lib)(*head, ctypes.byref(out), ctypes.c_void_p(stream)),
                        "gsr_backward")
         else:  # NULL for each struct the call does without
             planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
                                             dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
             cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
-            _lib.check(_lib.filtered_fns(lib)[1](
-                *head, ctypes.byref(planes) if plane_grads or depths else None,
-                ctypes.byref(cg) if camera else None,
-                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
-                if antialiasing else None,
-                ctypes.byref(out), ctypes.c_void_p(stream)), "gsr_backward_filtered")
+            structs = (ctypes.byref(planes) if plane_grads or depths else None,
+                       ctypes.byref(cg) if camera else None,
+                       ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
+                       if antialiasing else None)
+            if deterministic:
+                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
+                _lib.check(_lib.backward_ordered_fn(lib)(
+                    *head, *structs, ctypes.byref(order), ctypes.byref(out),
+                    ctypes.c_void_p(stream)), "gsr_backward_ordered")
+            else:
+                _lib.check(_lib.filtered_fns(lib)[1](
+                    *head, *structs, ctypes.byref(out), ctypes.c_void_p(stream)),
+                    "gsr_backward_filtered")
             grads.update(cam)
     return grads
 
@@ -453,24 +477,34 @@ _GRADIENT_ORDER = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "d
                    "dL_dsh", "dL_dscales", "dL_drotations") + _lib.CAMERA_GRADIENT_NAMES
 
 
+def _deterministic(rs) -> bool:
+    """The backward's mode: the setting, or with None torch's global switch, read when the
+    backward runs."""
+    det = getattr(rs, "deterministic", None)
+    return torch.are_deterministic_algorithms_enabled() if det is None else bool(det)
+
+
 def _backward(rs, saved, grads, camera=None):
     """The gradients of one frame.  saved: `_saved`'s seven; grads: those of (color, depth_map,
     inv_depth_map, final_T), None = unused; camera: None, or the (viewmatrix, projmatrix, campos)
     to differentiate by, which the frame was rendered with.  Returns `_GRADIENT_ORDER`'s eleven,
     the camera's three None without `camera`.  Through `_C`: upstream's entry when only the
-    image's gradient is asked for, else the general one; under GSR_LIB by ctypes."""
+    image's gradient is asked for, else the general one; under GSR_LIB by ctypes.  In the
+    deterministic mode (`_deterministic`) the general entry with a 23rd argument, True."""
     means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
+    det = _deterministic(rs)
     viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not _lib._native_shares_library():
         g = rasterize_gaussians_backward_native(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
             cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree,
             campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
-            dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing)
+            dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
+            deterministic=det)
         return tuple(g.get(n) for n in _GRADIENT_ORDER)
     from . import _C
     e = torch.empty(0)
-    if camera is None and not rs.antialiasing and all(t is None for t in grads[1:]):
+    if camera is None and not rs.antialiasing and not det and all(t is None for t in grads[1:]):
         # (radii, num_rendered and the three buffers: accepted and ignored)
         return _C.rasterize_gaussians_backward(
             rs.bg, means3D, e, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds,
@@ -482,7 +516,8 @@ def _backward(rs, saved, grads, camera=None):
     g = _C.rasterize_gaussians_backward_ext(
         rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
         viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
-        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing))
+        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing),
+        *((True,) if det else ()))
     return g if camera is not None else g[:8] + (None,) * 3
 
 

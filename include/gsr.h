@@ -264,7 +264,8 @@ int gsr_forward_surface(gsr_context *ctx, const gsr_gaussians *g, const gsr_rast
  * Afterwards gsr_get_binning exports the backward's lists (upstream's, K = num_rendered), as after
  * a forward.  Every member of gsr_gradients is optional (NULL = not wanted); the call zeroes, then
  * fills, each one given (it does not accumulate).  The sums over pixels are float atomics: the
- * last bits of a gradient may differ from run to run. */
+ * last bits of a gradient may differ from run to run (gsr_backward_ordered, below, has a mode in
+ * which they do not). */
 typedef struct {
     const float *dL_dcolor; /* [3,H,W] */
 } gsr_backward_inputs;
@@ -421,6 +422,42 @@ int gsr_backward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ra
                           const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                           const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                           gsr_gradients *grads, void *stream);
+/* gsr_backward_filtered with a choice of how the sums over pixels are formed.  (Additive to ABI 4;
+ * no existing struct changes layout.)
+ * deterministic == 1: every gradient of the call -- each member of gsr_gradients, dL_ddepths and
+ * the camera's three -- has the same bits on every call with the same inputs, whichever context,
+ * stream or option set (GSR_OPT_DEPTH_SORT, GSR_OPT_BLEND_CULL, GSR_OPT_SECOND_STREAM, ...) runs
+ * it and whatever ran before it.  No float atomics, no sort:
+ *   - in upstream's (untight) lists, which the backward rebuilds, a Gaussian is listed in exactly
+ *     the tiles of its rect, so every (Gaussian, tile, 8x8 quadrant) owns a slot: the blend's
+ *     backward stores that quadrant's 9 sums (10 with plane gradients) there with plain stores and
+ *     sets the slot's mark, one byte per slot (the four quadrant waves of a tile write different
+ *     bytes); only the marks are zeroed per call, an unmarked slot is never read;
+ *   - a gather then fills each Gaussian's 2D gradient row: it adds the marked slots of the rect in
+ *     a fixed order (lane j of 16 takes slots j, j + 16, ... in tile row-major, then quadrant
+ *     order; the 16 lanes by a fixed tree), from +0.0, in double, rounded once.  The order depends
+ *     on the Gaussian's rect and marks only;
+ *   - the per-Gaussian stage and the camera's 27 sums follow unchanged (they have no atomics).
+ * The values differ from gsr_backward_filtered's by the rounding of those sums only (a row with
+ * at most two addends has the same bits in both modes); culled Gaussians and Gaussians no pixel
+ * composites still get exact zeros.
+ * Workspace of the context, grown on demand and freed with it, with K = num_rendered: slots 144 B
+ * per list entry (160 B with plane gradients), marks 4 B per list entry, 8 B per Gaussian; at
+ * K = 9,594,635 that is 1.38 GB (1.54 GB), 38 MB.  A failed allocation: GSR_E_NOMEM, nothing
+ * written.  Slots are indexed with 32 bits: a frame with K >= 2^30 is refused with GSR_E_INVALID,
+ * nothing written.
+ * A NULL order, or deterministic == 0, is gsr_backward_filtered itself: the same kernels, the same
+ * arguments.  Any other value than 0 or 1: GSR_E_INVALID, nothing written.  Everything else is
+ * gsr_backward_filtered's: whole frames only (a strip: GSR_E_INVALID), planes, camera and filter
+ * as there, gsr_get_binning afterwards, and gsr_backward_times with the scan, the zeroing of the
+ * marks and the gather inside ms[1]. */
+typedef struct {
+    int32_t deterministic; /* 0 or 1 */
+} gsr_backward_order;
+int gsr_backward_ordered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                         const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                         const gsr_backward_order *order, gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

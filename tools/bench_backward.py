@@ -24,10 +24,16 @@ gsr_backward_filtered: k_preprocess_aa and the k_preprocess_bwd*_aa kernels); wi
 --planes and --camera.  The forward step also reports preprocess_ms, the per-Gaussian stage of
 the forward as gsr_stage_times gives it, with and without the option.
 
+--deterministic: the backward is gsr_backward_ordered in its deterministic mode
+(k_blend_bwd_det_q / k_blend_bwd_planes_det_q store to slots, k_grad_rows_gather fills the rows;
+the slab scan, the zeroing of the marks and the gather are inside blend_bwd_ms); with or without
+--planes, --camera and --antialiasing.  The atomic figures are then not reported: the mode has no
+float atomics.
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
-                                      [--camera] [--antialiasing]
+                                      [--camera] [--antialiasing] [--deterministic]
 """
 import argparse
 import ctypes
@@ -74,10 +80,13 @@ def worker(a):
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
                                                    scene.scale, scene.rot, 1.0, None, view, proj,
                                                    tx, ty, dL, scene.sh, scene.deg, campos,
-                                                   camera=bool(a.camera), **plane_grads, **aa)
+                                                   camera=bool(a.camera),
+                                                   deterministic=bool(a.deterministic),
+                                                   **plane_grads, **aa)
 
     out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
-           "camera": bool(a.camera), "antialiasing": bool(a.antialiasing)}
+           "camera": bool(a.camera), "antialiasing": bool(a.antialiasing),
+           "deterministic": bool(a.deterministic)}
     if a.step == "forward":
         for _ in range(a.warmup):
             forward()
@@ -134,6 +143,8 @@ def main():
                     help="gsr_backward_camera: also the gradients of the camera")
     ap.add_argument("--antialiasing", action="store_true",
                     help="gsr_forward_filtered / gsr_backward_filtered with antialiasing = 1")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="gsr_backward_ordered with deterministic = 1: bit-reproducible gradients")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -144,12 +155,16 @@ def main():
                             "--steps", str(a.steps), "--warmup", str(a.warmup), "--step", step] +
                            (["--planes"] if a.planes else []) +
                            (["--camera"] if a.camera else []) +
-                           (["--antialiasing"] if a.antialiasing else []),
+                           (["--antialiasing"] if a.antialiasing else []) +
+                           (["--deterministic"] if a.deterministic else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"bench_backward: the {step} step failed ({r.returncode}); nothing more is run")
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
+    if a.deterministic:  # plain stores to slots: no atomic traffic to report
+        print(json.dumps(out))
+        return
     atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0))
     out["atomic_MB_per_frame_upper"] = round(atomic_bytes / 1e6, 1)
     out["atomic_GBs_if_all_added"] = round(atomic_bytes / (out["blend_bwd_ms"] * 1e-3) / 1e9, 1)
