@@ -50,6 +50,11 @@ gradient.  The forward is `gsr_forward_filtered` with the per-pixel planes only 
 (without, the three tensors are empty) and the filter only if `antialiasing`; a shading, or
 neither, is `gsr_forward_shaded`.  The backward is `gsr_backward_filtered` with NULL for what is
 not asked for: an empty tensor is an unused gradient, and without `camera` its three are empty.
+A strip of tile rows (`GaussianRasterizationSettings(tile_rows=)`): the forward takes
+`tile_row_begin, tile_row_end` after `antialiasing` (they may be left out), and
+`_C.rasterize_gaussians_backward_strip_ext(<the backward's arguments>, deterministic,
+tile_row_begin, tile_row_end, image_height)` is `gsr_backward_strip` -- the image-like tensors are
+then strip-local, and image_height is the frame's.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -59,7 +64,8 @@ from __future__ import annotations
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
-                          rasterize_gaussians_ext, rasterize_gaussians_shaded)
+                          rasterize_gaussians_backward_strip_ext, rasterize_gaussians_ext,
+                          rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

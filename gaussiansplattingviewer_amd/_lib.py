@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
+    "gsr_backward_strip",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -148,6 +149,8 @@ _ADDITIVE = {
                               GsrFilterSettings, GsrGradients),
     "gsr_backward_ordered": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
                              GsrFilterSettings, GsrBackwardOrder, GsrGradients),
+    "gsr_backward_strip": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                           GsrFilterSettings, GsrBackwardOrder, GsrGradients),
 }
 
 _lock = threading.Lock()
@@ -274,6 +277,11 @@ def filtered_fns(lib: ctypes.CDLL):
 def backward_ordered_fn(lib: ctypes.CDLL):
     """gsr_backward_ordered of a loaded library; RuntimeError if that build does not have it."""
     return _optional_fn(lib, "gsr_backward_ordered", "a deterministic backward needs")
+
+
+def backward_strip_fn(lib: ctypes.CDLL):
+    """gsr_backward_strip of a loaded library; RuntimeError if that build does not have it."""
+    return _optional_fn(lib, "gsr_backward_strip", "a backward on a tile row strip needs")
 
 
 def check(rc: int, what: str) -> int:

@@ -1534,18 +1534,27 @@ int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
 // deterministic: gsr_backward_ordered's mode -- the blend's backward stores every
 // (Gaussian, tile, quadrant)'s sums to a slot of its own and a gather fills the 2D gradient rows in
 // a fixed order, both inside the second timed stage; nothing else of the call differs.
+// strips: gsr_backward_strip -- a tile row strip of the settings is honoured instead
+// of refused: the rebuild is the strip's, the blend's backward runs the strip's tiles with the
+// strip-local image gradients, and on a proper subset of the rows the Gaussians without a tile in
+// it are gated out of the per-Gaussian stage.  Without a strip in the settings nothing differs.
 static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                     const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
                     const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
                     const std::string &fn, bool antialiasing = false,
-                    bool deterministic = false) {
+                    bool deterministic = false, bool strips = false) {
     if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
-    if (st->tile_row_begin != 0 || st->tile_row_end != 0)
+    const bool strip = st->tile_row_begin != 0 || st->tile_row_end != 0;
+    if (strip && !strips)
         return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
     const int64_t P = g->P;
     if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, fn + ": bad P");
     if (st->image_width <= 0 || st->image_height <= 0)
         return fail(GSR_E_INVALID, fn + ": image size must be positive");
+    // (before anything is written: the P == 0 path below zeroes the camera's buffers)
+    if (strip && (st->tile_row_begin < 0 || st->tile_row_begin >= st->tile_row_end ||
+                  st->tile_row_end > (st->image_height + GSR_TILE_Y - 1) / GSR_TILE_Y))
+        return fail(GSR_E_INVALID, fn + ": bad tile row strip");
     const bool planes =
         pl && (pl->dL_ddepth_map || pl->dL_dinv_depth_map || pl->dL_dfinal_T);
     float *const dL_ddepths = pl ? pl->dL_ddepths : nullptr;
@@ -1621,6 +1630,13 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         return GSR_OK;
     };
     const gsr_context::LastFrame &l = ctx->last;
+    // the strip the rebuild binned (the whole frame's rows without one), as launch_blend offsets
+    // the forward's
+    GsrStripBwdArgs sa{};
+    sa.row_begin = l.rb;
+    sa.y0 = (int)(l.rb * GSR_TILE_Y);
+    sa.rows_out = std::min(st->image_height, (int)(l.re * GSR_TILE_Y)) - sa.y0;
+    const GsrStripBwdArgs *const sp = strip ? &sa : nullptr;
     GsrDetBwdArgs da{};
     if (deterministic) {
         // the slots: one per (list entry, quadrant); the lists are upstream's, K = num_rendered
@@ -1654,7 +1670,7 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     ba.W = st->image_width;
     ba.H = st->image_height;
     ba.grid_x = l.gx;
-    ba.n_tiles = l.gx * l.gy;
+    ba.n_tiles = l.gx * (l.re - l.rb);  // (the whole frame: l.gy rows)
     ba.bg = st->bg;
     ba.dL_dcolor = in->dL_dcolor;
     ba.id_mask = l.id_mask;
@@ -1668,18 +1684,23 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
             pa = {ctx->sort_keys.get(), pl->dL_ddepth_map, pl->dL_dinv_depth_map,
                   pl->dL_dfinal_T};
         if (deterministic)
-            GSR_HIP(gsr_launch_blend_bwd_det(ba, planes ? &pa : nullptr, da, s),
+            GSR_HIP(gsr_launch_blend_bwd_det(ba, planes ? &pa : nullptr, da, s, sp),
                     "blend backward launch");
         else if (planes)
-            GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s), "blend backward launch");
+            GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s, sp), "blend backward launch");
         else
-            GSR_HIP(gsr_launch_blend_bwd(ba, s), "blend backward launch");
+            GSR_HIP(gsr_launch_blend_bwd(ba, s, sp), "blend backward launch");
     }
     if (deterministic)  // every word of every row, zeros where nothing was stored
         GSR_HIP(gsr_launch_grad_rows_gather(da, P, planes, ctx->grad2d.get(), s),
                 "gradient rows gather launch");
     GSR_TRY(mark(2));
     GSR_TRY(stage_check("stage blend backward"));
+    // a proper subset of the rows: the Gaussians without a tile in it read as culled from here on
+    // (the strip (0, grid_y) gates nothing: the whole frame's per-Gaussian stage, bit for bit)
+    if (strip && l.re - l.rb < l.gy)
+        GSR_HIP(gsr_launch_strip_gate(ctx->strip_rect.get(), P, ctx->bwd_radii.get(), s),
+                "strip gate launch");
 
     GsrPreprocessBwdArgs pb{};
     pb.P = P;
@@ -1776,6 +1797,26 @@ int gsr_backward_ordered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
                                        std::to_string(filter->antialiasing));
     return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_ordered", aa != 0,
                     true);
+}
+
+int gsr_backward_strip(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                       const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                       const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                       const gsr_backward_order *order, gsr_gradients *gr, void *stream) {
+    if (!ctx || !g || !st || !in || !gr)
+        return fail(GSR_E_INVALID, "gsr_backward_strip: NULL argument");
+    if (st->tile_row_begin == 0 && st->tile_row_end == 0)
+        return gsr_backward_ordered(ctx, g, st, in, planes, camera, filter, order, gr, stream);
+    const int det = order ? order->deterministic : 0;
+    if (det != 0 && det != 1)
+        return fail(GSR_E_INVALID, "gsr_backward_strip: deterministic must be 0 or 1, got " +
+                                       std::to_string(det));
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_backward_strip: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_strip", aa != 0,
+                    det != 0, true);
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

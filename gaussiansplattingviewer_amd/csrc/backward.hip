@@ -40,8 +40,15 @@
 //    the rects' sizes, and marks it; the gather adds a Gaussian's marked slots in a fixed order, in
 //    double, into its row.  No atomics, no zeroing but the marks'.  The kernels above compile as
 //    before (profiles/backward_deterministic_resources.txt).
+//  * k_blend_bwd_strip_q, ..._planes_strip_q, ..._det_strip_q, ..._planes_det_strip_q, k_strip_gate
+//    -- the backward on a strip of tile rows (gsr_backward_strip): the blend's body
+//    with kStrip set takes its tile rows from the strip's first and reads the strip-local image
+//    gradients; the gate zeroes the rebuilt radius of every Gaussian without a tile in the strip,
+//    so the eight per-Gaussian kernels leave it as they leave a culled one.  The kernels above
+//    compile as before (profiles/backward_strips_resources.txt).
 #include "gsr_internal.h"
 
+#include <algorithm>
 #include <type_traits>
 
 using namespace gsr;
@@ -86,9 +93,13 @@ struct BwdSplatT<true> {
 // kDet (gsr_backward_ordered): the flush stores the sums to the (Gaussian, tile,
 // quadrant)'s own slot of d and marks it, instead of adding them to a.grad2d; without it d is not
 // read.
-template <bool kPlanes, bool kDet = false>
+// kStrip (gsr_backward_strip): the grid is the strip's tiles; r gives the strip's
+// first tile row (the pixels' coordinates stay the frame's) and the offset and height of the
+// strip-local image and plane gradients; without it r is not read.
+template <bool kPlanes, bool kDet = false, bool kStrip = false>
 __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
-                                          const GsrDetBwdArgs &d = GsrDetBwdArgs{}) {
+                                          const GsrDetBwdArgs &d = GsrDetBwdArgs{},
+                                          const GsrStripBwdArgs &r = GsrStripBwdArgs{}) {
     using BwdSplat = BwdSplatT<kPlanes>;
     // per (splat, quadrant): the words 0..8 of a gradient row, and word 9 (dL/dz) with the planes
     constexpr int kSums = kPlanes ? 10 : 9;
@@ -107,9 +118,11 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
     uint32_t *const s_id = s_id_q[quad];
     float *const s_red = s_red_q[quad];
     [[maybe_unused]] uint32_t *const s_slot = s_slot_q[kDet ? quad : 0];
+    // ty: the tile row within the launch's grid (the strip's, which the slots are addressed by)
     const uint32_t tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
-    const int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
+    int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
+    if constexpr (kStrip) qy0 = (int)(r.row_begin + ty) * GSR_TILE_Y + (int)(quad >> 1) * 8;
     const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
     const bool inside = px < a.W && py < a.H;
     const float pfx = (float)px, pfy = (float)py;
@@ -187,7 +200,11 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
     // With R_i the colour behind splat i at unit transmittance (R_n = bg, R_{i-1} = c_i alpha_i +
     // (1 - alpha_i) R_i) the pixel is R_0 and dC/dalpha_i = T_i (c_i - R_i); only r = g . R is
     // carried (g = dL/dC of the pixel).  T_i is rebuilt as T_{i+1} / (1 - alpha_i), alpha <= 0.99.
-    const size_t plane = (size_t)a.H * a.W, pid = (size_t)(inside ? py : 0) * a.W + (inside ? px : 0);
+    size_t plane = (size_t)a.H * a.W, pid = (size_t)(inside ? py : 0) * a.W + (inside ? px : 0);
+    if constexpr (kStrip) {  // strip-local gradients (an inside pixel of a strip tile: py >= y0)
+        plane = (size_t)r.rows_out * a.W;
+        pid = (size_t)(inside ? py - r.y0 : 0) * a.W + (inside ? px : 0);
+    }
     // (kPlanes: a NULL dL_dcolor, a NULL plane and a pixel outside the image all read 0)
     const bool has_g = inside && (!kPlanes || a.dL_dcolor);
     const float g0 = has_g ? a.dL_dcolor[pid] : 0.0f;
@@ -305,6 +322,35 @@ __global__ __launch_bounds__(256) void k_blend_bwd_planes_det_q(const GsrBlendBw
                                                                 const GsrPlaneBwdArgs p,
                                                                 const GsrDetBwdArgs d) {
     blend_bwd<true, true>(a, p, d);
+}
+// The same four on a strip of tile rows (gsr_backward_strip): instantiations of their own, so the
+// four above keep their code and registers (profiles/backward_strips_resources.txt).
+__global__ __launch_bounds__(256) void k_blend_bwd_strip_q(const GsrBlendBwdArgs a,
+                                                           const GsrStripBwdArgs r) {
+    blend_bwd<false, false, true>(a, GsrPlaneBwdArgs{}, GsrDetBwdArgs{}, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_strip_q(const GsrBlendBwdArgs a,
+                                                                  const GsrPlaneBwdArgs p,
+                                                                  const GsrStripBwdArgs r) {
+    blend_bwd<true, false, true>(a, p, GsrDetBwdArgs{}, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_det_strip_q(const GsrBlendBwdArgs a,
+                                                               const GsrDetBwdArgs d,
+                                                               const GsrStripBwdArgs r) {
+    blend_bwd<false, true, true>(a, GsrPlaneBwdArgs{}, d, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_det_strip_q(const GsrBlendBwdArgs a,
+                                                                      const GsrPlaneBwdArgs p,
+                                                                      const GsrDetBwdArgs d,
+                                                                      const GsrStripBwdArgs r) {
+    blend_bwd<true, true, true>(a, p, d, r);
+}
+
+// gsr_launch_strip_gate: a Gaussian without a tile in the strip reads as culled from here on.
+__global__ __launch_bounds__(256) void k_strip_gate(const uint2 *__restrict__ strip_rect,
+                                                    int64_t P, int32_t *radii) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < P && strip_rect[i].x == 0u) radii[i] = 0;
 }
 
 // ---- the deterministic mode's slab scan and gather ------------------------------
@@ -627,34 +673,69 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_planes_camera_aa(
 
 }  // namespace
 
-hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s) {
+// A strip's arguments must describe rows of the frame: the kernels index with them unchecked.
+static bool strip_ok(const GsrBlendBwdArgs &a, const GsrStripBwdArgs *r) {
+    if (!r) return true;
+    if (a.grid_x == 0 || a.n_tiles % a.grid_x != 0 || r->y0 != (int)r->row_begin * GSR_TILE_Y)
+        return false;
+    const int64_t end = ((int64_t)r->row_begin + a.n_tiles / a.grid_x) * GSR_TILE_Y;
+    return r->y0 < a.H && r->rows_out == (int)std::min<int64_t>(a.H, end) - r->y0;
+}
+
+hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s,
+                                const GsrStripBwdArgs *strip) {
     if (a.n_tiles == 0) return hipSuccess;
-    if (!a.dL_dcolor) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_blend_bwd_q, dim3(a.n_tiles), dim3(256), 0, s, a);
+    if (!a.dL_dcolor || !strip_ok(a, strip)) return hipErrorInvalidValue;
+    if (strip)
+        hipLaunchKernelGGL(k_blend_bwd_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, *strip);
+    else
+        hipLaunchKernelGGL(k_blend_bwd_q, dim3(a.n_tiles), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
-                                       hipStream_t s) {
+                                       hipStream_t s, const GsrStripBwdArgs *strip) {
     if (!p.z_bits || (!p.dL_ddepth_map && !p.dL_dinv_depth_map && !p.dL_dfinal_T))
         return hipErrorInvalidValue;
     if (a.n_tiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
+    if (!strip_ok(a, strip)) return hipErrorInvalidValue;
+    if (strip)
+        hipLaunchKernelGGL(k_blend_bwd_planes_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, p,
+                           *strip);
+    else
+        hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
     return hipGetLastError();
 }
 
 hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
-                                    const GsrDetBwdArgs &d, hipStream_t s) {
+                                    const GsrDetBwdArgs &d, hipStream_t s,
+                                    const GsrStripBwdArgs *strip) {
     if (p && (!p->z_bits || (!p->dL_ddepth_map && !p->dL_dinv_depth_map && !p->dL_dfinal_T)))
         return hipErrorInvalidValue;
     if (!p && !a.dL_dcolor) return hipErrorInvalidValue;
     if (!d.strip_rect || !d.slab || !d.sums || !d.marks || d.K >= (1u << 30))
         return hipErrorInvalidValue;
     if (a.n_tiles == 0) return hipSuccess;
-    if (p)
+    if (!strip_ok(a, strip)) return hipErrorInvalidValue;
+    if (p && strip)
+        hipLaunchKernelGGL(k_blend_bwd_planes_det_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, *p,
+                           d, *strip);
+    else if (strip)
+        hipLaunchKernelGGL(k_blend_bwd_det_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, d,
+                           *strip);
+    else if (p)
         hipLaunchKernelGGL(k_blend_bwd_planes_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, *p, d);
     else
         hipLaunchKernelGGL(k_blend_bwd_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, d);
+    return hipGetLastError();
+}
+
+hipError_t gsr_launch_strip_gate(const uint2 *strip_rect, int64_t P, int32_t *radii,
+                                 hipStream_t s) {
+    if (P <= 0) return hipSuccess;
+    if (!strip_rect || !radii) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_strip_gate, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s,
+                       strip_rect, P, radii);
     return hipGetLastError();
 }
 

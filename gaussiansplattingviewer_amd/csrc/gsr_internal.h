@@ -626,7 +626,20 @@ struct GsrBlendBwdArgs {
     int cull;
     float *grad2d;  // [P, kGradRow], zeroed by the caller
 };
-hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s);
+// gsr_backward_strip: the backward on the tile rows [row_begin, row_begin +
+// a.n_tiles / a.grid_x) of the frame.  a.ranges are then the strip's (strip-local tiles, the grid
+// of the launch), a.H stays the frame's; pixel coordinates stay the frame's (a tile's rows from
+// its global tile row) while a.dL_dcolor ([3, rows_out, W]) and the plane gradients ([rows_out, W])
+// are strip-local, read at (py - y0) * W + px, as blend.hip writes the forward's strip.  The
+// deterministic slot takes the strip-local tile row against the strip-local strip_rect.  Passed to
+// the three launchers below it selects the k_blend_bwd*_strip_q instantiations; NULL launches the
+// whole-frame kernels, which have no such argument (profiles/backward_strips_resources.txt).
+struct GsrStripBwdArgs {
+    uint32_t row_begin;
+    int y0, rows_out;
+};
+hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s,
+                                const GsrStripBwdArgs *strip = nullptr);
 // gsr_backward_planes (k_blend_bwd_planes_q): the gradients of depth_map, inv_depth_map and
 // final_T ([H, W] each, any NULL but not all) beside a.dL_dcolor, which may then be NULL.  z_bits:
 // per Gaussian, the bits of its view-space z (the rebuild's depth keys, as GsrDepthArgs).  The
@@ -636,7 +649,7 @@ struct GsrPlaneBwdArgs {
     const float *dL_ddepth_map, *dL_dinv_depth_map, *dL_dfinal_T;
 };
 hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
-                                       hipStream_t s);
+                                       hipStream_t s, const GsrStripBwdArgs *strip = nullptr);
 // gsr_backward_ordered, deterministic (k_blend_bwd_det_q, k_blend_bwd_planes_det_q; DESIGN.md
 // 3k): no sum is added to a.grad2d.  In upstream's (untight) lists a Gaussian is listed in exactly
 // the tiles of its rect, so every (Gaussian, tile, quadrant) owns a slot,
@@ -655,7 +668,8 @@ struct GsrDetBwdArgs {
     uint32_t K;
 };
 hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
-                                    const GsrDetBwdArgs &d, hipStream_t s);
+                                    const GsrDetBwdArgs &d, hipStream_t s,
+                                    const GsrStripBwdArgs *strip = nullptr);
 // slab[i] = sum over j < i of w_j * rows_j (strip_rect, 0 for a Gaussian without a rect), 64-bit;
 // partials: workspace of gsr_slab_blocks(P) uint64.  P == 0 launches nothing.
 int64_t gsr_slab_blocks(int64_t P);
@@ -669,6 +683,12 @@ hipError_t gsr_launch_slab_scan(const uint2 *strip_rect, int64_t P, uint64_t *pa
 // of the rect and the marks alone.
 hipError_t gsr_launch_grad_rows_gather(const GsrDetBwdArgs &d, int64_t P, bool planes,
                                        float *grad2d, hipStream_t s);
+// gsr_backward_strip's gate (k_strip_gate): radii[i] = 0 for every Gaussian without a tile in the
+// strip (strip_rect[i].x == 0), in place, so that each of the eight k_preprocess_bwd* kernels
+// leaves it where it leaves a culled Gaussian: before any arithmetic, +0.0 in every gradient, zeros
+// to the camera's sums.  The kernels themselves are the whole frame's.
+hipError_t gsr_launch_strip_gate(const uint2 *strip_rect, int64_t P, int32_t *radii,
+                                 hipStream_t s);
 struct GsrPreprocessBwdArgs {
     int64_t P;
     int D, M;
@@ -678,7 +698,9 @@ struct GsrPreprocessBwdArgs {
     float tanfovx, tanfovy, focal_x, focal_y;
     int W, H;
     int sh_vec4;  // set by the launcher: SH rows (and dL_dsh rows) of 16 coefficients, 16-B aligned
-    const int32_t *radii;  // of the rebuilt per-Gaussian stage: 0 = culled, every gradient 0
+    // of the rebuilt per-Gaussian stage: 0 = culled, every gradient 0 (on a strip also a Gaussian
+    // without a tile in it: gsr_launch_strip_gate)
+    const int32_t *radii;
     const float *grad2d;   // [P, kGradRow]
     // outputs, each optional (gsr_gradients)
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dopacity, *dL_dcolors, *dL_dconic, *dL_dsh, *dL_dscales,

@@ -22,13 +22,16 @@
 //     upstream RasterizeGaussiansBackwardCUDA's arguments and 8-tuple over gsr_backward, plus one
 //     trailing argument: upstream reads the opacities out of geomBuffer, here the state is
 //     rebuilt from the inputs.  radii, R and the three buffers are accepted and ignored.
-//   _C.rasterize_gaussians_ext(<rasterize_gaussians' 19 arguments>, shading, planes, antialiasing)
+//   _C.rasterize_gaussians_ext(<rasterize_gaussians' 19 arguments>, shading, planes, antialiasing,
+//                              tile_row_begin = 0, tile_row_end = 0)
 //       -> (num_rendered, color, radii, depth_map [H,W], inv_depth_map [H,W], final_T [H,W])
 //     this package's own, every forward in one entry (GaussianRasterizationSettings.shading,
 //     .depth_maps, .antialiasing).  A shading, or the plain splat frame: gsr_forward_shaded.
 //     Anything else: gsr_forward_filtered, with the depth planes and final_T only if `planes`
 //     (without, the three tensors are empty and nothing of them is rendered) and a filter only if
-//     `antialiasing` (the effective opacity of the 0.3-pixel dilation's compensation).
+//     `antialiasing` (the effective opacity of the 0.3-pixel dilation's compensation).  With a
+//     strip of tile rows (the two trailing arguments, not both 0; they may be left out) the image
+//     and the planes are strip-local, [3, rows, W] and [rows, W], rows = min(H, 16 end) - 16 begin.
 //   _C.rasterize_gaussians_backward_ext(bg, means3D, colors_precomp, opacities, scales, rotations,
 //                                       scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
 //                                       tanfovx, tanfovy, sh, sh_degree, campos, debug,
@@ -43,6 +46,13 @@
 //     `deterministic` gsr_backward_ordered, whose gradients have the same bits on every call
 //     (the trailing argument may be left out: the 22-argument call is unchanged).  The two matrices'
 //     gradients are in the inputs' layout (the 16 floats of the input, viewed (4, 4)).
+//   _C.rasterize_gaussians_backward_strip_ext(<rasterize_gaussians_backward_ext's 23 arguments>,
+//                                             tile_row_begin, tile_row_end, image_height)
+//       -> the same 11-tuple
+//     this package's own: gsr_backward_strip, the backward on a strip of tile rows (not both 0) in
+//     either mode.  The image and plane gradients are strip-local, [3, rows, W] and [rows, W], and
+//     image_height gives the frame's height, which they no longer tell; the gradients stay
+//     whole-scene.  (An entry of its own: rasterize_gaussians_backward_ext keeps its signature.)
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -50,6 +60,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -155,9 +166,19 @@ struct Scene {
 
 // Every forward: (num_rendered, color, radii, depth_map, inv_depth_map, final_T), the three
 // planes empty without `planes`.
-Forward6 forward_impl(const Inputs &in, int64_t H, int64_t W, int64_t shading, bool planes,
-                      bool antialiasing) {
+// rows of the strip [rb, re) of a frame H pixels high (0, 0: the frame); checks the strip
+int64_t strip_rows(int64_t H, int64_t rb, int64_t re) {
+    if (rb == 0 && re == 0) return H;
+    TORCH_CHECK(H > 0 && 0 <= rb && rb < re && re <= (H + 15) / 16, "tile rows (", rb, ", ", re,
+                ") outside [0, ", (H + 15) / 16, "]");
+    return std::min(H, 16 * re) - 16 * rb;
+}
+
+Forward6 forward_impl(const Inputs &in, int64_t frame_H, int64_t W, int64_t shading, bool planes,
+                      bool antialiasing, int64_t tile_row_begin = 0, int64_t tile_row_end = 0) {
     Scene sc(in);
+    // (the outputs are strip-local: H rows from here on)
+    const int64_t H = strip_rows(frame_H, tile_row_begin, tile_row_end);
     TORCH_CHECK(shading == GSR_SHADE_SPLAT || (!planes && !antialiasing),
                 "the planes and antialiasing belong to the splat composite: not available with "
                 "shading ", shading);
@@ -177,7 +198,9 @@ Forward6 forward_impl(const Inputs &in, int64_t H, int64_t W, int64_t shading, b
     }
     int64_t num_rendered = 0;
     if (P != 0) {
-        sc.fill(H, W);
+        sc.fill(frame_H, W);
+        sc.st.tile_row_begin = (int32_t)tile_row_begin;
+        sc.st.tile_row_end = (int32_t)tile_row_end;
         gsr_outputs out{};
         out.color = color.data_ptr<float>();
         out.radii = radii.data_ptr<int32_t>();
@@ -210,11 +233,13 @@ Forward6 rasterize_gaussians_ext(
     double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
     const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
     int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
-    bool prefiltered, bool debug, int64_t shading, bool planes, bool antialiasing) {
+    bool prefiltered, bool debug, int64_t shading, bool planes, bool antialiasing,
+    int64_t tile_row_begin, int64_t tile_row_end) {
     return forward_impl({background, means3D, colors, opacity, scales, rotations, scale_modifier,
                          cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree,
                          campos, prefiltered, debug},
-                        image_height, image_width, shading, planes, antialiasing);
+                        image_height, image_width, shading, planes, antialiasing, tile_row_begin,
+                        tile_row_end);
 }
 
 // ... with upstream's three buffers in the planes' place.  They hold upstream's backward state;
@@ -256,8 +281,11 @@ Forward6 rasterize_gaussians(const torch::Tensor &background, const torch::Tenso
 // which takes no plane gradient and is gsr_backward itself.
 Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
                          const torch::Tensor (&planes)[3], bool camera, bool antialiasing,
-                         bool upstream = false, bool deterministic = false) {
+                         bool upstream = false, bool deterministic = false,
+                         int64_t tile_row_begin = 0, int64_t tile_row_end = 0,
+                         int64_t image_height = 0) {
     Scene sc(in);
+    const bool strip = tile_row_begin != 0 || tile_row_end != 0;
     const bool has_color = dL_dout_color.defined() && dL_dout_color.numel() != 0;
     int64_t H = 0, W = 0;
     if (has_color || upstream) {
@@ -275,6 +303,12 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         any = true;
     }
     TORCH_CHECK(any || has_color || upstream, "dL_dout_color or a plane gradient is required");
+    // a strip: H so far is the strip's rows, which must be those of the frame's strip
+    const int64_t frame_H = strip ? image_height : H;
+    TORCH_CHECK(strip_rows(frame_H, tile_row_begin, tile_row_end) == H,
+                "the image and plane gradients of tile rows (", tile_row_begin, ", ", tile_row_end,
+                ") of a frame ", frame_H, " px high must have ",
+                strip_rows(frame_H, tile_row_begin, tile_row_end), " rows, got ", H);
     const int64_t P = sc.P, M = sc.M;
     auto f32 = in.means3D.options().dtype(torch::kFloat32);
     torch::Tensor d_means3D = torch::zeros({P, 3}, f32), d_means2D = torch::zeros({P, 3}, f32);
@@ -287,7 +321,9 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         d_campos = torch::zeros({3}, f32);
     }
     if (P != 0) {
-        sc.fill(H, W);
+        sc.fill(frame_H, W);
+        sc.st.tile_row_begin = (int32_t)tile_row_begin;
+        sc.st.tile_row_end = (int32_t)tile_row_end;
         std::vector<torch::Tensor> &keep = sc.keep;
         gsr_backward_inputs bi{};
         bi.dL_dcolor = opt_ptr(dL_dout_color, sc.dev, "dL_dout_color", keep, 3 * H * W);
@@ -299,7 +335,7 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         if (camera)
             cg = {d_view.data_ptr<float>(), d_proj.data_ptr<float>(), d_campos.data_ptr<float>()};
         const gsr_filter_settings fs{1};
-        const gsr_backward_order order{1};
+        const gsr_backward_order order{deterministic ? 1 : 0};
         gsr_gradients gr{};
         gr.dL_dmeans3D = d_means3D.data_ptr<float>();
         gr.dL_dmeans2D = d_means2D.data_ptr<float>();
@@ -319,6 +355,10 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
             pybind11::gil_scoped_release no_gil;
             if (upstream)
                 rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
+            else if (strip)  // gsr_backward_strip: the strip's loss, in either mode
+                rc = gsr_backward_strip(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
+                                        camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
+                                        &order, &gr, s);
             else if (deterministic)  // gsr_backward_ordered: bit-reproducible sums
                 rc = gsr_backward_ordered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
                                           camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
@@ -372,6 +412,26 @@ Backward11 rasterize_gaussians_backward_ext(
                          dL_dout_color, planes, camera, antialiasing, false, deterministic);
 }
 
+// ... on a strip of tile rows of a frame image_height pixels high.
+Backward11 rasterize_gaussians_backward_strip_ext(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T, bool camera, bool antialiasing, bool deterministic,
+    int64_t tile_row_begin, int64_t tile_row_end, int64_t image_height) {
+    TORCH_CHECK(tile_row_begin != 0 || tile_row_end != 0,
+                "rasterize_gaussians_backward_strip_ext needs a strip: tile rows (0, 0) given");
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    return backward_impl({background, means3D, colors, opacities, scales, rotations,
+                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                          sh, degree, campos, false, debug},
+                         dL_dout_color, planes, camera, antialiasing, false, deterministic,
+                         tile_row_begin, tile_row_end, image_height);
+}
+
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
                            const torch::Tensor &projmatrix) {
     TORCH_CHECK(means3D.is_cuda(), "means3D must be a device (HIP) tensor");
@@ -416,9 +476,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, "
           "dL_drotations)");
     m.def("rasterize_gaussians_ext", &rasterize_gaussians_ext,
-          "rasterize_gaussians' 19 arguments, then shading (GSR_SHADE_*), planes, antialiasing -> "
+          "rasterize_gaussians' 19 arguments, then shading (GSR_SHADE_*), planes, antialiasing, "
+          "tile_row_begin = 0, tile_row_end = 0 (a strip: strip-local image and planes) -> "
           "(num_rendered, color, radii, depth_map, inv_depth_map, final_T), the three planes "
-          "empty without `planes`");
+          "empty without `planes`",
+          pybind11::arg("bg"), pybind11::arg("means3D"), pybind11::arg("colors_precomp"),
+          pybind11::arg("opacities"), pybind11::arg("scales"), pybind11::arg("rotations"),
+          pybind11::arg("scale_modifier"), pybind11::arg("cov3D_precomp"),
+          pybind11::arg("viewmatrix"), pybind11::arg("projmatrix"), pybind11::arg("tanfovx"),
+          pybind11::arg("tanfovy"), pybind11::arg("image_height"), pybind11::arg("image_width"),
+          pybind11::arg("sh"), pybind11::arg("sh_degree"), pybind11::arg("campos"),
+          pybind11::arg("prefiltered"), pybind11::arg("debug"), pybind11::arg("shading"),
+          pybind11::arg("planes"), pybind11::arg("antialiasing"),
+          pybind11::arg("tile_row_begin") = 0, pybind11::arg("tile_row_end") = 0);
     m.def("rasterize_gaussians_backward_ext", &rasterize_gaussians_backward_ext,
           "bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, "
           "cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, sh, sh_degree, campos, debug, "
@@ -435,6 +505,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("dL_ddepth_map"), pybind11::arg("dL_dinv_depth_map"),
           pybind11::arg("dL_dfinal_T"), pybind11::arg("camera"), pybind11::arg("antialiasing"),
           pybind11::arg("deterministic") = false);
+    m.def("rasterize_gaussians_backward_strip_ext", &rasterize_gaussians_backward_strip_ext,
+          "rasterize_gaussians_backward_ext's 23 arguments, then tile_row_begin, tile_row_end, "
+          "image_height: gsr_backward_strip, the backward on a strip of tile rows of a frame "
+          "image_height px high (strip-local image and plane gradients) -> the same 11-tuple");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -21,6 +21,10 @@ antialiasing=True)` (upstream's keyword) switches all three Functions to the com
 (`gsr_forward_filtered` / `gsr_backward_filtered`).  `GaussianRasterizationSettings(...,
 deterministic=True)`, or `torch.use_deterministic_algorithms(True)` with the setting left at None,
 makes every backward bit-reproducible (`gsr_backward_ordered`).
+`GaussianRasterizationSettings(..., tile_rows=(b, e))` renders and differentiates one strip of
+16-px tile rows (`gsr_backward_strip`): the image-like outputs are strip-local, the gradients
+whole-scene, and over a partition of the rows they add up to the whole frame's
+(`strips.reduce_gradients` sums them over the ranks).
 """
 from __future__ import annotations
 
@@ -50,6 +54,23 @@ class _SettingsTuple(NamedTuple):
     shading: int = 0
 
 
+def _tile_rows(tile_rows):
+    """None, or (begin, end) as a tuple of two ints."""
+    if tile_rows is None:
+        return None
+    b, e = tile_rows
+    return int(b), int(e)
+
+
+def _strip_rows(tile_rows, H):
+    """(begin, end, y0, rows) of a strip of a frame H pixels high; RuntimeError outside the grid."""
+    gy = (H + 15) // 16
+    rb, re = int(tile_rows[0]), int(tile_rows[1])
+    if not (0 <= rb < re <= gy):
+        raise RuntimeError(f"tile_rows {tuple(tile_rows)} outside [0, {gy}]")
+    return rb, re, rb * 16, min(H, re * 16) - rb * 16
+
+
 class GaussianRasterizationSettings(_SettingsTuple):
     """upstream's settings tuple (its 12 fields, then `shading`) and one more setting beside it:
     depth_maps (not upstream's; the last argument, after shading, default False).  With it
@@ -70,32 +91,46 @@ class GaussianRasterizationSettings(_SettingsTuple):
     same inputs (gsr_backward_ordered in include/gsr.h: no float atomics; it costs workspace, 144
     to 160 B per (Gaussian, tile) pair).  True and False force the mode; None follows
     torch.are_deterministic_algorithms_enabled() when the backward runs.  The forward is
-    reproducible either way."""
+    reproducible either way.
+
+    tile_rows (not upstream's; keyword only, default None, an attribute like antialiasing): (b, e),
+    the 16-px tile rows [b, e) of the frame to render and to differentiate (gsr_backward_strip in
+    include/gsr.h).  image_height and image_width stay the frame's.  GaussianRasterizer then returns
+    the strip-local colour (3, rows, W), rows = min(H, 16 e) - 16 b, and with depth_maps the
+    strip-local planes (rows, W); radii stays (P,).  backward() gives the whole-scene gradients of
+    the strip's loss -- the whole frame's backward with the image gradients zero outside the strip
+    -- through all three Functions (planes, camera, antialiasing, deterministic).  The splat
+    composite only, like every backward."""
     depth_maps = False  # (instances made by _make)
     antialiasing = False
     deterministic = None
+    tile_rows = None
 
     def __new__(cls, *args, depth_maps=False, **kwargs):
         # (antialiasing and deterministic travel in kwargs: the parameter list ends at depth_maps,
         # as tests/test_plane_grad_reference.py pins it)
         antialiasing = kwargs.pop("antialiasing", False)
         deterministic = kwargs.pop("deterministic", None)
+        tile_rows = kwargs.pop("tile_rows", None)
         if len(args) == len(cls._fields) + 1:  # given by position, after shading
             *args, depth_maps = args
         self = super().__new__(cls, *args, **kwargs)
         self.depth_maps = bool(depth_maps)
         self.antialiasing = bool(antialiasing)
         self.deterministic = None if deterministic is None else bool(deterministic)
+        self.tile_rows = _tile_rows(tile_rows)
         return self
 
     def _replace(self, **kwargs):
         depth_maps = kwargs.pop("depth_maps", self.depth_maps)
         antialiasing = kwargs.pop("antialiasing", self.antialiasing)
         deterministic = kwargs.pop("deterministic", self.deterministic)
+        tile_rows = kwargs.pop("tile_rows", self.tile_rows)
         new = super()._replace(**kwargs)
         new.depth_maps = bool(depth_maps)
         new.antialiasing = bool(antialiasing)
         new.deterministic = None if deterministic is None else bool(deterministic)
+        new.tile_rows = _tile_rows(tile_rows)
         return new
 
 
@@ -218,16 +253,11 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,
         viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, debug)
 
-    gy = (H + 15) // 16
     if tile_rows is None:
         rb, re = 0, 0
         y0, rows = 0, H
     else:
-        rb, re = int(tile_rows[0]), int(tile_rows[1])
-        y0 = rb * 16
-        rows = min(H, re * 16) - y0
-        if not (0 <= rb < re <= gy):
-            raise RuntimeError(f"tile_rows {tile_rows} outside [0, {gy}]")
+        rb, re, y0, rows = _strip_rows(tile_rows, H)
 
     f32 = dict(dtype=torch.float32, device=device)
     if out_color is None:
@@ -295,7 +325,8 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         debug=False, *, conic=False, stream=None, slot=0,
                                         dL_ddepth_map=None, dL_dinv_depth_map=None,
                                         dL_dfinal_T=None, depths=False, camera=False,
-                                        antialiasing=False, deterministic=False) -> dict:
+                                        antialiasing=False, deterministic=False,
+                                        tile_rows=None, image_height=None) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -317,9 +348,19 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     planes and the camera is asked for.
 
     deterministic=True: the call is `gsr_backward_ordered` in its deterministic mode -- the same
-    gradients up to the rounding of the sums over pixels, with the same bits on every call."""
+    gradients up to the rounding of the sums over pixels, with the same bits on every call.
+
+    tile_rows=(b, e), with image_height (required then: the strip does not tell the frame's
+    height): the call is `gsr_backward_strip` -- the backward of the strip's loss.  dL_dout_color is
+    strip-local, (3, rows, W) with rows = min(H, 16 e) - 16 b, the plane gradients (rows, W); the
+    gradients are whole-scene, exact zeros for Gaussians without a tile in the strip."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if tile_rows is not None and image_height is None:
+        raise RuntimeError("tile_rows needs image_height: the frame's height, not the strip's")
+    if tile_rows is None and image_height is not None:
+        raise RuntimeError("image_height belongs to tile_rows: a whole frame's comes from "
+                           "dL_dout_color")
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
                    "dL_dfinal_T": dL_dfinal_T}
     plane_grads = {n: t for n, t in plane_grads.items() if t is not None}
@@ -333,12 +374,22 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     else:
         first = next(iter(plane_grads.values()))
         H, W = int(first.size(-2)), int(first.size(-1))
+    rb = re = 0
+    if tile_rows is not None:  # H so far: the strip's rows
+        rb, re, _, rows = _strip_rows(tile_rows, int(image_height))
+        if H != rows:
+            raise RuntimeError(f"tile_rows {tuple(tile_rows)} of a frame {int(image_height)} px "
+                               f"high: the image and plane gradients must have {rows} rows, got {H}")
+        H = int(image_height)
+    else:
+        rows = H
     for n, t in plane_grads.items():
-        if t.ndimension() != 2 or tuple(t.shape) != (H, W):
-            raise RuntimeError(f"{n} must have dimensions (H, W) = ({H}, {W})")
+        if t.ndimension() != 2 or tuple(t.shape) != (rows, W):
+            raise RuntimeError(f"{n} must have dimensions (H, W) = ({rows}, {W})")
     device, dev_index, P, g, st, held = _scene_structs(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,
         viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, False, debug)
+    st.tile_row_begin, st.tile_row_end = rb, re
     dL = _as_dev(dL_dout_color, device, "3,H,W")
     f32 = dict(dtype=torch.float32, device=device)
     grads = {"dL_dmeans3D": torch.zeros((P, 3), **f32), "dL_dmeans2D": torch.zeros((P, 3), **f32),
@@ -366,7 +417,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
     with torch.cuda.device(dev_index):
-        if not (plane_grads or depths or camera or antialiasing or deterministic):
+        if not (plane_grads or depths or camera or antialiasing or deterministic or re):
             _lib.check(_lib.backward_fn(lib)(*head, ctypes.byref(out), ctypes.c_void_p(stream)),
                        "gsr_backward")
         else:  # NULL for each struct the call does without
@@ -377,7 +428,12 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                        ctypes.byref(cg) if camera else None,
                        ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
                        if antialiasing else None)
-            if deterministic:
+            if re:
+                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
+                _lib.check(_lib.backward_strip_fn(lib)(
+                    *head, *structs, ctypes.byref(order), ctypes.byref(out),
+                    ctypes.c_void_p(stream)), "gsr_backward_strip")
+            elif deterministic:
                 order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
                 _lib.check(_lib.backward_ordered_fn(lib)(
                     *head, *structs, ctypes.byref(order), ctypes.byref(out),
@@ -456,15 +512,19 @@ def _forward(args, rs, planes: bool):
     tensors, or () without `planes`.  Through `_C`: upstream's entry for the plain frame, its
     shaded twin, the general entry for the rest; under GSR_LIB (an A/B build: `_C` links the
     in-tree library) by ctypes."""
+    strip = getattr(rs, "tile_rows", None)
     if not _lib._native_shares_library():
         res = rasterize_gaussians_native(*args, extras=PLANE_NAMES if planes else (),
-                                         shading=rs.shading, antialiasing=rs.antialiasing)
+                                         shading=rs.shading, antialiasing=rs.antialiasing,
+                                         tile_rows=strip)
         return (res.num_rendered, res.color, res.radii,
                 tuple(res.extras[n] for n in PLANE_NAMES) if planes else ())
     from . import _C
-    if planes or rs.antialiasing:
+    if planes or rs.antialiasing or strip:
+        if strip:  # (checked here for the message; the entry checks it again)
+            _strip_rows(strip, int(rs.image_height))
         num_rendered, color, radii, *maps = _C.rasterize_gaussians_ext(
-            *args, int(rs.shading), planes, bool(rs.antialiasing))
+            *args, int(rs.shading), planes, bool(rs.antialiasing), *(strip or ()))
         return num_rendered, color, radii, tuple(maps) if planes else ()
     if rs.shading:  # upstream's 19 arguments and the shading
         num_rendered, color, radii, *_ = _C.rasterize_gaussians_shaded(*args, int(rs.shading))
@@ -490,9 +550,12 @@ def _backward(rs, saved, grads, camera=None):
     to differentiate by, which the frame was rendered with.  Returns `_GRADIENT_ORDER`'s eleven,
     the camera's three None without `camera`.  Through `_C`: upstream's entry when only the
     image's gradient is asked for, else the general one; under GSR_LIB by ctypes.  In the
-    deterministic mode (`_deterministic`) the general entry with a 23rd argument, True."""
+    deterministic mode (`_deterministic`) the general entry with a 23rd argument, True; on a
+    strip (rs.tile_rows) the strip's entry, whose three more are the strip's rows and the frame's
+    height."""
     means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
     det = _deterministic(rs)
+    strip = getattr(rs, "tile_rows", None)
     viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not _lib._native_shares_library():
         g = rasterize_gaussians_backward_native(
@@ -500,11 +563,13 @@ def _backward(rs, saved, grads, camera=None):
             cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree,
             campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
             dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
-            deterministic=det)
+            deterministic=det, tile_rows=strip,
+            image_height=None if strip is None else rs.image_height)
         return tuple(g.get(n) for n in _GRADIENT_ORDER)
     from . import _C
     e = torch.empty(0)
-    if camera is None and not rs.antialiasing and not det and all(t is None for t in grads[1:]):
+    if (camera is None and not rs.antialiasing and not det and strip is None and
+            all(t is None for t in grads[1:])):
         # (radii, num_rendered and the three buffers: accepted and ignored)
         return _C.rasterize_gaussians_backward(
             rs.bg, means3D, e, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds,
@@ -513,11 +578,13 @@ def _backward(rs, saved, grads, camera=None):
     if camera is not None:
         viewmatrix, projmatrix, campos = (_as_dev(t.detach(), means3D.device, "")
                                           for t in camera)
-    g = _C.rasterize_gaussians_backward_ext(
+    entry = _C.rasterize_gaussians_backward_strip_ext if strip else \
+        _C.rasterize_gaussians_backward_ext
+    g = entry(
         rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
         viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
         *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing),
-        *((True,) if det else ()))
+        *((det, *strip, int(rs.image_height)) if strip else (True,) if det else ()))
     return g if camera is not None else g[:8] + (None,) * 3
 
 

@@ -14,6 +14,9 @@ bit-identical to the same rows of a single-GPU frame, wherever the boundaries fa
   message per colour plane (a CHW strip is three contiguous row blocks of the frame), grouped
   into one `batch_isend_irecv` (RCCL send/recv over xGMI on MI355X; gloo on CPU in the tests).
   No padding, no `cat`: the only copy is rank 0's own strip into the frame.
+* Gradients: a rank differentiates its own strip (`GaussianRasterizationSettings(tile_rows=)`,
+  `gsr_backward_strip`); the strips' whole-scene gradients add up to the frame's, and
+  `reduce_gradients` sums them over the ranks.
 """
 from __future__ import annotations
 
@@ -233,6 +236,25 @@ def gather_strips(strip: torch.Tensor, H: int, W: int, world: int, rank: int, gr
                     depth=1)
     g.submit(strip, layout)
     return g.finish()
+
+
+def reduce_gradients(tensors, group=None) -> None:
+    """Sum the given tensors over the ranks, in place (one all_reduce each): the strips' gradients
+    of `GaussianRasterizationSettings(tile_rows=)` add up to the whole frame's, so after the call
+    every rank holds the whole frame's gradients.  `tensors`: an iterable of tensors, e.g. the
+    leaves' `.grad`; None entries are skipped.  A no-op at world 1.  With a backend that moves
+    device tensors from host threads (gloo; not RCCL) the current stream of every device tensor's
+    device is synchronised first, as StripGather does, so the backward that wrote them is done.
+    A two-term float sum is commutative: with two ranks every rank's result has the bits of the
+    sum a single process forms of the two strips' gradients."""
+    if dist.get_world_size(group) == 1:
+        return
+    tensors = [t for t in tensors if t is not None]
+    if dist.get_backend(group) != "nccl":
+        for dev in {t.device for t in tensors if t.is_cuda}:
+            torch.cuda.current_stream(dev).synchronize()
+    for t in tensors:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
 
 def render_strips(render_fn, H: int, W: int, world: int, rank: int, group=None,

@@ -458,6 +458,38 @@ int gsr_backward_ordered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                          const gsr_backward_order *order, gsr_gradients *grads, void *stream);
+/* gsr_backward_ordered on a strip of tile rows: the one backward entry that honours
+ * s->tile_row_begin / tile_row_end (every entry above keeps refusing a strip).  (Additive to ABI 4;
+ * no existing struct changes layout.)
+ * Every term a pixel adds to any gradient is proportional to that pixel's own image gradient, so
+ * the backward on the strip [begin, end) is the whole-frame backward with the image gradients zero
+ * outside the strip's pixel rows y0 = 16 begin .. min(H, 16 end), rows = min(H, 16 end) - y0:
+ *   - the inputs are strip-local, like the forward's outputs: in->dL_dcolor is [3, rows, W], the
+ *     three plane gradients [rows, W];
+ *   - the outputs are whole-scene: every gsr_gradients member [P, ...], dL_ddepths [P], the
+ *     camera's three buffers of their fixed sizes;
+ *   - on a strip that is a proper subset of the tile rows, a Gaussian without a tile in it (the
+ *     rebuild's strip rect is empty; culled Gaussians included) leaves the per-Gaussian stage before
+ *     any arithmetic: +0.0 in every gradient, and exactly 0 added to the camera's sums.  A Gaussian
+ *     with a tile that no pixel composites gets zeros of either sign, as on a whole frame;
+ *   - over a partition of the tile rows into strips the strips' gradients, the camera's included,
+ *     add up to the whole frame's up to float32 rounding.
+ * deterministic == 1: the same bits on every call, as gsr_backward_ordered.  The slots exist for
+ * the strip's (Gaussian, tile) pairs only: with K the strip's num_rendered the workspace is 144 B
+ * (160 B with plane gradients) plus 4 B of marks per list entry of the strip, and K < 2^30 is asked
+ * of the strip's K.  The gather's order is a function of a Gaussian's strip rect and marks alone, so
+ * a Gaussian whose rect lies wholly inside the strip's rows has the bits of the whole-frame
+ * deterministic backward under the image gradient zeroed outside the strip, and the strip
+ * (0, grid_y) has those bits for every Gaussian and for the camera.
+ * tile_row_begin == tile_row_end == 0 is gsr_backward_ordered itself: the same kernels, the same
+ * arguments.  A bad strip (begin < 0, end > grid_y, begin >= end): GSR_E_INVALID, nothing written.
+ * Everything else is gsr_backward_ordered's: a function of its inputs, zeroes then fills each
+ * gradient, debug, gsr_backward_times, planes, camera, filter and order as there; gsr_get_binning
+ * afterwards exports the strip's lists, as after a strip forward. */
+int gsr_backward_strip(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                       const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                       const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                       const gsr_backward_order *order, gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

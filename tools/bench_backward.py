@@ -30,10 +30,17 @@ the slab scan, the zeroing of the marks and the gather are inside blend_bwd_ms);
 --planes, --camera and --antialiasing.  The atomic figures are then not reported: the mode has no
 float atomics.
 
+--strip r/N: forward and backward on strip r of the equal split of the tile rows into N
+(strips.strip_rows): the strip forward, and gsr_backward_strip under strip-local gradients; with
+any of the options above.  Also reports the strip's tile rows and, with --deterministic, the
+slots' and marks' workspace for the strip's num_rendered (det_workspace_MB).  The atomic figures
+are not reported for a strip (--contributions is the whole frame's).
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
                                       [--camera] [--antialiasing] [--deterministic]
+                                      [--strip r/N]
 """
 import argparse
 import ctypes
@@ -62,19 +69,27 @@ def worker(a):
     lib = _lib.load_library()
     ctx = _lib.context(0)
     view, proj, campos, tx, ty, _ = scene.cams[0]
-    color = torch.empty((3, scene.H, scene.W), device=dev)
-    dL = torch.randn((3, scene.H, scene.W), device=dev)
+    n_rows, fwd_strip, bwd_strip = scene.H, {}, {}
+    if a.strip:
+        from gaussiansplattingviewer_amd.strips import strip_pixel_rows, strip_rows
+        r, n = (int(v) for v in a.strip.split("/"))
+        tile_rows = strip_rows((scene.H + 15) // 16, n, r)
+        n_rows = strip_pixel_rows(tile_rows, scene.H)[1]
+        fwd_strip = {"tile_rows": tile_rows}
+        bwd_strip = {"tile_rows": tile_rows, "image_height": scene.H}
+    color = torch.empty((3, n_rows, scene.W), device=dev)
+    dL = torch.randn((3, n_rows, scene.W), device=dev)
     extras, plane_grads = (), {}
     aa = {"antialiasing": True} if a.antialiasing else {}
     if a.planes:
         extras = ("depth_map", "inv_depth_map", "final_T")
-        plane_grads = {f"dL_d{n}": torch.randn((scene.H, scene.W), device=dev) for n in extras}
+        plane_grads = {f"dL_d{n}": torch.randn((n_rows, scene.W), device=dev) for n in extras}
 
     def forward():
         return rasterize_gaussians_native(scene.bg, scene.xyz, None, scene.opacity, scene.scale,
                                           scene.rot, 1.0, None, view, proj, tx, ty, scene.H,
                                           scene.W, scene.sh, scene.deg, campos, False, False,
-                                          out_color=color, extras=extras, **aa)
+                                          out_color=color, extras=extras, **aa, **fwd_strip)
 
     def backward():
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
@@ -82,11 +97,13 @@ def worker(a):
                                                    tx, ty, dL, scene.sh, scene.deg, campos,
                                                    camera=bool(a.camera),
                                                    deterministic=bool(a.deterministic),
-                                                   **plane_grads, **aa)
+                                                   **plane_grads, **aa, **bwd_strip)
 
     out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
            "camera": bool(a.camera), "antialiasing": bool(a.antialiasing),
            "deterministic": bool(a.deterministic)}
+    if a.strip:
+        out.update(strip=a.strip, tile_rows=list(fwd_strip["tile_rows"]), rows=n_rows)
     if a.step == "forward":
         for _ in range(a.warmup):
             forward()
@@ -101,6 +118,9 @@ def worker(a):
         out.update(forward_ms=round(statistics.fmean(ms), 5),
                    forward_ms_min_max=[round(min(ms), 5), round(max(ms), 5)],
                    num_rendered=res.num_rendered)
+        if a.deterministic:  # 4 slots of 9 (10) floats and 4 marks per list entry
+            out.update(det_workspace_MB=round(
+                res.num_rendered * (4 * 4 * (10 if a.planes else 9) + 4) / 1e6, 2))
         # the per-Gaussian stage of the forward: the library's own stage events, the mean over
         # these frames
         _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
@@ -145,6 +165,9 @@ def main():
                     help="gsr_forward_filtered / gsr_backward_filtered with antialiasing = 1")
     ap.add_argument("--deterministic", action="store_true",
                     help="gsr_backward_ordered with deterministic = 1: bit-reproducible gradients")
+    ap.add_argument("--strip", default=None, metavar="r/N",
+                    help="strip r of the equal split of the tile rows into N: the strip forward "
+                         "and gsr_backward_strip")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -156,13 +179,14 @@ def main():
                            (["--planes"] if a.planes else []) +
                            (["--camera"] if a.camera else []) +
                            (["--antialiasing"] if a.antialiasing else []) +
-                           (["--deterministic"] if a.deterministic else []),
+                           (["--deterministic"] if a.deterministic else []) +
+                           (["--strip", a.strip] if a.strip else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"bench_backward: the {step} step failed ({r.returncode}); nothing more is run")
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    if a.deterministic:  # plain stores to slots: no atomic traffic to report
+    if a.deterministic or a.strip:  # plain stores to slots: no atomic traffic to report
         print(json.dumps(out))
         return
     atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0))
