@@ -55,6 +55,12 @@ A strip of tile rows (`GaussianRasterizationSettings(tile_rows=)`): the forward 
 `_C.rasterize_gaussians_backward_strip_ext(<the backward's arguments>, deterministic,
 tile_row_begin, tile_row_end, image_height)` is `gsr_backward_strip` -- the image-like tensors are
 then strip-local, and image_height is the frame's.
+Feature channels (`GaussianRasterizer(...)(..., features=)`):
+`_C.rasterize_gaussians_features(<the 19 arguments>, planes, antialiasing, tile_row_begin,
+tile_row_end, features)` is `gsr_forward_features` -> the 6-tuple of `rasterize_gaussians_ext`,
+then feature_map (C, rows, W); `_C.rasterize_gaussians_backward_features(<the backward's
+arguments>, deterministic, tile_row_begin, tile_row_end, image_height, features,
+dL_dfeature_map)` is `gsr_backward_features` -> the 11-tuple, then dL_dfeatures (P, C).
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -64,8 +70,9 @@ from __future__ import annotations
 try:
     from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
+                          rasterize_gaussians_backward_features,
                           rasterize_gaussians_backward_strip_ext, rasterize_gaussians_ext,
-                          rasterize_gaussians_shaded)
+                          rasterize_gaussians_features, rasterize_gaussians_shaded)
 except ImportError as e:  # pragma: no cover - a build problem, reported loudly
     raise ImportError(f"gaussiansplattingviewer_amd._native is not built or does not load ({e}); "
                       "run __graft_entry__.build()") from e

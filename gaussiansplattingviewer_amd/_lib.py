@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
-    "gsr_backward_strip",
+    "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -127,6 +127,21 @@ class GsrBackwardOrder(ctypes.Structure):
     _fields_ = [("deterministic", ctypes.c_int32)]
 
 
+MAX_FEATURES = 256  # GSR_MAX_FEATURES
+
+
+class GsrFeatureOutputs(ctypes.Structure):
+    """gsr_feature_outputs: gsr_forward_features' per-Gaussian rows [P, C] and planes [C, rows, W]."""
+    _fields_ = [("C", ctypes.c_int32), ("features", ctypes.c_void_p),
+                ("feature_map", ctypes.c_void_p)]
+
+
+class GsrFeatureGradients(ctypes.Structure):
+    """gsr_feature_gradients: gsr_backward_features' rows, the planes' gradient and dL_dfeatures."""
+    _fields_ = [("C", ctypes.c_int32), ("features", ctypes.c_void_p),
+                ("dL_dfeature_map", ctypes.c_void_p), ("dL_dfeatures", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -151,6 +166,11 @@ _ADDITIVE = {
                              GsrFilterSettings, GsrBackwardOrder, GsrGradients),
     "gsr_backward_strip": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
                            GsrFilterSettings, GsrBackwardOrder, GsrGradients),
+    "gsr_forward_features": (GsrOutputs, GsrDepthOutputs, GsrSurfaceOutputs, GsrFilterSettings,
+                             GsrFeatureOutputs),
+    "gsr_backward_features": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                              GsrFilterSettings, GsrBackwardOrder, GsrFeatureGradients,
+                              GsrGradients),
 }
 
 _lock = threading.Lock()
@@ -282,6 +302,13 @@ def backward_ordered_fn(lib: ctypes.CDLL):
 def backward_strip_fn(lib: ctypes.CDLL):
     """gsr_backward_strip of a loaded library; RuntimeError if that build does not have it."""
     return _optional_fn(lib, "gsr_backward_strip", "a backward on a tile row strip needs")
+
+
+def features_fns(lib: ctypes.CDLL):
+    """(gsr_forward_features, gsr_backward_features) of a loaded library; RuntimeError if that
+    build does not have them."""
+    return _optional_fn(lib, "gsr_forward_features / gsr_backward_features",
+                        "per-Gaussian feature channels need")
 
 
 def check(rc: int, what: str) -> int:

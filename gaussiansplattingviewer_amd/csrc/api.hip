@@ -377,6 +377,10 @@ struct Frame {
     // gsr_forward_surface: the median planes stage 7 also fills (both NULL: none)
     float *median_depth = nullptr;
     int32_t *median_id = nullptr;
+    // gsr_forward_features: the planes stage 7's feature launches fill (feature_map NULL: none)
+    int feat_C = 0;
+    const float *features = nullptr;
+    float *feature_map = nullptr;
     bool no_blend = false;  // gsr_backward's rebuild: everything up to the lists, no stage 7
     uint64_t K = 0;   // upstream's num_rendered
     uint64_t KL = 0;  // pairs in the list (K, or fewer with tight binning)
@@ -397,6 +401,7 @@ struct FrameRequest {
     // antialiased frames share their graphs
     bool antialiasing = false;
     bool no_blend = false;
+    const gsr_feature_outputs *feat = nullptr;  // NULL, or checked by gsr_forward_features
 };
 
 int stage_end(gsr_context *ctx, const Frame &f, int i) {
@@ -450,6 +455,8 @@ int setup_frame(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_setti
     if (rq.depth) f.depth_map = rq.depth->depth_map, f.inv_depth_map = rq.depth->inv_depth_map;
     if (rq.surface)
         f.median_depth = rq.surface->median_depth, f.median_id = rq.surface->median_id;
+    if (rq.feat && rq.feat->feature_map)
+        f.feat_C = rq.feat->C, f.features = rq.feat->features, f.feature_map = rq.feat->feature_map;
     f.no_blend = rq.no_blend;
     f.P = P;
     f.W = W;
@@ -890,17 +897,20 @@ int launch_blend(gsr_context *ctx, const Frame &f, const gsr_raster_settings *st
         const GsrDepthArgs da{f.pa.sort_keys, f.depth_map, f.inv_depth_map};
         const GsrSurfaceArgs ma{f.median_depth, f.median_id};
         GSR_HIP(gsr_launch_blend_surface(ba, da, ma, f.s), "surface blend launch");
-        return GSR_OK;
-    }
-    if (f.depth_map || f.inv_depth_map) {
+    } else if (f.depth_map || f.inv_depth_map) {
         // z by Gaussian id from the depth keys: written by this frame's preprocess on f.s and only
         // read since (the depth sort takes them const); the next writer is the next call's
         // preprocess or gsr_depth_argsort, queued behind this blend (order_stream)
         const GsrDepthArgs da{f.pa.sort_keys, f.depth_map, f.inv_depth_map};
         GSR_HIP(gsr_launch_blend_depth(ba, da, f.s), "depth blend launch");
-        return GSR_OK;
+    } else {
+        GSR_HIP(gsr_launch_blend(ba, f.s), "blend launch");
     }
-    GSR_HIP(gsr_launch_blend(ba, f.s), "blend launch");
+    // gsr_forward_features: launches of their own over the same lists, behind the colour's (with
+    // frame graphs they honour the list_n > list_cap early return through ba, as the colour's)
+    if (f.feature_map)
+        GSR_HIP(gsr_launch_blend_features(ba, f.features, f.feat_C, f.feature_map, f.s),
+                "feature blend launch");
     return GSR_OK;
 }
 
@@ -1229,6 +1239,10 @@ int forward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings 
         if (f.median_id)  // -1: no surface
             GSR_HIP(hipMemsetAsync(f.median_id, 0xFF, (size_t)f.rows_out * f.W * sizeof(int32_t), s),
                     "hipMemsetAsync(median id)");
+        if (f.feature_map)
+            GSR_HIP(hipMemsetAsync(f.feature_map, 0,
+                                   (size_t)f.feat_C * f.rows_out * f.W * sizeof(float), s),
+                    "hipMemsetAsync(feature map)");
         GSR_HIP(hipMemsetAsync(ctx->ranges_words(), 0, f.T_strip * 8, s), "hipMemsetAsync");
         // an empty list in the per-pair form's buffers; no stage ran, so no timed frame
         f.K = f.KL = 0;
@@ -1522,6 +1536,32 @@ int gsr_forward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
     return forward_entry(ctx, g, st, out, stream, {GSR_SHADE_SPLAT, depth, surface, true});
 }
 
+// NULL if the struct's C and features can be used, else what is wrong with them.
+static const char *feature_fault(int32_t C, const float *features, int64_t P) {
+    if (C < 1 || C > GSR_MAX_FEATURES) return "C must be in 1..GSR_MAX_FEATURES";
+    if (P > 0 && !features) return "features is NULL";
+    return nullptr;
+}
+
+int gsr_forward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                         gsr_outputs *out, const gsr_depth_outputs *depth,
+                         const gsr_surface_outputs *surface, const gsr_filter_settings *filter,
+                         const gsr_feature_outputs *feat, void *stream) {
+    if (!feat || !feat->feature_map)
+        return gsr_forward_filtered(ctx, g, st, out, depth, surface, filter, stream);
+    if (!g) return fail(GSR_E_INVALID, "gsr_forward: NULL argument");
+    if (const char *why = feature_fault(feat->C, feat->features, g->P))
+        return fail(GSR_E_INVALID, std::string("gsr_forward_features: ") + why + " (C = " +
+                                       std::to_string(feat->C) + ")");
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_forward_features: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    FrameRequest rq{GSR_SHADE_SPLAT, depth, surface, aa != 0};
+    rq.feat = feat;
+    return forward_entry(ctx, g, st, out, stream, rq);
+}
+
 // The gradients of the splat composite.  Everything is rebuilt from the arguments -- the
 // per-Gaussian stage, the depth sort and upstream's (untight) lists, the direct way: no recorded
 // graph is replayed, none is invalidated beyond what a forward of the same shape would -- so
@@ -1542,7 +1582,8 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
                     const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
                     const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
                     const std::string &fn, bool antialiasing = false,
-                    bool deterministic = false, bool strips = false) {
+                    bool deterministic = false, bool strips = false,
+                    const gsr_feature_gradients *ft = nullptr) {
     if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
     const bool strip = st->tile_row_begin != 0 || st->tile_row_end != 0;
     if (strip && !strips)
@@ -1559,7 +1600,7 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         pl && (pl->dL_ddepth_map || pl->dL_dinv_depth_map || pl->dL_dfinal_T);
     float *const dL_ddepths = pl ? pl->dL_ddepths : nullptr;
     if (P > 0) {
-        if (!in->dL_dcolor && !planes)
+        if (!in->dL_dcolor && !planes && !ft)
             return fail(GSR_E_INVALID, fn + (pl ? ": dL_dcolor or a plane gradient is required"
                                                 : ": dL_dcolor is required"));
         if ((g->shs == nullptr) == (g->colors_precomp == nullptr))
@@ -1663,6 +1704,9 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         GSR_HIP(hipMemsetAsync(ctx->grad2d.get(), 0, (size_t)P * kGradRow * sizeof(float), s),
                 "hipMemsetAsync(grad2d)");
     }
+    if (ft && ft->dL_dfeatures)  // zeroed, then filled: culled Gaussians keep exact zeros
+        GSR_HIP(hipMemsetAsync(ft->dL_dfeatures, 0, (size_t)P * ft->C * sizeof(float), s),
+                "hipMemsetAsync(dL_dfeatures)");
     GsrBlendBwdArgs ba{};
     ba.ranges = ctx->ranges_local.get();
     ba.point_list = l.point_list;
@@ -1688,8 +1732,13 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
                     "blend backward launch");
         else if (planes)
             GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s, sp), "blend backward launch");
-        else
+        else if (ba.dL_dcolor)  // (NULL: a feature gradient alone, no colour pass)
             GSR_HIP(gsr_launch_blend_bwd(ba, s, sp), "blend backward launch");
+        // gsr_backward_features: beside the pass above, into the same zeroed rows
+        if (ft)
+            GSR_HIP(gsr_launch_blend_bwd_features(ba, ft->features, ft->C, ft->dL_dfeature_map,
+                                                  ft->dL_dfeatures, s, sp),
+                    "feature blend backward launch");
     }
     if (deterministic)  // every word of every row, zeros where nothing was stored
         GSR_HIP(gsr_launch_grad_rows_gather(da, P, planes, ctx->grad2d.get(), s),
@@ -1817,6 +1866,34 @@ int gsr_backward_strip(gsr_context *ctx, const gsr_gaussians *g, const gsr_raste
                                        std::to_string(filter->antialiasing));
     return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_strip", aa != 0,
                     det != 0, true);
+}
+
+int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                          const gsr_backward_order *order, const gsr_feature_gradients *feat,
+                          gsr_gradients *gr, void *stream) {
+    if (!feat || !feat->dL_dfeature_map)
+        return gsr_backward_strip(ctx, g, st, in, planes, camera, filter, order, gr, stream);
+    if (!ctx || !g || !st || !in || !gr)
+        return fail(GSR_E_INVALID, "gsr_backward_features: NULL argument");
+    if (const char *why = feature_fault(feat->C, feat->features, g->P))
+        return fail(GSR_E_INVALID, std::string("gsr_backward_features: ") + why + " (C = " +
+                                       std::to_string(feat->C) + ")");
+    const int det = order ? order->deterministic : 0;
+    if (det == 1)
+        return fail(GSR_E_INVALID,
+                    "gsr_backward_features: deterministic == 1 with a feature gradient: the "
+                    "deterministic slots hold 9 or 10 sums and have no room for C more");
+    if (det != 0)
+        return fail(GSR_E_INVALID, "gsr_backward_features: deterministic must be 0 or 1, got " +
+                                       std::to_string(det));
+    const int aa = filter_antialiasing(filter);
+    if (aa < 0)
+        return fail(GSR_E_INVALID, "gsr_backward_features: antialiasing must be 0 or 1, got " +
+                                       std::to_string(filter->antialiasing));
+    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_features", aa != 0,
+                    false, true, feat);
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

@@ -46,6 +46,11 @@
 //    gradients; the gate zeroes the rebuilt radius of every Gaussian without a tile in the strip,
 //    so the eight per-Gaussian kernels leave it as they leave a culled one.  The kernels above
 //    compile as before (profiles/backward_strips_resources.txt).
+//  * k_blend_bwd_features_q -- the blend's backward for 16, 8 or 4 feature channels of the caller's
+//    own (gsr_backward_features): a body of its own beside blend_bwd, launched per
+//    chunk of channels over the same lists; it adds its share of the six geometry sums to the same
+//    rows and the channels' sums straight to dL_dfeatures.  The kernels above compile as before
+//    (profiles/features_resources.txt).
 #include "gsr_internal.h"
 
 #include <algorithm>
@@ -344,6 +349,209 @@ __global__ __launch_bounds__(256) void k_blend_bwd_planes_det_strip_q(const GsrB
                                                                       const GsrDetBwdArgs d,
                                                                       const GsrStripBwdArgs r) {
     blend_bwd<true, true, true>(a, p, d, r);
+}
+
+// ---- the feature channels' blend backward (gsr_backward_features) ----------------
+// What one launch differentiates: channels [c0, c0 + kC) of the Gaussians' feature rows.
+struct FeatBwdArgs {
+    const float *features;         // [P, C]
+    const float *dL_dfeature_map;  // [C, rows, W]
+    float *dL_dfeatures;           // [P, C], zeroed by the caller, or NULL
+    int C, c0;
+    int vec4;  // 16-B aligned feature rows
+};
+
+// blend_bwd's two passes for kC channels of the caller's own in place of the colours: the pixel
+// keeps kC gradients gF, the per-splat term is gF . f_i (f_i the splat's feature words, staged into
+// LDS by the lane that stages the splat and read by broadcast), the carried value starts at 0 (no
+// background), and a splat has 6 + kC sums per quadrant: words 0..5 (d/dmean2D, d/dconic,
+// d/dopacity) are added to the Gaussian's row of a.grad2d beside the colour pass's, the kC sums
+// gF_c w straight to dL_dfeatures[id * C + c0 + c].  Channels at or beyond C read as zero and are
+// neither read from memory nor written.
+template <int kC, bool kStrip>
+__device__ __forceinline__ void blend_bwd_features(const GsrBlendBwdArgs &a, const FeatBwdArgs &ft,
+                                                   const GsrStripBwdArgs &r) {
+    static_assert(kC % 4 == 0, "feature chunks are whole float4s");
+    using BwdSplat = BwdSplatT<false>;
+    constexpr int kSums = 6 + kC;
+    __shared__ BwdSplat s_spl_q[4][64];
+    __shared__ uint32_t s_id_q[4][64];
+    __shared__ float s_red_q[4][64 * kSums];
+    __shared__ alignas(16) float s_ft_q[4][64 * kC];
+
+    const uint32_t tile = blockIdx.x;
+    if (tile >= a.n_tiles) return;
+    const uint32_t quad = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    BwdSplat *const s_spl = s_spl_q[quad];
+    uint32_t *const s_id = s_id_q[quad];
+    float *const s_red = s_red_q[quad];
+    float *const s_ft = s_ft_q[quad];
+    const uint32_t tx = tile % a.grid_x, ty = tile / a.grid_x;
+    const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
+    int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
+    if constexpr (kStrip) qy0 = (int)(r.row_begin + ty) * GSR_TILE_Y + (int)(quad >> 1) * 8;
+    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
+    const bool inside = px < a.W && py < a.H;
+    const float pfx = (float)px, pfy = (float)py;
+    const float X0 = (float)qx0, Y0 = (float)qy0;
+    const uint2 range = a.ranges[tile];
+    if (__ballot(inside) == 0ull || range.x >= range.y) return;
+    const int n_ch = ft.C - ft.c0;  // channels of this launch that exist (the rest: zeros)
+
+    // blend_bwd's stage; with_f (the back-to-front pass): also the splat's feature words
+    auto stage = [&](uint32_t start, auto with_f) {
+        const uint32_t idx = start + (uint32_t)lane;
+        const bool valid = idx < range.y;
+        SplatRecord rec;
+        uint32_t id = 0u;
+        if (valid) {
+            id = a.point_list[idx] & a.id_mask;
+            rec = a.records[id];
+        }
+        bool keep = valid;
+        if (valid && a.cull)
+            keep = may_touch(rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.z, rec.b.w,
+                             2.0f * rec.c.x, X0, X0 + 7, Y0, Y0 + 7);
+        const uint64_t bal = __ballot(keep);
+        if (keep) {
+            const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+            const int slot = __popcll(bal & lt);
+            s_spl[slot].g = rec.a;
+            s_spl[slot].q = make_float4(rec.b.x, rec.b.y, rec.c.y, rec.c.z);
+            s_spl[slot].e = make_float2(rec.c.w, __uint_as_float(idx - range.x + 1u));
+            s_id[slot] = id;
+            if constexpr (decltype(with_f)::value) {
+                const float *src = ft.features + (size_t)id * ft.C + ft.c0;
+                float *dst = s_ft + slot * kC;
+                if (ft.vec4) {
+#pragma unroll
+                    for (int c = 0; c < kC; c += 4)
+                        *reinterpret_cast<float4 *>(dst + c) =
+                            c < n_ch ? *reinterpret_cast<const float4 *>(src + c)
+                                     : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < kC; ++c) dst[c] = c < n_ch ? src[c] : 0.0f;
+                }
+            }
+        }
+        return __popcll(bal);
+    };
+
+    // ---- front to back: the forward's decisions, as blend_bwd ---------------------------------
+    float T = inside ? 1.0f : -1.0f;
+    uint32_t last = 0u, chunks = 0u;
+    for (uint32_t start = range.x; start < range.y; start += 64) {
+        ++chunks;
+        const int count = stage(start, std::false_type{});
+        for (int k = 0; k < count; ++k) {
+            const BwdSplat sp = s_spl[k];
+            const float dx = sp.g.x - pfx, dy = sp.g.y - pfy;
+            const float power = -0.5f * (sp.g.z * dx * dx + sp.q.x * dy * dy) - sp.g.w * dx * dy;
+            const float alpha = fminf(0.99f, sp.q.y * exp_core(power));
+            const bool vis = !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
+            const float test_T = T * (1 - alpha);
+            const bool acc = vis && !(test_T < 0.0001f);
+            const bool term = vis && (test_T < 0.0001f);
+            T = acc ? test_T : (term ? -fabsf(T) : T);
+            last = acc ? __float_as_uint(sp.e.y) : last;
+        }
+        if (__ballot(!(T <= 0.0f)) == 0ull) break;
+    }
+
+    // ---- back to front -------------------------------------------------------------------------
+    size_t plane = (size_t)a.H * a.W, pid = (size_t)(inside ? py : 0) * a.W + (inside ? px : 0);
+    if constexpr (kStrip) {
+        plane = (size_t)r.rows_out * a.W;
+        pid = (size_t)(inside ? py - r.y0 : 0) * a.W + (inside ? px : 0);
+    }
+    float gF[kC];
+#pragma unroll
+    for (int c = 0; c < kC; ++c)
+        gF[c] = inside && c < n_ch ? ft.dL_dfeature_map[(size_t)(ft.c0 + c) * plane + pid] : 0.0f;
+    float Tc = fabsf(T);
+    float rr = 0.0f;  // the features' background is 0
+    for (uint32_t ch = chunks; ch-- > 0u;) {
+        const int count = stage(range.x + 64u * ch, std::true_type{});
+        for (int kg = (count - 1) >> 4; kg >= 0; --kg) {
+            const int k_lo = 16 * kg, k_hi = min(count, k_lo + 16);
+            float s[kSums];
+#pragma unroll
+            for (int w = 0; w < kSums; ++w) s[w] = 0.f;
+            uint32_t touched = 0u;
+            for (int k = k_hi; k-- > k_lo;) {
+                const BwdSplat sp = s_spl[k];
+                const float dx = sp.g.x - pfx, dy = sp.g.y - pfy;
+                const float power =
+                    -0.5f * (sp.g.z * dx * dx + sp.q.x * dy * dy) - sp.g.w * dx * dy;
+                const float G = exp_core(power);
+                const float oG = sp.q.y * G;
+                const float alpha = fminf(0.99f, oG);
+                const bool con = inside && __float_as_uint(sp.e.y) <= last && !(power > 0.0f) &&
+                                 !(alpha < 1.0f / 255.0f);
+                if (__ballot(con) == 0ull) continue;
+                touched |= 1u << (k & 15);
+                const float Ti = Tc / (1.0f - alpha);
+                const float w = alpha * Ti;
+                float gc = 0.0f;
+                float v[kSums];
+#pragma unroll
+                for (int c = 0; c < kC; c += 4) {
+                    const float4 f = *reinterpret_cast<const float4 *>(s_ft + k * kC + c);
+                    gc += gF[c] * f.x;
+                    gc += gF[c + 1] * f.y;
+                    gc += gF[c + 2] * f.z;
+                    gc += gF[c + 3] * f.w;
+                }
+                const float dLa = Ti * (gc - rr);
+                const bool open = con && !(oG > 0.99f);
+                const float dLp = open ? dLa * oG : 0.0f;
+                v[0] = dLp * (-sp.g.z * dx - sp.g.w * dy);
+                v[1] = dLp * (-sp.q.x * dy - sp.g.w * dx);
+                v[2] = dLp * (-0.5f * dx * dx);
+                v[3] = dLp * (-dx * dy);
+                v[4] = dLp * (-0.5f * dy * dy);
+                v[5] = open ? dLa * G : 0.0f;
+#pragma unroll
+                for (int c = 0; c < kC; ++c) v[6 + c] = con ? gF[c] * w : 0.0f;
+                rr = con ? alpha * gc + (1.0f - alpha) * rr : rr;
+                Tc = con ? Ti : Tc;
+                const bool mine = (lane & 15) == (k & 15);
+#pragma unroll
+                for (int i = 0; i < kSums; ++i) {
+                    const float t = row_sum(v[i]);
+                    s[i] = mine ? t : s[i];
+                }
+            }
+            if (touched == 0u) continue;
+            // slot-major in LDS, the four rows of a slot side by side, as blend_bwd; word t of
+            // the group's slots x kSums: the first six to the 2D gradient row, the rest to the
+            // Gaussian's feature gradient row -- consecutive lanes on consecutive words of both
+            float *mine_s = s_red + ((lane & 15) * 4 + (lane >> 4)) * kSums;
+#pragma unroll
+            for (int i = 0; i < kSums; ++i) mine_s[i] = s[i];
+            const int n = (k_hi - k_lo) * kSums;
+            for (int t = lane; t < n; t += 64) {
+                const int slot = t / kSums, word = t - slot * kSums;
+                if (!((touched >> slot) & 1u)) continue;
+                const float *q4 = s_red + slot * 4 * kSums + word;
+                const float sum = (q4[0] + q4[kSums]) + (q4[2 * kSums] + q4[3 * kSums]);
+                const size_t id = s_id[k_lo + slot];
+                if (word < 6)
+                    atomicAdd(&a.grad2d[id * kGradRow + word], sum);
+                else if (ft.dL_dfeatures && word - 6 < n_ch)
+                    atomicAdd(&ft.dL_dfeatures[id * ft.C + ft.c0 + (word - 6)], sum);
+            }
+        }
+    }
+}
+
+template <int kC, bool kStrip>
+__global__ __launch_bounds__(256) void k_blend_bwd_features_q(const GsrBlendBwdArgs a,
+                                                              const FeatBwdArgs ft,
+                                                              const GsrStripBwdArgs r) {
+    blend_bwd_features<kC, kStrip>(a, ft, r);
 }
 
 // gsr_launch_strip_gate: a Gaussian without a tile in the strip reads as culled from here on.
@@ -705,6 +913,41 @@ hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneB
     else
         hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
     return hipGetLastError();
+}
+
+hipError_t gsr_launch_blend_bwd_features(const GsrBlendBwdArgs &a, const float *features, int C,
+                                         const float *dL_dfeature_map, float *dL_dfeatures,
+                                         hipStream_t s, const GsrStripBwdArgs *strip) {
+    if (!features || !dL_dfeature_map || C < 1) return hipErrorInvalidValue;
+    if (a.n_tiles == 0) return hipSuccess;
+    if (!strip_ok(a, strip)) return hipErrorInvalidValue;
+    FeatBwdArgs ft{features, dL_dfeature_map, dL_dfeatures, C, 0,
+                   (reinterpret_cast<uintptr_t>(features) & 15) == 0 && C % 4 == 0};
+    const GsrStripBwdArgs r = strip ? *strip : GsrStripBwdArgs{};
+    while (ft.c0 < C) {
+        // the rest of the channels in the narrowest of 4, 8, 16 that holds it, else 16: at C3 one
+        // launch of 16 (22 row sums per splat, 3 waves per SIMD) takes 1.66 ms where two of 8
+        // (14 row sums, 4 waves) take 2.19 ms -- the two passes over the list, the exp and the six
+        // geometry sums are paid per launch
+        const int rest = C - ft.c0, w = rest > 8 ? 16 : rest > 4 ? 8 : 4;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(a.n_tiles), dim3(256), 0, s, a, ft, r);
+        };
+        if (w == 4) {
+            if (strip) launch(k_blend_bwd_features_q<4, true>);
+            else launch(k_blend_bwd_features_q<4, false>);
+        } else if (w == 8) {
+            if (strip) launch(k_blend_bwd_features_q<8, true>);
+            else launch(k_blend_bwd_features_q<8, false>);
+        } else {
+            if (strip) launch(k_blend_bwd_features_q<16, true>);
+            else launch(k_blend_bwd_features_q<16, false>);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        ft.c0 += w;
+    }
+    return hipSuccess;
 }
 
 hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,

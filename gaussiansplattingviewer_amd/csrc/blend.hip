@@ -97,11 +97,21 @@ struct StagedSplat {
 // the loop's own back edge (one v_cmp, the scalar branch it already had) and the serial C3 blend
 // goes 113.5 -> 101-103 us; a test every 2, 4 or 8 pairs compiles to a second branch and a
 // recomputed LDS address per pair and gains less (108-110 us).
+//
+// kFeat (k_blend_features_q, gsr_forward_features): the composite with kFeat channels of the
+// caller's own in place of the three colours: channels [ft.c0, ft.c0 + kFeat) of the Gaussians'
+// feature rows ([P, C] floats), each accumulated under the colour's weight as a colour channel is
+// (the twin property).  The lane that stages a splat gathers its kFeat words into LDS,
+// slot for slot (words at or beyond C are zeros and never read from memory); the composite reads
+// the row by broadcast.  No colour, final_T, n_contrib, depth or median work: the epilogue writes
+// the planes below C only.  Without kFeat none of it is compiled.
 constexpr int kStopPairs = 1;
-template <bool kFast, bool kContrib, bool kDepth, bool kMedian = false>
+template <bool kFast, bool kContrib, bool kDepth, bool kMedian = false, int kFeat = 0>
 __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
                                         const GsrDepthArgs &d,
-                                        const GsrSurfaceArgs &m = GsrSurfaceArgs{}) {
+                                        const GsrSurfaceArgs &m = GsrSurfaceArgs{},
+                                        const GsrFeatureArgs &ft = GsrFeatureArgs{}) {
+    static_assert(kFeat % 4 == 0 && kFeat <= 64, "feature chunks are whole float4s, a lane a word");
     __shared__ StagedSplat s_spl_q[4][64];  // per quadrant wave
     // paired colour / bound words (see staging)
     constexpr bool kPair = kFast && !kContrib && !kMedian;
@@ -117,6 +127,11 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
         __shared__ alignas(16) float2 s_zf_q[4][64];  // (a pair: one 16-B read)
         s_zf = s_zf_q[quad];
     }
+    float *s_ft = nullptr;  // kFeat: the staged splats' feature words, slot for slot
+    if constexpr (kFeat > 0) {
+        __shared__ alignas(16) float s_ft_q[4][64 * kFeat];
+        s_ft = s_ft_q[quad];
+    }
     const uint32_t tx = tile % a.grid_x, ty_local = tile / a.grid_x, ty = a.row_begin + ty_local;
     const int qx0 = (int)tx * GSR_TILE_X + (int)(quad & 1u) * 8;
     const int qy0 = (int)ty * GSR_TILE_Y + (int)(quad >> 1) * 8;
@@ -131,6 +146,7 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
     // done carried in the sign of T (T <= 0: the lane composites no more)
     float T = inside ? 1.0f : -1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
     float D0 = 0.0f, D1 = 0.0f;  // kDepth: sum z w, sum (1 / z) w
+    [[maybe_unused]] float F[kFeat > 0 ? kFeat : 1] = {};  // kFeat: sum f_c w
     uint32_t last_contributor = 0;
     uint32_t median_pos = 0;  // kMedian: list position + 1 of the median splat, 0 = none (yet)
     auto live_any = [&]() { return __ballot(!(T <= 0.0f)) != 0ull; };
@@ -138,8 +154,18 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
 
     // kBound (fast form): test upstream's power > 0 skip as p > bound -- only chunks holding a
     // conic that is not positive definite need it (staging below)
-    auto composite = [&](const StagedSplat &sp, float fz, float fiz, auto bound_tag) {
+    // frow (kFeat): the splat's feature words in LDS
+    auto composite = [&](const StagedSplat &sp, float fz, float fiz, auto bound_tag,
+                         [[maybe_unused]] const float *frow = nullptr) {
         constexpr bool kBound = decltype(bound_tag)::value;
+        [[maybe_unused]] float f[kFeat > 0 ? kFeat : 1];
+        if constexpr (kFeat > 0) {
+#pragma unroll
+            for (int c = 0; c < kFeat; c += 4) {
+                const float4 v = *reinterpret_cast<const float4 *>(frow + c);
+                f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
+            }
+        }
         bool vis, acc, term;
         float test_T;
         if (kFast) {
@@ -161,9 +187,14 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             const bool lo = test_T < 0.0001f;
             const float T_next = lo ? -fabsf(T) : test_T;
             const float wgt = fabsf(T) - fabsf(T_next);
-            C0 = __builtin_fmaf(sp.q.z, wgt, C0);
-            C1 = __builtin_fmaf(sp.q.w, wgt, C1);
-            C2 = __builtin_fmaf(sp.e.x, wgt, C2);
+            if constexpr (kFeat == 0) {
+                C0 = __builtin_fmaf(sp.q.z, wgt, C0);
+                C1 = __builtin_fmaf(sp.q.w, wgt, C1);
+                C2 = __builtin_fmaf(sp.e.x, wgt, C2);
+            } else {
+#pragma unroll
+                for (int c = 0; c < kFeat; ++c) F[c] = __builtin_fmaf(f[c], wgt, F[c]);
+            }
             if constexpr (kDepth) {
                 D0 = __builtin_fmaf(fz, wgt, D0);
                 D1 = __builtin_fmaf(fiz, wgt, D1);
@@ -183,9 +214,14 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             test_T = T * (1 - alpha);
             acc = vis && !(test_T < 0.0001f);
             term = vis && (test_T < 0.0001f);
-            C0 = acc ? C0 + sp.q.z * alpha * T : C0;
-            C1 = acc ? C1 + sp.q.w * alpha * T : C1;
-            C2 = acc ? C2 + sp.e.x * alpha * T : C2;
+            if constexpr (kFeat == 0) {
+                C0 = acc ? C0 + sp.q.z * alpha * T : C0;
+                C1 = acc ? C1 + sp.q.w * alpha * T : C1;
+                C2 = acc ? C2 + sp.e.x * alpha * T : C2;
+            } else {
+#pragma unroll
+                for (int c = 0; c < kFeat; ++c) F[c] = acc ? F[c] + f[c] * alpha * T : F[c];
+            }
             if constexpr (kDepth) {
                 D0 = acc ? D0 + fz * alpha * T : D0;
                 D1 = acc ? D1 + fiz * alpha * T : D1;
@@ -210,6 +246,7 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
         float z = 1.0f;  // kDepth: by Gaussian id, as the record
         if constexpr (kDepth)
             if (valid) z = __uint_as_float(d.z_bits[id_next]);
+        [[maybe_unused]] const uint32_t id_cur = id_next;  // kFeat: the feature row's
         if (idx + 64u < range.y) id_next = (a.point_list[idx + 64u] & a.id_mask);
 
         bool keep = valid;
@@ -274,6 +311,22 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
                 s_spl[slot] = st;
             }
             if constexpr (kDepth) s_zf[slot] = make_float2(z, 1.0f / z);
+            if constexpr (kFeat > 0) {
+                // words [c0, c0 + n) of the Gaussian's row; n <= kFeat, the rest of the chunk 0
+                const float *src = ft.features + (size_t)id_cur * ft.C + ft.c0;
+                const int n = ft.C - ft.c0;
+                float *dst = s_ft + slot * kFeat;
+                if (ft.vec4) {  // 16-B aligned rows (C, c0 and so n multiples of 4)
+#pragma unroll
+                    for (int c = 0; c < kFeat; c += 4)
+                        *reinterpret_cast<float4 *>(dst + c) =
+                            c < n ? *reinterpret_cast<const float4 *>(src + c)
+                                  : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < kFeat; ++c) dst[c] = c < n ? src[c] : 0.0f;
+                }
+            }
         }
         int count = __popcll(bal);
         if (count == 0) continue;
@@ -293,6 +346,8 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             }
             if constexpr (kDepth)
                 if (lane == 12) s_zf[count] = make_float2(0.0f, 0.0f);
+            if constexpr (kFeat > 0)  // (weight 0 times a finite feature)
+                if (lane < kFeat) s_ft[count * kFeat + lane] = 0.0f;
             ++count;
         }
         // one wave: its LDS writes above complete before the reads below are served
@@ -304,17 +359,19 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
             do {
                 float4 zf = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pair's {z, 1 / z}
                 if constexpr (kDepth) zf = *reinterpret_cast<const float4 *>(&s_zf[k]);
+                // (kFeat: the pair's feature rows; without it the argument is not read)
+                const float *const f0 = s_ft + k * kFeat, *const f1 = f0 + kFeat;
                 if (kPair) {
                     const float4 e = s_spl[k].e;
                     composite(StagedSplat{s_spl[k].g, s_spl[k].q, make_float4(e.x, 0.0f, e.z, 0.0f)},
-                              zf.x, zf.y, bound_tag);
+                              zf.x, zf.y, bound_tag, f0);
                     composite(StagedSplat{s_spl[k + 1].g, s_spl[k + 1].q,
                                           make_float4(e.y, 0.0f, e.w, 0.0f)},
-                              zf.z, zf.w, bound_tag);
+                              zf.z, zf.w, bound_tag, f1);
                 } else {
                     const StagedSplat a0 = s_spl[k], a1 = s_spl[k + 1];
-                    composite(a0, zf.x, zf.y, bound_tag);
-                    composite(a1, zf.z, zf.w, bound_tag);
+                    composite(a0, zf.x, zf.y, bound_tag, f0);
+                    composite(a1, zf.z, zf.w, bound_tag, f1);
                 }
                 k += 2;
                 // the early exit (kStopPairs above): k and count are wave-uniform, the test is
@@ -329,6 +386,17 @@ __device__ __forceinline__ void blend_q(const GsrBlendArgs &a, uint32_t n_tiles,
         if (!live_any()) break;
     }
 
+    if constexpr (kFeat > 0) {  // the planes below C, no background term; nothing else
+        if (inside) {
+            const size_t pid = (size_t)(py - a.y0) * a.W + px;
+            const size_t plane = (size_t)a.rows_out * a.W;
+            const int n = ft.C - ft.c0;
+#pragma unroll
+            for (int c = 0; c < kFeat; ++c)
+                if (c < n) ft.feature_map[(size_t)(ft.c0 + c) * plane + pid] = F[c];
+        }
+        return;
+    }
     if (inside) {
         const int row = py - a.y0;
         const size_t pid = (size_t)row * a.W + px;
@@ -383,6 +451,18 @@ template <bool kFast, bool kContrib, bool kDepth>
 __global__ __launch_bounds__(256, kDepth ? kDepthWaves : kSurfaceWaves) void k_blend_surface_q(
     const GsrBlendArgs a, uint32_t n_tiles, const GsrDepthArgs d, const GsrSurfaceArgs m) {
     blend_q<kFast, kContrib, kDepth, true>(a, n_tiles, d, m);
+}
+
+// The feature-compositing form (gsr_forward_features): kFeat channels per launch, 12 KiB of staged
+// splats and 1 KiB per channel of their feature words.  At kFeat = 16 that is 28 KiB, 5 blocks per
+// CU, so the bound is 5 waves per SIMD -- 4 for the fast form, whose pair of splats in flight with
+// their two feature rows spilled 56 B per lane at 5 waves' 96 VGPRs; the narrower chunks keep their
+// LDS's share of the registers (profiles/features_resources.txt: no scratch in any).
+template <bool kFast, int kFeat>
+__global__ __launch_bounds__(256, kFeat >= 16 ? (kFast ? 4 : 5)
+                                  : kFeat >= 8 ? 6 : 7) void k_blend_features_q(
+    const GsrBlendArgs a, uint32_t n_tiles, const GsrFeatureArgs ft) {
+    blend_q<kFast, false, false, false, kFeat>(a, n_tiles, GsrDepthArgs{}, GsrSurfaceArgs{}, ft);
 }
 
 // Grid of whole XCD groups: one block per tile, kGroupTiles per XCD round; blocks past the
@@ -598,4 +678,37 @@ hipError_t gsr_launch_blend_surface(const GsrBlendArgs &a, const GsrDepthArgs &d
     const uint32_t n_tiles = a.grid_x * a.rows_tiles;
     if (d.depth_map || d.inv_depth_map) return launch_surface<true>(a, d, m, n_tiles, s);
     return launch_surface<false>(a, d, m, n_tiles, s);
+}
+
+// The chunk widths of a feature launch: the rest of the channels in the narrowest of 4, 8, 16 that
+// holds it, else 16.
+static int feature_chunk(int rest) { return rest > 8 ? 16 : rest > 4 ? 8 : 4; }
+
+hipError_t gsr_launch_blend_features(const GsrBlendArgs &a, const float *features, int C,
+                                     float *feature_map, hipStream_t s) {
+    if (!features || !feature_map || C < 1) return hipErrorInvalidValue;
+    if (a.rows_tiles == 0 || a.grid_x == 0) return hipSuccess;
+    const uint32_t n_tiles = a.grid_x * a.rows_tiles;
+    const dim3 grid(xcd_grid(n_tiles));
+    GsrFeatureArgs ft{features, feature_map, C, 0,
+                      (reinterpret_cast<uintptr_t>(features) & 15) == 0 && C % 4 == 0};
+    for (; ft.c0 < C;) {
+        const int w = feature_chunk(C - ft.c0);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a, n_tiles, ft);
+        };
+        if (a.fast) {
+            if (w == 16) launch(k_blend_features_q<true, 16>);
+            else if (w == 8) launch(k_blend_features_q<true, 8>);
+            else launch(k_blend_features_q<true, 4>);
+        } else {
+            if (w == 16) launch(k_blend_features_q<false, 16>);
+            else if (w == 8) launch(k_blend_features_q<false, 8>);
+            else launch(k_blend_features_q<false, 4>);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        ft.c0 += w;
+    }
+    return hipSuccess;
 }

@@ -600,6 +600,21 @@ struct GsrSurfaceArgs {
 };
 hipError_t gsr_launch_blend_surface(const GsrBlendArgs &a, const GsrDepthArgs &d,
                                     const GsrSurfaceArgs &m, hipStream_t s);
+// gsr_forward_features' planes (blend.hip k_blend_features_q): launches of their own over the
+// lists of `a`, after its blend: per chunk of 16, 8 or 4 channels (the last one padded inside the
+// kernel) the composite of gsr_launch_blend with the Gaussians' feature words in the colours'
+// place, under the colour's weights in a.fast's arithmetic.  features: [P, C] floats at any 4-byte
+// aligned address (float4 gathers where the rows are 16-B aligned, scalar ones otherwise);
+// feature_map: [C, rows_out, W], strip-local like out_color.  Of `a` the colour, final_T,
+// n_contrib and bg members are not read.  No word beyond C is read or written.
+struct GsrFeatureArgs {
+    const float *features;
+    float *feature_map;
+    int C, c0;  // the row length; the launch's first channel
+    int vec4;   // set by the launcher: 16-B aligned rows
+};
+hipError_t gsr_launch_blend_features(const GsrBlendArgs &a, const float *features, int C,
+                                     float *feature_map, hipStream_t s);
 // The GL backend's geometry shadings in place of the composite (blend.hip k_shade_q): shading =
 // GSR_SHADE_BILLBOARD / FLAT_BALL / GAUSS_BALL.  Same arguments; a.fast is not read.
 hipError_t gsr_launch_shade(const GsrBlendArgs &a, int shading, hipStream_t s);
@@ -650,6 +665,16 @@ struct GsrPlaneBwdArgs {
 };
 hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
                                        hipStream_t s, const GsrStripBwdArgs *strip = nullptr);
+// gsr_backward_features (k_blend_bwd_features_q): launches of their own beside the colour / planes
+// blend-backward, per chunk of 16, 8 or 4 channels (the forward's rule), over the same lists.
+// A launch carries the recursion for its own channels (the start value is 0: no background), adds
+// its share of the words 0..5 of a.grad2d (dL/dalpha is linear in the channel set) and the chunk's
+// sums gF_c w_i straight into dL_dfeatures[id * C + c] (zeroed by the caller; NULL: not wanted).
+// Of `a`, dL_dcolor and bg are not read.  dL_dfeature_map: [C, rows, W], strip-local under `strip`
+// like a.dL_dcolor.  No word beyond C is read or written.
+hipError_t gsr_launch_blend_bwd_features(const GsrBlendBwdArgs &a, const float *features, int C,
+                                         const float *dL_dfeature_map, float *dL_dfeatures,
+                                         hipStream_t s, const GsrStripBwdArgs *strip = nullptr);
 // gsr_backward_ordered, deterministic (k_blend_bwd_det_q, k_blend_bwd_planes_det_q; DESIGN.md
 // 3k): no sum is added to a.grad2d.  In upstream's (untight) lists a Gaussian is listed in exactly
 // the tiles of its rect, so every (Gaussian, tile, quadrant) owns a slot,

@@ -53,6 +53,18 @@
 //     either mode.  The image and plane gradients are strip-local, [3, rows, W] and [rows, W], and
 //     image_height gives the frame's height, which they no longer tell; the gradients stay
 //     whole-scene.  (An entry of its own: rasterize_gaussians_backward_ext keeps its signature.)
+//   _C.rasterize_gaussians_features(<rasterize_gaussians' 19 arguments>, planes, antialiasing,
+//                                   tile_row_begin, tile_row_end, features)
+//       -> rasterize_gaussians_ext's 6-tuple, then feature_map [C, rows, W]
+//     this package's own: gsr_forward_features, the splat composite with C channels of the
+//     caller's own per Gaussian (features [P, C], 1 <= C <= GSR_MAX_FEATURES) composited under the
+//     colour's weights.  (An entry of its own: the entries above keep their signatures.)
+//   _C.rasterize_gaussians_backward_features(<rasterize_gaussians_backward_ext's 23 arguments>,
+//                                            tile_row_begin, tile_row_end, image_height, features,
+//                                            dL_dfeature_map)
+//       -> the 11-tuple, then dL_dfeatures [P, C]
+//     this package's own: gsr_backward_features; tile rows (0, 0) for a whole frame (image_height
+//     is then not read); dL_dout_color may be empty.  `deterministic` is refused by the library.
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
 #include <torch/extension.h>
@@ -174,8 +186,21 @@ int64_t strip_rows(int64_t H, int64_t rb, int64_t re) {
     return std::min(H, 16 * re) - 16 * rb;
 }
 
+// features [P, C] as the library reads it (contiguous float32 on the scene's device); checks the
+// shape and C
+torch::Tensor feature_rows(const torch::Tensor &features, const Scene &sc) {
+    TORCH_CHECK(features.defined() && features.dim() == 2 && features.size(0) == sc.P,
+                "features must have dimensions (num_points, C) = (", sc.P, ", C)");
+    TORCH_CHECK(features.size(1) >= 1 && features.size(1) <= GSR_MAX_FEATURES, "features: C = ",
+                features.size(1), " outside 1..", GSR_MAX_FEATURES);
+    return features.to(sc.dev, torch::kFloat32).contiguous();
+}
+
+// features / feature_map: gsr_forward_features' (both NULL: none); feature_map is allocated here.
 Forward6 forward_impl(const Inputs &in, int64_t frame_H, int64_t W, int64_t shading, bool planes,
-                      bool antialiasing, int64_t tile_row_begin = 0, int64_t tile_row_end = 0) {
+                      bool antialiasing, int64_t tile_row_begin = 0, int64_t tile_row_end = 0,
+                      const torch::Tensor *features = nullptr,
+                      torch::Tensor *feature_map = nullptr) {
     Scene sc(in);
     // (the outputs are strip-local: H rows from here on)
     const int64_t H = strip_rows(frame_H, tile_row_begin, tile_row_end);
@@ -196,11 +221,21 @@ Forward6 forward_impl(const Inputs &in, int64_t frame_H, int64_t W, int64_t shad
         inv_depth_map = P ? torch::empty({H, W}, f32) : torch::zeros({H, W}, f32);
         final_T = P ? torch::empty({H, W}, f32) : torch::ones({H, W}, f32);
     }
+    torch::Tensor rows_f;
+    if (features) {  // (a pixel that composites nothing: 0)
+        rows_f = feature_rows(*features, sc);
+        *feature_map = P ? torch::empty({rows_f.size(1), H, W}, f32)
+                         : torch::zeros({rows_f.size(1), H, W}, f32);
+    }
     int64_t num_rendered = 0;
     if (P != 0) {
         sc.fill(frame_H, W);
         sc.st.tile_row_begin = (int32_t)tile_row_begin;
         sc.st.tile_row_end = (int32_t)tile_row_end;
+        gsr_feature_outputs fo{};
+        if (features)
+            fo = {(int32_t)rows_f.size(1), rows_f.data_ptr<float>(),
+                  feature_map->data_ptr<float>()};
         gsr_outputs out{};
         out.color = color.data_ptr<float>();
         out.radii = radii.data_ptr<int32_t>();
@@ -216,7 +251,10 @@ Forward6 forward_impl(const Inputs &in, int64_t frame_H, int64_t W, int64_t shad
         int rc;
         {  // the forward waits for K (pinned memory): other Python threads may run meanwhile
             pybind11::gil_scoped_release no_gil;
-            rc = planes || antialiasing
+            rc = features
+                     ? gsr_forward_features(ctx, &sc.g, &sc.st, &out, planes ? &d : nullptr,
+                                            nullptr, antialiasing ? &fs : nullptr, &fo, s)
+                 : planes || antialiasing
                      ? gsr_forward_filtered(ctx, &sc.g, &sc.st, &out, planes ? &d : nullptr,
                                             nullptr, antialiasing ? &fs : nullptr, s)
                      : gsr_forward_shaded(ctx, &sc.g, &sc.st, &out, (int32_t)shading, s);
@@ -240,6 +278,24 @@ Forward6 rasterize_gaussians_ext(
                          campos, prefiltered, debug},
                         image_height, image_width, shading, planes, antialiasing, tile_row_begin,
                         tile_row_end);
+}
+
+using Forward7 = decltype(std::tuple_cat(Forward6(), std::tuple<torch::Tensor>()));
+Forward7 rasterize_gaussians_features(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
+    int64_t image_width, const torch::Tensor &sh, int64_t degree, const torch::Tensor &campos,
+    bool prefiltered, bool debug, bool planes, bool antialiasing, int64_t tile_row_begin,
+    int64_t tile_row_end, const torch::Tensor &features) {
+    torch::Tensor feature_map;
+    Forward6 r = forward_impl({background, means3D, colors, opacity, scales, rotations,
+                               scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                               tan_fovy, sh, degree, campos, prefiltered, debug},
+                              image_height, image_width, GSR_SHADE_SPLAT, planes, antialiasing,
+                              tile_row_begin, tile_row_end, &features, &feature_map);
+    return std::tuple_cat(r, std::make_tuple(feature_map));
 }
 
 // ... with upstream's three buffers in the planes' place.  They hold upstream's backward state;
@@ -283,7 +339,9 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
                          const torch::Tensor (&planes)[3], bool camera, bool antialiasing,
                          bool upstream = false, bool deterministic = false,
                          int64_t tile_row_begin = 0, int64_t tile_row_end = 0,
-                         int64_t image_height = 0) {
+                         int64_t image_height = 0, const torch::Tensor *features = nullptr,
+                         const torch::Tensor *dL_dfeature_map = nullptr,
+                         torch::Tensor *dL_dfeatures = nullptr) {
     Scene sc(in);
     const bool strip = tile_row_begin != 0 || tile_row_end != 0;
     const bool has_color = dL_dout_color.defined() && dL_dout_color.numel() != 0;
@@ -302,7 +360,19 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
                     "the image and plane gradients must share (H, W)");
         any = true;
     }
-    TORCH_CHECK(any || has_color || upstream, "dL_dout_color or a plane gradient is required");
+    torch::Tensor rows_f;
+    if (features) {  // gsr_backward_features: the feature planes' gradient, [C, H, W]
+        rows_f = feature_rows(*features, sc);
+        const torch::Tensor &t = *dL_dfeature_map;
+        TORCH_CHECK(t.defined() && t.dim() == 3 && t.size(0) == rows_f.size(1),
+                    "dL_dfeature_map must have dimensions (C, H, W) = (", rows_f.size(1),
+                    ", H, W)");
+        if (!has_color && !any) H = t.size(1), W = t.size(2);
+        TORCH_CHECK(t.size(1) == H && t.size(2) == W,
+                    "the image, plane and feature gradients must share (H, W)");
+    }
+    TORCH_CHECK(any || has_color || upstream || features,
+                "dL_dout_color or a plane gradient is required");
     // a strip: H so far is the strip's rows, which must be those of the frame's strip
     const int64_t frame_H = strip ? image_height : H;
     TORCH_CHECK(strip_rows(frame_H, tile_row_begin, tile_row_end) == H,
@@ -320,11 +390,18 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         d_view = torch::zeros({4, 4}, f32), d_proj = torch::zeros({4, 4}, f32);
         d_campos = torch::zeros({3}, f32);
     }
+    if (features) *dL_dfeatures = torch::zeros({P, rows_f.size(1)}, f32);
     if (P != 0) {
         sc.fill(frame_H, W);
         sc.st.tile_row_begin = (int32_t)tile_row_begin;
         sc.st.tile_row_end = (int32_t)tile_row_end;
         std::vector<torch::Tensor> &keep = sc.keep;
+        gsr_feature_gradients fg{};
+        if (features)
+            fg = {(int32_t)rows_f.size(1), rows_f.data_ptr<float>(),
+                  opt_ptr(*dL_dfeature_map, sc.dev, "dL_dfeature_map", keep,
+                          rows_f.size(1) * H * W),
+                  dL_dfeatures->data_ptr<float>()};
         gsr_backward_inputs bi{};
         bi.dL_dcolor = opt_ptr(dL_dout_color, sc.dev, "dL_dout_color", keep, 3 * H * W);
         gsr_plane_gradients pg{};
@@ -353,7 +430,11 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         int rc;
         {  // the rebuild waits for K (pinned memory), as the forward does
             pybind11::gil_scoped_release no_gil;
-            if (upstream)
+            if (features)  // gsr_backward_features: a strip or a frame; refuses deterministic
+                rc = gsr_backward_features(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
+                                           camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
+                                           &order, &fg, &gr, s);
+            else if (upstream)
                 rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
             else if (strip)  // gsr_backward_strip: the strip's loss, in either mode
                 rc = gsr_backward_strip(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
@@ -430,6 +511,29 @@ Backward11 rasterize_gaussians_backward_strip_ext(
                           sh, degree, campos, false, debug},
                          dL_dout_color, planes, camera, antialiasing, false, deterministic,
                          tile_row_begin, tile_row_end, image_height);
+}
+
+// ... with feature channels: tile rows (0, 0) for a whole frame.
+using Backward12 = decltype(std::tuple_cat(Backward11(), std::tuple<torch::Tensor>()));
+Backward12 rasterize_gaussians_backward_features(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T, bool camera, bool antialiasing, bool deterministic,
+    int64_t tile_row_begin, int64_t tile_row_end, int64_t image_height,
+    const torch::Tensor &features, const torch::Tensor &dL_dfeature_map) {
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    torch::Tensor dL_dfeatures;
+    Backward11 g = backward_impl({background, means3D, colors, opacities, scales, rotations,
+                                  scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                                  tan_fovy, sh, degree, campos, false, debug},
+                                 dL_dout_color, planes, camera, antialiasing, false, deterministic,
+                                 tile_row_begin, tile_row_end, image_height, &features,
+                                 &dL_dfeature_map, &dL_dfeatures);
+    return std::tuple_cat(g, std::make_tuple(dL_dfeatures));
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -509,6 +613,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "rasterize_gaussians_backward_ext's 23 arguments, then tile_row_begin, tile_row_end, "
           "image_height: gsr_backward_strip, the backward on a strip of tile rows of a frame "
           "image_height px high (strip-local image and plane gradients) -> the same 11-tuple");
+    m.def("rasterize_gaussians_features", &rasterize_gaussians_features,
+          "rasterize_gaussians' 19 arguments, then planes, antialiasing, tile_row_begin, "
+          "tile_row_end, features (P, C): gsr_forward_features -> rasterize_gaussians_ext's "
+          "6-tuple, then feature_map (C, rows, W)");
+    m.def("rasterize_gaussians_backward_features", &rasterize_gaussians_backward_features,
+          "rasterize_gaussians_backward_ext's 23 arguments, then tile_row_begin, tile_row_end, "
+          "image_height, features (P, C), dL_dfeature_map (C, rows, W): gsr_backward_features -> "
+          "the 11-tuple, then dL_dfeatures (P, C)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(

@@ -191,12 +191,30 @@ def _scene_structs(bg, means3D, colors_precomp, opacities, scales, rotations, sc
                                          colors_precomp, sh, bg, viewmatrix, projmatrix, campos)
 
 
+def _feature_rows(features, P, device):
+    """`features` as the library reads it: float32 (P, C) on `device` with contiguous rows of C --
+    the tensor itself when it already is (a view at an odd offset included), else a copy.
+    RuntimeError for another shape or a C outside 1..256."""
+    if not isinstance(features, torch.Tensor) or features.ndimension() != 2 or \
+            int(features.size(0)) != P:
+        raise RuntimeError(f"features must have dimensions (num_points, C) = ({P}, C)")
+    C = int(features.size(1))
+    if not 1 <= C <= _lib.MAX_FEATURES:
+        raise RuntimeError(f"features: C = {C} outside 1..{_lib.MAX_FEATURES}")
+    if features.device != device:
+        features = features.to(device)
+    if features.dtype != torch.float32:
+        features = features.float()
+    return features.detach().contiguous()
+
+
 class ForwardResult(NamedTuple):
     """Everything one native forward produced (color/radii plus optional intermediates)."""
     num_rendered: int
     color: torch.Tensor
     radii: torch.Tensor
     extras: dict
+    feature_map: torch.Tensor | None = None  # (C, rows, W) with `features`, else None
 
 
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations,
@@ -204,7 +222,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                                tanfovy, image_height, image_width, sh, degree, campos, prefiltered,
                                debug, *, tile_rows=None, extras=(), stream=None, slot=0,
                                out_color=None, radii=True, shading=0,
-                               antialiasing=False) -> ForwardResult:
+                               antialiasing=False, features=None) -> ForwardResult:
     """Same arguments, order and validation as upstream `_C.rasterize_gaussians`.
 
     Extensions (keyword-only, for the strip partition and the parity tests):
@@ -231,9 +249,21 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                    place of the opacity (gsr_forward_filtered in include/gsr.h; the extra
                    conic_opacity[:, 3] is then that opacity).  Splat composite only: RuntimeError
                    with a shading.  False is the call without the argument.
+      features  -- (P, C) float32, 1 <= C <= 256: C channels of the caller's own per Gaussian.
+                   ForwardResult.feature_map is then (C, rows, W): each plane the sum of the
+                   channel under the colour's weights, no background term (gsr_forward_features in
+                   include/gsr.h: bit for bit a colour channel of a colors_precomp forward with
+                   bg = 0).  A view whose rows are contiguous and whose storage is a (P, C) block
+                   is read in place, whatever its alignment.  Splat composite only: RuntimeError
+                   with a shading.  None is the call without the argument.
     """
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if features is not None:
+        if shading != _lib.GSR_SHADE_SPLAT:
+            raise RuntimeError("features are composited by the splat composite: not available "
+                               f"with shading {shading}")
+        features = _feature_rows(features, int(means3D.size(0)), means3D.device)
     if not radii and (tile_rows is None or any(
             n in extras for n in ("depths", "means2D", "conic_opacity", "rgb", "tiles_touched"))):
         raise RuntimeError("radii=False needs tile_rows and no per-Gaussian extras")
@@ -290,6 +320,9 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
         else:
             raise ValueError(f"unknown extra output {name!r}")
 
+    feature_map = None
+    if features is not None:
+        feature_map = torch.zeros((features.size(1), rows, W), **f32)
     st.tile_row_begin, st.tile_row_end = rb, re
     out = _lib.GsrOutputs(color=color.data_ptr(),
                           radii=radii.data_ptr() if P and radii is not None else None)
@@ -305,6 +338,17 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
         if shading != _lib.GSR_SHADE_SPLAT:
             _lib.check(lib.gsr_forward_shaded(*head, int(shading), ctypes.c_void_p(stream)),
                        "gsr_forward_shaded")
+        elif features is not None:  # NULL for each struct the call does without
+            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
+            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
+            feat = _lib.GsrFeatureOutputs(C=int(features.size(1)), features=_lib.ptr(features),
+                                          feature_map=feature_map.data_ptr())
+            _lib.check(_lib.features_fns(lib)[0](
+                *head, ctypes.byref(planes) if depth_planes else None,
+                ctypes.byref(surface) if surface_planes else None,
+                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
+                if antialiasing else None,
+                ctypes.byref(feat), ctypes.c_void_p(stream)), "gsr_forward_features")
         elif not (depth_planes or surface_planes or antialiasing):
             _lib.check(lib.gsr_forward(*head, ctypes.c_void_p(stream)), "gsr_forward")
         else:  # NULL for each struct the call does without
@@ -316,7 +360,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                 ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
                 if antialiasing else None,
                 ctypes.c_void_p(stream)), "gsr_forward_filtered")
-    return ForwardResult(int(out.num_rendered), color, radii, ext)
+    return ForwardResult(int(out.num_rendered), color, radii, ext, feature_map)
 
 
 def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, scales, rotations,
@@ -326,7 +370,8 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         dL_ddepth_map=None, dL_dinv_depth_map=None,
                                         dL_dfinal_T=None, depths=False, camera=False,
                                         antialiasing=False, deterministic=False,
-                                        tile_rows=None, image_height=None) -> dict:
+                                        tile_rows=None, image_height=None, features=None,
+                                        dL_dfeature_map=None) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -353,9 +398,21 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     tile_rows=(b, e), with image_height (required then: the strip does not tell the frame's
     height): the call is `gsr_backward_strip` -- the backward of the strip's loss.  dL_dout_color is
     strip-local, (3, rows, W) with rows = min(H, 16 e) - 16 b, the plane gradients (rows, W); the
-    gradients are whole-scene, exact zeros for Gaussians without a tile in the strip."""
+    gradients are whole-scene, exact zeros for Gaussians without a tile in the strip.
+
+    features (P, C) with dL_dfeature_map (C, rows, W): the call is `gsr_backward_features` -- the
+    feature planes' gradient joins the others (dL_dout_color may then be None) and the result also
+    holds dL_dfeatures (P, C), exact zeros for culled Gaussians.  With deterministic=True the
+    library refuses the call (RuntimeError): the deterministic slots have no room for C more sums."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if (features is None) != (dL_dfeature_map is None):
+        raise RuntimeError("features and dL_dfeature_map belong together")
+    if features is not None:
+        features = _feature_rows(features, int(means3D.size(0)), means3D.device)
+        if dL_dfeature_map.ndimension() != 3 or int(dL_dfeature_map.size(0)) != features.size(1):
+            raise RuntimeError("dL_dfeature_map must have dimensions (C, H, W) = "
+                               f"({features.size(1)}, H, W)")
     if tile_rows is not None and image_height is None:
         raise RuntimeError("tile_rows needs image_height: the frame's height, not the strip's")
     if tile_rows is None and image_height is not None:
@@ -364,7 +421,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     plane_grads = {"dL_ddepth_map": dL_ddepth_map, "dL_dinv_depth_map": dL_dinv_depth_map,
                    "dL_dfinal_T": dL_dfinal_T}
     plane_grads = {n: t for n, t in plane_grads.items() if t is not None}
-    if dL_dout_color is None and not plane_grads:
+    if dL_dout_color is None and not plane_grads and features is None:
         raise RuntimeError("dL_dout_color or a plane gradient is required")
     if dL_dout_color is not None and (dL_dout_color.ndimension() != 3 or
                                       dL_dout_color.size(0) != 3):
@@ -372,7 +429,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     if dL_dout_color is not None:
         H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     else:
-        first = next(iter(plane_grads.values()))
+        first = next(iter(plane_grads.values())) if plane_grads else dL_dfeature_map
         H, W = int(first.size(-2)), int(first.size(-1))
     rb = re = 0
     if tile_rows is not None:  # H so far: the strip's rows
@@ -386,6 +443,9 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     for n, t in plane_grads.items():
         if t.ndimension() != 2 or tuple(t.shape) != (rows, W):
             raise RuntimeError(f"{n} must have dimensions (H, W) = ({rows}, {W})")
+    if features is not None and tuple(dL_dfeature_map.shape[1:]) != (rows, W):
+        raise RuntimeError(f"dL_dfeature_map must have dimensions (C, H, W) = "
+                           f"({features.size(1)}, {rows}, {W})")
     device, dev_index, P, g, st, held = _scene_structs(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,
         viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, False, debug)
@@ -416,8 +476,13 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
+    d_feat = None
+    if features is not None:
+        d_feat = torch.zeros((P, features.size(1)), **f32)
+        d_map = _as_dev(dL_dfeature_map, device, "C,H,W")
     with torch.cuda.device(dev_index):
-        if not (plane_grads or depths or camera or antialiasing or deterministic or re):
+        if not (plane_grads or depths or camera or antialiasing or deterministic or re or
+                features is not None):
             _lib.check(_lib.backward_fn(lib)(*head, ctypes.byref(out), ctypes.c_void_p(stream)),
                        "gsr_backward")
         else:  # NULL for each struct the call does without
@@ -428,7 +493,16 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                        ctypes.byref(cg) if camera else None,
                        ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
                        if antialiasing else None)
-            if re:
+            if features is not None:
+                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
+                feat = _lib.GsrFeatureGradients(
+                    C=int(features.size(1)), features=_lib.ptr(features),
+                    dL_dfeature_map=_lib.ptr(d_map), dL_dfeatures=_lib.ptr(d_feat))
+                _lib.check(_lib.features_fns(lib)[1](
+                    *head, *structs, ctypes.byref(order), ctypes.byref(feat), ctypes.byref(out),
+                    ctypes.c_void_p(stream)), "gsr_backward_features")
+                grads["dL_dfeatures"] = d_feat
+            elif re:
                 order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
                 _lib.check(_lib.backward_strip_fn(lib)(
                     *head, *structs, ctypes.byref(order), ctypes.byref(out),
@@ -447,13 +521,19 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                        cov3Ds_precomp, raster_settings: GaussianRasterizationSettings):
+                        cov3Ds_precomp, raster_settings: GaussianRasterizationSettings,
+                        features=None):
     """upstream rasterize_gaussians(...) -> (color, radii), through _RasterizeGaussians; with
     raster_settings.depth_maps -> (color, radii, depth_map, inv_depth_map, final_T), through
     _RasterizeGaussiansPlanes.  When viewmatrix, projmatrix or campos of the settings requires a
     gradient (and gradients are recorded), through _RasterizeGaussiansCamera, which returns the
-    same outputs and also differentiates with respect to the three."""
+    same outputs and also differentiates with respect to the three.  With `features` (P, C), through
+    _RasterizeGaussiansFeatures: the same outputs followed by feature_map (C, rows, W)."""
     rs = raster_settings
+    if features is not None:
+        return _RasterizeGaussiansFeatures.apply(means3D, means2D, sh, colors_precomp, opacities,
+                                                 scales, rotations, cov3Ds_precomp, rs, features,
+                                                 rs.viewmatrix, rs.projmatrix, rs.campos)
     if torch.is_grad_enabled() and any(
             isinstance(t, torch.Tensor) and t.requires_grad
             for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
@@ -735,6 +815,125 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 like(g[10], campos) if need[11] else None)
 
 
+def _forward_features(args, rs, planes: bool, features):
+    """`_forward` with feature channels -> (num_rendered, color, radii, planes, feature_map);
+    through `_C.rasterize_gaussians_features`, under GSR_LIB by ctypes."""
+    strip = getattr(rs, "tile_rows", None)
+    if not _lib._native_shares_library():
+        res = rasterize_gaussians_native(*args, extras=PLANE_NAMES if planes else (),
+                                         antialiasing=rs.antialiasing, tile_rows=strip,
+                                         features=features)
+        return (res.num_rendered, res.color, res.radii,
+                tuple(res.extras[n] for n in PLANE_NAMES) if planes else (), res.feature_map)
+    from . import _C
+    if strip:
+        _strip_rows(strip, int(rs.image_height))
+    num_rendered, color, radii, *maps, feature_map = _C.rasterize_gaussians_features(
+        *args, planes, bool(rs.antialiasing), *(strip or (0, 0)), features)
+    return num_rendered, color, radii, tuple(maps) if planes else (), feature_map
+
+
+def _backward_features(rs, saved, grads, features, grad_feature_map, camera):
+    """`_backward` with feature channels: `_GRADIENT_ORDER`'s eleven, then dL_dfeatures.  The
+    deterministic mode has no feature sums (gsr_backward_features refuses it): the setting raises;
+    torch's global switch raises too, or with warn_only warns and runs the atomic sums."""
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
+    what = ("the deterministic backward has no feature channels: its slots hold 9 or 10 sums per "
+            "(Gaussian, tile, quadrant) and have no room for C more")
+    if getattr(rs, "deterministic", None):
+        raise RuntimeError(f"GaussianRasterizationSettings(deterministic=True) with features: {what}")
+    if getattr(rs, "deterministic", None) is None and torch.are_deterministic_algorithms_enabled():
+        if not torch.is_deterministic_algorithms_warn_only_enabled():
+            raise RuntimeError(f"torch.use_deterministic_algorithms(True) with features: {what} "
+                               "(deterministic=False in the settings runs the atomic sums)")
+        import warnings
+        warnings.warn(f"gaussiansplattingviewer_amd: {what}; the sums over pixels are float "
+                      "atomics in this backward", UserWarning, stacklevel=2)
+    strip = getattr(rs, "tile_rows", None)
+    viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if grad_feature_map is None:  # the loss does not read the feature planes
+        g = _backward(rs._replace(deterministic=False), saved, grads, camera)
+        return (*g, torch.zeros_like(features))
+    if not _lib._native_shares_library():
+        g = rasterize_gaussians_backward_native(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
+            cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree,
+            campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
+            dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
+            tile_rows=strip, image_height=None if strip is None else rs.image_height,
+            features=features, dL_dfeature_map=grad_feature_map)
+        return tuple(g.get(n) for n in _GRADIENT_ORDER) + (g["dL_dfeatures"],)
+    from . import _C
+    e = torch.empty(0)
+    if camera is not None:
+        viewmatrix, projmatrix, campos = (_as_dev(t.detach(), means3D.device, "")
+                                          for t in camera)
+    g = _C.rasterize_gaussians_backward_features(
+        rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
+        viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
+        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing), False,
+        *(strip or (0, 0)), int(rs.image_height), features, grad_feature_map)
+    return g if camera is not None else g[:8] + (None,) * 3 + g[11:]
+
+
+class _RasterizeGaussiansFeatures(torch.autograd.Function):
+    """The three Functions above in one, with `features` (P, C) composited beside the colour
+    (`gsr_forward_features`): returns the outputs of the call without features -- (color, radii),
+    with depth_maps (color, radii, depth_map, inv_depth_map, final_T) -- followed by feature_map
+    (C, rows, W).  Everything but radii is differentiable through one `gsr_backward_features` call,
+    with respect to features and everything the colour reaches; viewmatrix, projmatrix and campos
+    travel as tensor arguments and get their gradients when they require them.  An unused output's
+    gradient travels as NULL."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                cov3Ds_precomp, raster_settings, features, viewmatrix, projmatrix, campos):
+        rs = raster_settings
+        if rs.shading != _lib.GSR_SHADE_SPLAT:
+            raise RuntimeError("features are composited by the splat composite: not available "
+                               f"with shading {rs.shading}")
+        ctx.has_means2D = isinstance(means2D, torch.Tensor)
+        ctx.raster_settings = rs
+        ctx.set_materialize_grads(False)
+        args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
+                     cov3Ds_precomp)
+        rows = _feature_rows(features, int(means3D.size(0)), means3D.device)
+        _, color, radii, planes, feature_map = _forward_features(args, rs, bool(rs.depth_maps),
+                                                                 rows)
+        # (a camera given as plain numbers has no gradient and is read from the settings)
+        ctx.save_for_backward(*_saved(args), rows, *(
+            t if isinstance(t, torch.Tensor) else None for t in (viewmatrix, projmatrix, campos)))
+        ctx.features_like = (features.dtype, features.device)
+        ctx.mark_non_differentiable(radii)
+        return (color, radii, *planes, feature_map)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, *more):
+        """Gradients in input order: the nine of `_input_grads`, features', then viewmatrix's,
+        projmatrix's and campos's."""
+        del grad_radii
+        rs = ctx.raster_settings
+        *saved, rows, viewmatrix, projmatrix, campos = ctx.saved_tensors
+        grad_planes = more[:-1] if rs.depth_maps else (None, None, None)
+        grads = _contiguous((grad_color, *grad_planes))
+        grad_map = None if more[-1] is None else more[-1].contiguous()
+        if all(t is None for t in grads) and grad_map is None:
+            return (None,) * 13
+        need = ctx.needs_input_grad
+        with_camera = any(need[10:13])
+        if viewmatrix is None or projmatrix is None or campos is None:
+            viewmatrix, projmatrix, campos = rs.viewmatrix, rs.projmatrix, rs.campos
+        g = _backward_features(rs, saved, grads, rows, grad_map,
+                               (viewmatrix, projmatrix, campos) if with_camera else None)
+        like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731
+        features = ctx.features_like
+        return (*_input_grads(ctx.has_means2D, saved, g)[:8], None,
+                g[11].to(dtype=features[0], device=features[1]) if need[9] else None,
+                like(g[8], viewmatrix) if need[10] else None,
+                like(g[9], projmatrix) if need[11] else None,
+                like(g[10], campos) if need[12] else None)
+
+
 class GaussianRasterizer(torch.nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -749,7 +948,13 @@ class GaussianRasterizer(torch.nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                rotations=None, cov3D_precomp=None):
+                rotations=None, cov3D_precomp=None, features=None):
+        """upstream's forward; features (not upstream's; (P, C) float32, 1 <= C <= 256): the call
+        returns its usual outputs followed by feature_map (C, rows, W), the channels composited
+        under the colour's weights without a background term (gsr_forward_features in
+        include/gsr.h), differentiable with respect to features and everything the colour
+        reaches.  Composes with depth_maps, camera gradients, antialiasing and tile_rows; not
+        with a shading, nor with the deterministic backward (RuntimeError at backward)."""
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -757,6 +962,9 @@ class GaussianRasterizer(torch.nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or '
                             'precomputed 3D covariance!')
+        if features is not None:
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales,
+                                       rotations, cov3D_precomp, rs, features=features)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales,
                                    rotations, cov3D_precomp, rs)
 

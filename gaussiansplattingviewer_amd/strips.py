@@ -242,7 +242,9 @@ def reduce_gradients(tensors, group=None) -> None:
     """Sum the given tensors over the ranks, in place (one all_reduce each): the strips' gradients
     of `GaussianRasterizationSettings(tile_rows=)` add up to the whole frame's, so after the call
     every rank holds the whole frame's gradients.  `tensors`: an iterable of tensors, e.g. the
-    leaves' `.grad`; None entries are skipped.  A no-op at world 1.  With a backend that moves
+    leaves' `.grad` -- that of a `features` tensor included (dL_dfeatures is whole-scene like the
+    others, zeros for Gaussians outside the strip); None entries are skipped.  A no-op at world 1.
+    With a backend that moves
     device tensors from host threads (gloo; not RCCL) the current stream of every device tensor's
     device is synchronised first, as StripGather does, so the backward that wrote them is done.
     A two-term float sum is commutative: with two ranks every rank's result has the bits of the

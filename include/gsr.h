@@ -490,6 +490,82 @@ int gsr_backward_strip(gsr_context *ctx, const gsr_gaussians *g, const gsr_raste
                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                        const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                        const gsr_backward_order *order, gsr_gradients *grads, void *stream);
+/* gsr_forward_filtered and gsr_backward_strip with C channels of the caller's own per Gaussian: a
+ * semantic or language embedding, normals, a soft label field, any learned C-vector.  (Additive to
+ * ABI 4; no existing struct, entry point or kernel changes.)
+ * Forward.  features is [P, C] float32, row-major; feature_map is [C, rows, W] float32, strip-local
+ * like color:
+ *   feature_map[c, y, x] = sum_k features[id_k, c] * w_k
+ * over exactly the splats the colour composites at that pixel (the list order, the power > 0 and
+ * alpha < 1/255 skips, the 0.99 cap and the T < 1e-4 termination are the colour's), with w_k the
+ * very weight of the colour channels in the context's arithmetic (GSR_OPT_BLEND_FAST 0 or 1), as
+ * gsr_forward_depth defines it.  There is no background term, as for the depth planes: a pixel that
+ * composites nothing is 0, and normalising by 1 - final_T is the caller's business.
+ * Twin property (tests/test_gpu_feature_maps.py): plane c is, bit for bit, a colour channel of a
+ * gsr_forward of the same scene with colors_precomp[:, j] = features[:, c] and bg = 0 -- in both
+ * arithmetic modes, on strips, with tight or upstream lists, with and without n_contrib, with frame
+ * graphs, with the blend cull on or off, and under antialiasing against the antialiased twin.
+ * colors_precomp is copied unclamped by the preprocess, so negative features obey the twin too.
+ * Everything else the call returns is the bits of the same call without features: the image, radii,
+ * every gsr_outputs member, the depth and median planes, num_rendered and the lists gsr_get_binning
+ * exports.  Rows of Gaussians that are on no list (culled, or outside the strip) are never read:
+ * NaN in such rows reaches no output.  P == 0 and empty lists give all-zero planes.
+ * The feature channels run as launches of their own over the lists the call has built, after the
+ * colour blend, in chunks of 16, 8 or 4 channels (the last one padded inside the kernel: no word at
+ * or beyond C is read or written); they are timed inside the "blend" stage.  Frame graphs: the
+ * launches come directly after the recorded chains with the call's pointers, nothing of a feature
+ * is recorded, and a frame whose list outgrew the capacity writes no plane before it is rendered
+ * again.  features rows may sit at any 4-byte-aligned address and C need not be a multiple of 4:
+ * the rows are gathered as float4 where they are 16-byte aligned (the pointer, and C % 4 == 0) and
+ * word by word otherwise, with the same bits.
+ * A NULL feat, or one with feature_map NULL, is gsr_forward_filtered itself: the same kernels, the
+ * same arguments.  Refused with GSR_E_INVALID and nothing written: C < 1 or C > GSR_MAX_FEATURES,
+ * features NULL with a map given (P > 0).  The splat composite only: the GL shadings have no
+ * features (the entry takes no shading).
+ *
+ * Backward.  dL_dfeature_map is [C, rows, W], strip-local.  With gF the pixel's C feature
+ * gradients, f_i splat i's feature row, and every gate held constant as in gsr_backward:
+ *   - dL_dfeatures[id_i, c] += gF_c w_i: final, there is no per-Gaussian stage behind it;
+ *   - the per-splat term of the recursion gains gF . f_i:
+ *     gc_i = g . c_i + gd z_i + gi / z_i + gF . f_i;
+ *   - the carried value's start gains nothing: the features' background is 0;
+ *   - dL/dalpha_i = T_i (gc_i - r_i) then feeds dL_dmeans2D, dL_dconic, dL_dopacity and everything
+ *     behind them, the camera's sums and the antialiasing term included, unchanged;
+ *   - dL_dcolors gets nothing from features;
+ *   - culled Gaussians (and, on a strip, Gaussians without a tile in it) get exact zeros in
+ *     dL_dfeatures: the buffer is zeroed and then filled, never accumulated into.
+ * dL/dalpha and the six geometry sums are linear in the channel set, so the feature channels run
+ * as launches of their own beside the colour / planes blend-backward, each carrying r for its own
+ * channels and adding into the same zeroed 2D gradient rows: the same gradient up to the float32
+ * rounding of the sums.  They are timed inside ms[1] of gsr_backward_times.
+ * A NULL feat, or one with dL_dfeature_map NULL, is gsr_backward_strip itself: the same kernels,
+ * the same arguments.  tile_row_begin / tile_row_end are honoured exactly as there.  With a feature
+ * gradient present in->dL_dcolor may be NULL and reads as zero; then no colour blend-backward
+ * runs.  dL_dfeatures may be NULL when only the geometry's gradients are wanted.  Refused with
+ * GSR_E_INVALID and nothing written: C < 1 or C > GSR_MAX_FEATURES, features NULL with a gradient
+ * given, and order->deterministic == 1 together with a feature gradient (the deterministic slots
+ * hold 9 or 10 sums per (Gaussian, tile, quadrant) and have no room for C more). */
+#define GSR_MAX_FEATURES 256
+typedef struct {
+    int32_t C;             /* channels per Gaussian, 1..GSR_MAX_FEATURES */
+    const float *features; /* [P, C] */
+    float *feature_map;    /* [C, rows, W] or NULL */
+} gsr_feature_outputs;
+int gsr_forward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                         gsr_outputs *out, const gsr_depth_outputs *depth,
+                         const gsr_surface_outputs *surface, const gsr_filter_settings *filter,
+                         const gsr_feature_outputs *feat, void *stream);
+typedef struct {
+    int32_t C;
+    const float *features;        /* [P, C] */
+    const float *dL_dfeature_map; /* [C, rows, W] or NULL */
+    float *dL_dfeatures;          /* [P, C] or NULL */
+} gsr_feature_gradients;
+int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                          const gsr_backward_order *order, const gsr_feature_gradients *feat,
+                          gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

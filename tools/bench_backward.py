@@ -36,11 +36,17 @@ any of the options above.  Also reports the strip's tile rows and, with --determ
 slots' and marks' workspace for the strip's num_rendered (det_workspace_MB).  The atomic figures
 are not reported for a strip (--contributions is the whole frame's).
 
+--features C: forward and backward with C feature channels per Gaussian beside the colour
+(gsr_forward_features, gsr_backward_features: the k_blend_features_q launches inside the forward,
+the k_blend_bwd_features_q launches inside blend_bwd_ms); with --planes, --camera, --antialiasing
+and --strip, not with --deterministic.  The atomic figures are not reported (--contributions counts
+the colour pass's).  tools/bench_features.py compares the pair with what a caller had to do before.
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
                                       [--camera] [--antialiasing] [--deterministic]
-                                      [--strip r/N]
+                                      [--strip r/N] [--features C]
 """
 import argparse
 import ctypes
@@ -85,11 +91,18 @@ def worker(a):
         extras = ("depth_map", "inv_depth_map", "final_T")
         plane_grads = {f"dL_d{n}": torch.randn((n_rows, scene.W), device=dev) for n in extras}
 
+    feat = {}
+    if a.features:
+        feat = {"features": torch.randn((scene.xyz.shape[0], a.features), device=dev)}
+        bwd_strip = dict(bwd_strip, **feat, dL_dfeature_map=torch.randn(
+            (a.features, n_rows, scene.W), device=dev))
+
     def forward():
         return rasterize_gaussians_native(scene.bg, scene.xyz, None, scene.opacity, scene.scale,
                                           scene.rot, 1.0, None, view, proj, tx, ty, scene.H,
                                           scene.W, scene.sh, scene.deg, campos, False, False,
-                                          out_color=color, extras=extras, **aa, **fwd_strip)
+                                          out_color=color, extras=extras, **aa, **fwd_strip,
+                                          **feat)
 
     def backward():
         return rasterize_gaussians_backward_native(scene.bg, scene.xyz, None, scene.opacity,
@@ -101,7 +114,7 @@ def worker(a):
 
     out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
            "camera": bool(a.camera), "antialiasing": bool(a.antialiasing),
-           "deterministic": bool(a.deterministic)}
+           "deterministic": bool(a.deterministic), "features": a.features}
     if a.strip:
         out.update(strip=a.strip, tile_rows=list(fwd_strip["tile_rows"]), rows=n_rows)
     if a.step == "forward":
@@ -168,6 +181,8 @@ def main():
     ap.add_argument("--strip", default=None, metavar="r/N",
                     help="strip r of the equal split of the tile rows into N: the strip forward "
                          "and gsr_backward_strip")
+    ap.add_argument("--features", type=int, default=0, metavar="C",
+                    help="C feature channels per Gaussian beside the colour, forward and backward")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -180,13 +195,14 @@ def main():
                            (["--camera"] if a.camera else []) +
                            (["--antialiasing"] if a.antialiasing else []) +
                            (["--deterministic"] if a.deterministic else []) +
-                           (["--strip", a.strip] if a.strip else []),
+                           (["--strip", a.strip] if a.strip else []) +
+                           (["--features", str(a.features)] if a.features else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"bench_backward: the {step} step failed ({r.returncode}); nothing more is run")
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    if a.deterministic or a.strip:  # plain stores to slots: no atomic traffic to report
+    if a.deterministic or a.strip or a.features:  # no colour-pass atomic traffic to report
         print(json.dumps(out))
         return
     atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0))
