@@ -61,6 +61,11 @@ tile_row_end, features)` is `gsr_forward_features` -> the 6-tuple of `rasterize_
 then feature_map (C, rows, W); `_C.rasterize_gaussians_backward_features(<the backward's
 arguments>, deterministic, tile_row_begin, tile_row_end, image_height, features,
 dL_dfeature_map)` is `gsr_backward_features` -> the 11-tuple, then dL_dfeatures (P, C).
+The photometric loss (`losses.photometric_loss`): `_C.fused_image_loss(image, target,
+lambda_dssim, need_saved)` is `gsr_image_loss` -> (values (3,) = loss, l1, ssim; saved
+(3, C, H, W), empty without `need_saved`), and `_C.fused_image_loss_backward(image, target,
+lambda_dssim, saved, dL_dloss)` is `gsr_image_loss_backward` -> dL_dimage; the images are contiguous
+float32 (C, H, W) device tensors and dL_dloss one device value (empty = 1.0).  No context is used.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -68,7 +73,8 @@ No fallback: importing this module fails when `_native.so` is not built
 from __future__ import annotations
 
 try:
-    from ._native import (abi_version, mark_visible, rasterize_gaussians,  # noqa: F401
+    from ._native import (abi_version, fused_image_loss, fused_image_loss_backward,  # noqa: F401
+                          mark_visible, rasterize_gaussians,
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,
                           rasterize_gaussians_backward_strip_ext, rasterize_gaussians_ext,

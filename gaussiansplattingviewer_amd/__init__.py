@@ -16,6 +16,7 @@ from .renderer import (GaussianDataHIP, GaussianRenderBase, HIPRenderer, _sort_g
 from .gaussian_data import GaussianData, naive_gaussian, synthetic_gaussians
 from .camera import Camera, cuda_camera_inputs, look_at, orbit_eye, static_camera
 from .strips import strip_rows, render_strips
+from .losses import photometric_loss, ssim
 
 __all__ = [
     "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
@@ -23,5 +24,5 @@ __all__ = [
     "GaussianRenderBase", "GaussianDataHIP", "gaus_hip_from_cpu", "_sort_gaussian_hip",
     "depth_argsort", "GaussianData", "naive_gaussian", "synthetic_gaussians", "Camera",
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
-    "render_strips",
+    "render_strips", "photometric_loss", "ssim",
 ]

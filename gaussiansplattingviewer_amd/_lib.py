@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
     "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
+    "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -142,6 +143,13 @@ class GsrFeatureGradients(ctypes.Structure):
                 ("dL_dfeature_map", ctypes.c_void_p), ("dL_dfeatures", ctypes.c_void_p)]
 
 
+class GsrImageLossInputs(ctypes.Structure):
+    """gsr_image_loss_inputs: the two [C, H, W] images of gsr_image_loss and its backward."""
+    _fields_ = [("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("lambda_", ctypes.c_float), ("image", ctypes.c_void_p),
+                ("target", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -199,6 +207,14 @@ def _declare(lib: ctypes.CDLL) -> None:
             fn.argtypes = [vp, ctypes.POINTER(GsrGaussians), ctypes.POINTER(GsrRasterSettings),
                            *(ctypes.POINTER(t) for t in structs), vp]
             fn.restype = i32
+    if hasattr(lib, "gsr_image_loss"):
+        loss_in = ctypes.POINTER(GsrImageLossInputs)
+        lib.gsr_image_loss_workspace.argtypes = [ctypes.c_int32] * 3
+        lib.gsr_image_loss_workspace.restype = i64
+        lib.gsr_image_loss.argtypes = [loss_in, vp, vp, vp, vp]
+        lib.gsr_image_loss.restype = i32
+        lib.gsr_image_loss_backward.argtypes = [loss_in, vp, vp, vp, vp]
+        lib.gsr_image_loss_backward.restype = i32
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
@@ -309,6 +325,13 @@ def features_fns(lib: ctypes.CDLL):
     build does not have them."""
     return _optional_fn(lib, "gsr_forward_features / gsr_backward_features",
                         "per-Gaussian feature channels need")
+
+
+def image_loss_fns(lib: ctypes.CDLL):
+    """(gsr_image_loss_workspace, gsr_image_loss, gsr_image_loss_backward) of a loaded library;
+    RuntimeError if that build does not have them."""
+    return _optional_fn(lib, "gsr_image_loss_workspace / gsr_image_loss / "
+                        "gsr_image_loss_backward", "the fused image loss needs")
 
 
 def check(rc: int, what: str) -> int:

@@ -67,6 +67,13 @@
 //     is then not read); dL_dout_color may be empty.  `deterministic` is refused by the library.
 //   _C.mark_visible(means3D, viewmatrix, projmatrix) -> bool [P]
 //     upstream markVisible (GaussianRasterizer.markVisible).
+//   _C.fused_image_loss(image, target, lambda_dssim, need_saved) -> (values [3], saved)
+//     this package's own: gsr_image_loss, the fused L1 + D-SSIM loss of two contiguous float32
+//     [C, H, W] device images; values = (loss, l1, ssim), saved = [3, C, H, W] for the backward,
+//     empty (and not computed) without `need_saved`.  No context is involved.
+//   _C.fused_image_loss_backward(image, target, lambda_dssim, saved, dL_dloss) -> dL_dimage
+//     gsr_image_loss_backward; dL_dloss is a one-element device tensor (read on the device, no
+//     host wait) or empty for 1.0.
 #include <torch/extension.h>
 
 #include <c10/hip/HIPGuard.h>
@@ -557,6 +564,70 @@ torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &vi
     return present;
 }
 
+// The loss's two images: contiguous float32 [C, H, W] on one HIP device (the Python entry makes
+// them so); fills the C ABI's struct.
+gsr_image_loss_inputs loss_inputs(const torch::Tensor &image, const torch::Tensor &target,
+                                  double lambda) {
+    TORCH_CHECK(image.is_cuda() && target.is_cuda(), "image and target must be device (HIP) tensors");
+    TORCH_CHECK(image.device() == target.device(), "image and target must be on one device");
+    TORCH_CHECK(image.dim() == 3 && image.sizes() == target.sizes(),
+                "image and target must have one shape (C, H, W)");
+    TORCH_CHECK(image.scalar_type() == torch::kFloat32 && target.scalar_type() == torch::kFloat32 &&
+                    image.is_contiguous() && target.is_contiguous(),
+                "image and target must be contiguous float32");
+    TORCH_CHECK(image.numel() < ((int64_t)1 << 31), "image too large: C*H*W must be < 2^31");
+    gsr_image_loss_inputs in{};
+    in.C = (int32_t)image.size(0);
+    in.H = (int32_t)image.size(1);
+    in.W = (int32_t)image.size(2);
+    in.lambda = (float)lambda;
+    in.image = image.data_ptr<float>();
+    in.target = target.data_ptr<float>();
+    return in;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> fused_image_loss(const torch::Tensor &image,
+                                                          const torch::Tensor &target,
+                                                          double lambda, bool need_saved) {
+    const gsr_image_loss_inputs in = loss_inputs(image, target, lambda);
+    const int64_t bytes = gsr_image_loss_workspace(in.C, in.H, in.W);
+    TORCH_CHECK(bytes >= 0, "gsr_image_loss_workspace failed (", bytes, "): ", gsr_last_error());
+    c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor values = torch::empty({3}, image.options());
+    torch::Tensor saved = need_saved ? torch::empty({3, in.C, in.H, in.W}, image.options())
+                                     : torch::empty({0}, image.options());
+    torch::Tensor ws = torch::empty({bytes}, image.options().dtype(torch::kUInt8));
+    hipStream_t s = c10::hip::getCurrentHIPStream(image.device().index()).stream();
+    const int rc = gsr_image_loss(&in, values.data_ptr<float>(),
+                                  need_saved ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), s);
+    TORCH_CHECK(rc == GSR_OK, "gsr_image_loss failed (", rc, "): ", gsr_last_error());
+    return std::make_tuple(values, saved);
+}
+
+torch::Tensor fused_image_loss_backward(const torch::Tensor &image, const torch::Tensor &target,
+                                        double lambda, const torch::Tensor &saved,
+                                        const torch::Tensor &dL_dloss) {
+    const gsr_image_loss_inputs in = loss_inputs(image, target, lambda);
+    TORCH_CHECK(saved.is_cuda() && saved.device() == image.device() &&
+                    saved.scalar_type() == torch::kFloat32 && saved.is_contiguous() &&
+                    saved.numel() == 3 * image.numel(),
+                "saved must be the forward's contiguous float32 (3, C, H, W) tensor");
+    const float *gl = nullptr;
+    torch::Tensor g;
+    if (dL_dloss.defined() && dL_dloss.numel() != 0) {
+        TORCH_CHECK(dL_dloss.numel() == 1, "dL_dloss must hold one value");
+        g = dL_dloss.to(image.device(), torch::kFloat32).contiguous();
+        gl = g.data_ptr<float>();
+    }
+    c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor grad = torch::empty_like(image);
+    hipStream_t s = c10::hip::getCurrentHIPStream(image.device().index()).stream();
+    const int rc = gsr_image_loss_backward(&in, saved.data_ptr<float>(), gl,
+                                           grad.data_ptr<float>(), s);
+    TORCH_CHECK(rc == GSR_OK, "gsr_image_loss_backward failed (", rc, "): ", gsr_last_error());
+    return grad;
+}
+
 void release_contexts() {
     std::lock_guard<std::mutex> lk(g_lock);
     for (gsr_context *&c : g_ctx) {
@@ -622,6 +693,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "image_height, features (P, C), dL_dfeature_map (C, rows, W): gsr_backward_features -> "
           "the 11-tuple, then dL_dfeatures (P, C)");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
+    m.def("fused_image_loss", &fused_image_loss,
+          "image, target (contiguous float32 (C, H, W)), lambda_dssim, need_saved: gsr_image_loss "
+          "-> (values (3,) = loss, l1, ssim; saved (3, C, H, W), empty without need_saved)");
+    m.def("fused_image_loss_backward", &fused_image_loss_backward,
+          "image, target, lambda_dssim, saved, dL_dloss (one device value, or empty for 1.0): "
+          "gsr_image_loss_backward -> dL_dimage (C, H, W)");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(
         "context_handle",

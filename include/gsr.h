@@ -648,6 +648,57 @@ int gsr_disparity_colors(const float *means3D, int64_t P, const float *view_host
 int gsr_pack_image(const float *chw, int32_t H, int32_t W, int32_t format, int32_t flip_rows,
                    void *out, void *stream);
 
+/* ---- The photometric loss of a fit: fused L1 + D-SSIM of one image against a target ----
+ * (additive to ABI 4)
+ *
+ *   loss = (1 - lambda) * l1 + lambda * (1 - ssim),  l1 = mean|image - target|, ssim = mean(map)
+ *
+ * over all N = C*H*W elements of two contiguous float32 [C, H, W] images whose channels are
+ * independent.  The window is g (x) g with g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0..10,
+ * normalised to sum 1 (the kernels hold the float32 roundings of the float64 values); conv(x) is
+ * the "same" correlation with zero padding of 5 per channel, so images smaller than the window
+ * are valid.  With mu1 = conv(image), mu2 = conv(target), s1 = conv(image^2) - mu1^2,
+ * s2 = conv(target^2) - mu2^2, s12 = conv(image target) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2:
+ *   A = mu1^2 + mu2^2 + C1, B = s1 + s2 + C2, Cc = 2 mu1 mu2 + C1, D = 2 s12 + C2,
+ *   map = Cc D / (A B).
+ * NaN and infinities propagate; nothing is clamped.  A strip image is an image like any other:
+ * its loss is that of the strip alone, zero padded at the strip's edges.
+ *
+ * Neither call takes a context (no mutex, no ordering against frames in flight), allocates or
+ * synchronises: all memory is the caller's and all work is enqueued on `stream`.  No atomics:
+ * every block writes its two partial sums to `workspace` and one finishing block adds them in
+ * a fixed order in double and rounds once, so `values` and `dL_dimage` have the same bits on
+ * every call with the same inputs, on any stream.
+ *
+ * gsr_image_loss_workspace: the bytes of device scratch gsr_image_loss needs for C, H, W
+ *   (GSR_E_INVALID for a size < 1 or C*H*W >= 2^31).
+ * gsr_image_loss: values = device float[3] (loss, l1, ssim).  saved = device [3, C, H, W], the
+ *   partial derivatives of map the backward reads,
+ *     dm_dmu1 = 2 mu2 D/(A B) - 2 mu2 Cc/(A B) - 2 mu1 Cc D/(A^2 B) + 2 mu1 Cc D/(A B^2),
+ *     dm_ds1  = -Cc D/(A B^2),   dm_ds12 = 2 Cc/(A B),
+ *   or NULL when no gradient is wanted: then nothing of them is computed or written.
+ * gsr_image_loss_backward: the gradient with respect to `image` (target is a constant).  With
+ *   gl = *dL_dloss (a device float[1], so that no host wait is needed; NULL = 1.0) and
+ *   gm = -gl lambda / N,
+ *     dL_dimage = gm conv(dm_dmu1) + 2 image gm conv(dm_ds1) + target gm conv(dm_ds12)
+ *                 + gl (1 - lambda)/N sign(image - target),   sign(0) = 0
+ *   (the window is symmetric, so conv is its own adjoint).  dL_dimage [C, H, W] is written, not
+ *   accumulated into.
+ * Refused with GSR_E_INVALID before any HIP call, nothing written: a NULL in, image, target or
+ * values; a size < 1 or C*H*W >= 2^31; lambda outside [0, 1] or NaN; a NULL workspace; the
+ * backward's NULL saved or dL_dimage. */
+typedef struct gsr_image_loss_inputs {
+    int32_t C, H, W;
+    float lambda;        /* the weight of the D-SSIM term (3D Gaussian Splatting: 0.2) */
+    const float *image;  /* device [C, H, W] */
+    const float *target; /* device [C, H, W] */
+} gsr_image_loss_inputs;
+int64_t gsr_image_loss_workspace(int32_t C, int32_t H, int32_t W);
+int gsr_image_loss(const gsr_image_loss_inputs *in, float *values, float *saved, void *workspace,
+                   void *stream);
+int gsr_image_loss_backward(const gsr_image_loss_inputs *in, const float *saved,
+                            const float *dL_dloss, float *dL_dimage, void *stream);
+
 /* Stage timing (HIP events on the forward's stream, no extra synchronisation).
  * gsr_set_timing(1) starts recording one event set per forward (a ring of the last 256);
  * gsr_stage_times waits for the last timed forward and writes the MEAN per-stage time (ms)
