@@ -66,6 +66,12 @@ lambda_dssim, need_saved)` is `gsr_image_loss` -> (values (3,) = loss, l1, ssim;
 (3, C, H, W), empty without `need_saved`), and `_C.fused_image_loss_backward(image, target,
 lambda_dssim, saved, dL_dloss)` is `gsr_image_loss_backward` -> dL_dimage; the images are contiguous
 float32 (C, H, W) device tensors and dL_dloss one device value (empty = 1.0).  No context is used.
+The optimizer (`optim.SparseGaussianAdam`, `optim.densification_stats`): `_C.adamUpdate(param,
+grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)` has upstream's signature (one group,
+in place, no bias correction); `_C.fused_adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs,
+epss, mask, b1, b2, bc1, bc2_sqrt)` is `gsr_adam_step` on up to 8 groups in one launch (mask: bool
+or uint8 (P), int32 radii (P), or empty); `_C.densification_stats(radii, means2D_grad, grad_accum,
+denom, max_radii)` is `gsr_densify_stats`.  All three work in place on torch's current stream.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -73,7 +79,8 @@ No fallback: importing this module fails when `_native.so` is not built
 from __future__ import annotations
 
 try:
-    from ._native import (abi_version, fused_image_loss, fused_image_loss_backward,  # noqa: F401
+    from ._native import (abi_version, adamUpdate, densification_stats,  # noqa: F401
+                          fused_adam_step, fused_image_loss, fused_image_loss_backward,
                           mark_visible, rasterize_gaussians,
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,

@@ -17,6 +17,7 @@ from .gaussian_data import GaussianData, naive_gaussian, synthetic_gaussians
 from .camera import Camera, cuda_camera_inputs, look_at, orbit_eye, static_camera
 from .strips import strip_rows, render_strips
 from .losses import photometric_loss, ssim
+from .optim import SparseGaussianAdam, densification_stats
 
 __all__ = [
     "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
@@ -24,5 +25,6 @@ __all__ = [
     "GaussianRenderBase", "GaussianDataHIP", "gaus_hip_from_cpu", "_sort_gaussian_hip",
     "depth_argsort", "GaussianData", "naive_gaussian", "synthetic_gaussians", "Camera",
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
-    "render_strips", "photometric_loss", "ssim",
+    "render_strips", "photometric_loss", "ssim", "SparseGaussianAdam",
+    "densification_stats",
 ]

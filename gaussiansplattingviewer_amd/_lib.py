@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
     "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
     "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
+    "gsr_adam_step", "gsr_densify_stats",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -150,6 +151,31 @@ class GsrImageLossInputs(ctypes.Structure):
                 ("target", ctypes.c_void_p)]
 
 
+MAX_PARAM_GROUPS = 8  # GSR_MAX_PARAM_GROUPS
+
+
+class GsrParamGroup(ctypes.Structure):
+    """gsr_param_group: one [P, M] parameter tensor of gsr_adam_step with its gradient and moments."""
+    _fields_ = [("M", ctypes.c_int32), ("lr", ctypes.c_float), ("eps", ctypes.c_float),
+                ("param", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+                ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p)]
+
+
+class GsrAdamSettings(ctypes.Structure):
+    """gsr_adam_settings: what the groups of one gsr_adam_step share; at most one mask."""
+    _fields_ = [("P", ctypes.c_int64), ("n_groups", ctypes.c_int32),
+                ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("bias_correction1", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float),
+                ("visible", ctypes.c_void_p), ("radii", ctypes.c_void_p)]
+
+
+class GsrDensifyInputs(ctypes.Structure):
+    """gsr_densify_inputs: gsr_densify_stats' radii, dL_dmeans2D and the three accumulators."""
+    _fields_ = [("P", ctypes.c_int64), ("radii", ctypes.c_void_p),
+                ("dL_dmeans2D", ctypes.c_void_p), ("grad_accum", ctypes.c_void_p),
+                ("denom", ctypes.c_void_p), ("max_radii", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -215,6 +241,12 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_image_loss.restype = i32
         lib.gsr_image_loss_backward.argtypes = [loss_in, vp, vp, vp, vp]
         lib.gsr_image_loss_backward.restype = i32
+    if hasattr(lib, "gsr_adam_step"):
+        lib.gsr_adam_step.argtypes = [ctypes.POINTER(GsrAdamSettings),
+                                      ctypes.POINTER(GsrParamGroup), vp]
+        lib.gsr_adam_step.restype = i32
+        lib.gsr_densify_stats.argtypes = [ctypes.POINTER(GsrDensifyInputs), vp]
+        lib.gsr_densify_stats.restype = i32
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
@@ -332,6 +364,13 @@ def image_loss_fns(lib: ctypes.CDLL):
     RuntimeError if that build does not have them."""
     return _optional_fn(lib, "gsr_image_loss_workspace / gsr_image_loss / "
                         "gsr_image_loss_backward", "the fused image loss needs")
+
+
+def optimizer_fns(lib: ctypes.CDLL):
+    """(gsr_adam_step, gsr_densify_stats) of a loaded library; RuntimeError if that build does
+    not have them."""
+    return _optional_fn(lib, "gsr_adam_step / gsr_densify_stats",
+                        "the fused Adam step and the densification statistics need")
 
 
 def check(rc: int, what: str) -> int:

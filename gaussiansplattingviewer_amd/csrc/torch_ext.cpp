@@ -74,6 +74,17 @@
 //   _C.fused_image_loss_backward(image, target, lambda_dssim, saved, dL_dloss) -> dL_dimage
 //     gsr_image_loss_backward; dL_dloss is a one-element device tensor (read on the device, no
 //     host wait) or empty for 1.0.
+//   _C.adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)
+//     upstream's fused sparse Adam (SparseGaussianAdam): gsr_adam_step on one [N, M] group, in
+//     place, for the rows whose `visible` (bool or uint8 [N]) is set; no bias correction.
+//   _C.fused_adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, epss, mask, b1, b2, bc1,
+//                      bc2_sqrt)
+//     this package's own: gsr_adam_step on 1..GSR_MAX_PARAM_GROUPS groups [P, M_i] in ONE launch,
+//     in place.  mask: bool / uint8 [P] (visible), int32 [P] (radii, > 0 = update) or empty
+//     (every row).  bc1, bc2_sqrt: 1 - b1^t and sqrt(1 - b2^t), or 1.0 for upstream's form.
+//   _C.densification_stats(radii, means2D_grad, grad_accum, denom, max_radii)
+//     gsr_densify_stats, upstream's add_densification_stats in place; max_radii int32 [P] or
+//     empty.  None of the three uses a context.
 #include <torch/extension.h>
 
 #include <c10/hip/HIPGuard.h>
@@ -628,6 +639,137 @@ torch::Tensor fused_image_loss_backward(const torch::Tensor &image, const torch:
     return grad;
 }
 
+// A float32 [P, M] tensor of the optimizer entries: on `dev`, contiguous, `numel` elements.
+float *adam_buffer(const torch::Tensor &t, const torch::Device &dev, int64_t numel,
+                   const char *name) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == dev, name,
+                " must be a device (HIP) tensor on the parameters' device");
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous(), name,
+                " must be contiguous float32");
+    TORCH_CHECK(t.numel() == numel, name, " holds ", t.numel(), " values, expected ", numel);
+    return t.data_ptr<float>();
+}
+
+// mask -> the settings' visible (bool / uint8) or radii (int32), or neither for an empty one
+void adam_mask(const torch::Tensor &mask, const torch::Device &dev, int64_t P,
+               gsr_adam_settings *s) {
+    if (!mask.defined() || mask.numel() == 0) return;
+    TORCH_CHECK(mask.is_cuda() && mask.device() == dev && mask.is_contiguous(),
+                "mask must be a contiguous device (HIP) tensor on the parameters' device");
+    TORCH_CHECK(mask.numel() == P, "mask holds ", mask.numel(), " values, expected ", P);
+    if (mask.scalar_type() == torch::kBool || mask.scalar_type() == torch::kUInt8)
+        s->visible = static_cast<const uint8_t *>(mask.data_ptr());
+    else if (mask.scalar_type() == torch::kInt32)
+        s->radii = mask.data_ptr<int32_t>();
+    else
+        TORCH_CHECK(false, "mask must be bool, uint8 (visible) or int32 (radii)");
+}
+
+void fused_adam_step(const std::vector<torch::Tensor> &params,
+                     const std::vector<torch::Tensor> &grads,
+                     const std::vector<torch::Tensor> &exp_avgs,
+                     const std::vector<torch::Tensor> &exp_avg_sqs, const std::vector<double> &lrs,
+                     const std::vector<double> &epss, const torch::Tensor &mask, double b1,
+                     double b2, double bc1, double bc2_sqrt) {
+    const size_t n = params.size();
+    TORCH_CHECK(n >= 1 && n <= GSR_MAX_PARAM_GROUPS, "1..", GSR_MAX_PARAM_GROUPS,
+                " parameter groups per call, got ", n);
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n &&
+                    lrs.size() == n && epss.size() == n,
+                "params, grads, exp_avgs, exp_avg_sqs, lrs and epss must have one length");
+    TORCH_CHECK(params[0].defined() && params[0].is_cuda(),
+                "params must be device (HIP) tensors");
+    const torch::Device dev = params[0].device();
+    TORCH_CHECK(params[0].dim() >= 1, "a parameter must be at least 1-D: [P, ...]");
+    const int64_t P = params[0].size(0);
+    gsr_adam_settings s{};
+    s.P = P;
+    s.n_groups = (int32_t)n;
+    s.beta1 = (float)b1;
+    s.beta2 = (float)b2;
+    s.bias_correction1 = (float)bc1;
+    s.bias_correction2_sqrt = (float)bc2_sqrt;
+    adam_mask(mask, dev, P, &s);
+    gsr_param_group g[GSR_MAX_PARAM_GROUPS] = {};
+    for (size_t i = 0; i < n; ++i) {
+        const torch::Tensor &p = params[i];
+        TORCH_CHECK(p.defined() && p.dim() >= 1 && p.size(0) == P,
+                    "every parameter's first dimension must be ", P);
+        const int64_t numel = p.numel(), M = P > 0 ? numel / P : 1;
+        TORCH_CHECK(M >= 1 && M < ((int64_t)1 << 31), "a parameter row of ", M, " floats");
+        g[i].M = (int32_t)M;
+        g[i].lr = (float)lrs[i];
+        g[i].eps = (float)epss[i];
+        g[i].param = adam_buffer(p, dev, numel, "param");
+        g[i].grad = adam_buffer(grads[i], dev, numel, "grad");
+        g[i].exp_avg = adam_buffer(exp_avgs[i], dev, numel, "exp_avg");
+        g[i].exp_avg_sq = adam_buffer(exp_avg_sqs[i], dev, numel, "exp_avg_sq");
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_adam_step(&s, g, st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_adam_step failed (", rc, "): ", gsr_last_error());
+}
+
+void adam_update(torch::Tensor &param, const torch::Tensor &grad, torch::Tensor &exp_avg,
+                 torch::Tensor &exp_avg_sq, const torch::Tensor &visible, double lr, double b1,
+                 double b2, double eps, int64_t N, int64_t M) {
+    TORCH_CHECK(param.defined() && param.is_cuda(), "param must be a device (HIP) tensor");
+    TORCH_CHECK(N >= 0 && M >= 1 && M < ((int64_t)1 << 31), "bad N, M: ", N, ", ", M);
+    TORCH_CHECK(visible.defined() && visible.numel() == N &&
+                    (visible.scalar_type() == torch::kBool ||
+                     visible.scalar_type() == torch::kUInt8),
+                "visible must be a bool or uint8 tensor of N values");
+    const torch::Device dev = param.device();
+    gsr_adam_settings s{};
+    s.P = N;
+    s.n_groups = 1;
+    s.beta1 = (float)b1;
+    s.beta2 = (float)b2;
+    s.bias_correction1 = 1.0f;
+    s.bias_correction2_sqrt = 1.0f;
+    adam_mask(visible, dev, N, &s);
+    gsr_param_group g{};
+    g.M = (int32_t)M;
+    g.lr = (float)lr;
+    g.eps = (float)eps;
+    g.param = adam_buffer(param, dev, N * M, "param");
+    g.grad = adam_buffer(grad, dev, N * M, "grad");
+    g.exp_avg = adam_buffer(exp_avg, dev, N * M, "exp_avg");
+    g.exp_avg_sq = adam_buffer(exp_avg_sq, dev, N * M, "exp_avg_sq");
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_adam_step(&s, &g, st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_adam_step failed (", rc, "): ", gsr_last_error());
+}
+
+void densification_stats(const torch::Tensor &radii, const torch::Tensor &means2D_grad,
+                         torch::Tensor &grad_accum, torch::Tensor &denom,
+                         const torch::Tensor &max_radii) {
+    TORCH_CHECK(radii.defined() && radii.is_cuda() && radii.scalar_type() == torch::kInt32 &&
+                    radii.is_contiguous(),
+                "radii must be a contiguous int32 device (HIP) tensor");
+    const torch::Device dev = radii.device();
+    const int64_t P = radii.numel();
+    gsr_densify_inputs in{};
+    in.P = P;
+    in.radii = radii.data_ptr<int32_t>();
+    in.dL_dmeans2D = adam_buffer(means2D_grad, dev, 3 * P, "means2D_grad");
+    in.grad_accum = adam_buffer(grad_accum, dev, P, "grad_accum");
+    in.denom = adam_buffer(denom, dev, P, "denom");
+    if (max_radii.defined() && max_radii.numel() != 0) {
+        TORCH_CHECK(max_radii.is_cuda() && max_radii.device() == dev &&
+                        max_radii.scalar_type() == torch::kInt32 && max_radii.is_contiguous() &&
+                        max_radii.numel() == P,
+                    "max_radii must be a contiguous int32 tensor of ", P, " values on radii's device");
+        in.max_radii = max_radii.data_ptr<int32_t>();
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_densify_stats(&in, st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_densify_stats failed (", rc, "): ", gsr_last_error());
+}
+
 void release_contexts() {
     std::lock_guard<std::mutex> lk(g_lock);
     for (gsr_context *&c : g_ctx) {
@@ -699,6 +841,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_image_loss_backward", &fused_image_loss_backward,
           "image, target, lambda_dssim, saved, dL_dloss (one device value, or empty for 1.0): "
           "gsr_image_loss_backward -> dL_dimage (C, H, W)");
+    m.def("adamUpdate", &adam_update,
+          "upstream's adamUpdate: param, grad, exp_avg, exp_avg_sq (N, M), visible (bool or uint8 "
+          "N), lr, b1, b2, eps, N, M: gsr_adam_step on one group, in place, no bias correction");
+    m.def("fused_adam_step", &fused_adam_step,
+          "params, grads, exp_avgs, exp_avg_sqs (lists of (P, M_i) tensors), lrs, epss, mask "
+          "(bool / uint8 (P), int32 radii (P), or empty), b1, b2, bc1, bc2_sqrt: gsr_adam_step on "
+          "all groups in one launch, in place");
+    m.def("densification_stats", &densification_stats,
+          "radii (P) int32, means2D_grad (P, 3), grad_accum (P), denom (P), max_radii (P) int32 "
+          "or empty: gsr_densify_stats, in place");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(
         "context_handle",

@@ -699,6 +699,75 @@ int gsr_image_loss(const gsr_image_loss_inputs *in, float *values, float *saved,
 int gsr_image_loss_backward(const gsr_image_loss_inputs *in, const float *saved,
                             const float *dL_dloss, float *dL_dimage, void *stream);
 
+/* ---- The parameter update of a fit: a fused, visibility-masked ("sparse") Adam step, and the
+ * densification statistics ---- (additive to ABI 4)
+ *
+ * gsr_adam_step updates up to GSR_MAX_PARAM_GROUPS parameter tensors of one scene, [P, M] each
+ * with its own M, lr and eps, in ONE kernel launch.  Every element of an updated row runs, in
+ * float32, in exactly this order, without FMA contraction and with a correctly rounded divide
+ * and square root:
+ *
+ *   m = beta1 * m + (1.0f - beta1) * g
+ *   v = beta2 * v + ((1.0f - beta2) * g) * g
+ *   p = p - (lr / bias_correction1) * (m / (sqrtf(v) / bias_correction2_sqrt + eps))
+ *
+ * (1.0f - beta and lr / bias_correction1 are computed once, in float32.)  With both corrections
+ * 1.0f the divisions by them are exact and this is upstream's adamUpdate (SparseGaussianAdam);
+ * with 1 - beta1^t and sqrt(1 - beta2^t) it is torch.optim.Adam's step without weight decay,
+ * amsgrad or maximize.  NaN and infinities propagate; nothing is clamped; g = 0, v = 0, eps > 0
+ * leaves p unchanged.
+ *
+ * The rows that are updated: with `visible`, those whose byte is nonzero; with `radii` (the
+ * rasterizer's output), those with radii[i] > 0; with neither, all.  A row that is not updated is
+ * never read or written, in any of its four buffers: it keeps its bits, moments included (they
+ * do not decay: the sparse rule), and a NaN in its grad reaches nothing.
+ *
+ * gsr_densify_stats is upstream's add_densification_stats: for every row with radii[i] > 0, in
+ * place, grad_accum[i] += sqrtf(x * x + y * y) (float32, in that order) with x, y =
+ * dL_dmeans2D[i][0], [1]; denom[i] += 1.0f; and, with max_radii, max_radii[i] =
+ * max(max_radii[i], radii[i]).  No other row is touched.
+ *
+ * Neither call takes a context, allocates or synchronises: all memory is the caller's (device
+ * memory, except the host array `groups`, which is read before the call returns) and all work is
+ * enqueued on `stream`.  The update is elementwise, so the results have the same bits on every
+ * call with the same inputs.  Buffers of one call that alias each other: undefined.
+ *
+ * Refused with GSR_E_INVALID before any HIP call, nothing written: gsr_adam_step for a NULL s or
+ * groups; P < 0; n_groups outside 1..GSR_MAX_PARAM_GROUPS; an M < 1; a NULL buffer with P > 0; a
+ * beta outside [0, 1) or NaN; a correction <= 0 or NaN; an lr or eps NaN; both masks given; sizes
+ * beyond 2^31 - 1 blocks (P M of the order of 2^41).  gsr_densify_stats for a NULL in, P < 0, or
+ * a NULL radii, dL_dmeans2D, grad_accum or denom with P > 0.  P == 0 is GSR_OK, with no launch. */
+#define GSR_MAX_PARAM_GROUPS 8
+typedef struct gsr_param_group {
+    int32_t M;            /* floats per Gaussian row, >= 1 */
+    float lr, eps;
+    float *param;         /* [P, M] contiguous float32; 4-byte alignment is enough */
+    const float *grad;    /* [P, M] */
+    float *exp_avg;       /* [P, M] */
+    float *exp_avg_sq;    /* [P, M] */
+} gsr_param_group;
+typedef struct gsr_adam_settings {
+    int64_t P;
+    int32_t n_groups;         /* 1..GSR_MAX_PARAM_GROUPS */
+    float beta1, beta2;
+    float bias_correction1;   /* 1 - beta1^t, or 1.0f for upstream's uncorrected form */
+    float bias_correction2_sqrt; /* sqrt(1 - beta2^t), or 1.0f */
+    const uint8_t *visible;   /* [P], nonzero = update the row; or NULL */
+    const int32_t *radii;     /* [P], > 0 = update the row (the rasterizer's output); or NULL */
+} gsr_adam_settings;
+int gsr_adam_step(const gsr_adam_settings *s, const gsr_param_group *groups /* host */,
+                  void *stream);
+
+typedef struct gsr_densify_inputs {
+    int64_t P;
+    const int32_t *radii;      /* [P] */
+    const float *dL_dmeans2D;  /* [P, 3], upstream's units; x and y are read */
+    float *grad_accum;         /* [P]  += sqrtf(x*x + y*y) */
+    float *denom;              /* [P]  += 1.0f */
+    int32_t *max_radii;        /* [P]  = max(old, radii), or NULL */
+} gsr_densify_inputs;
+int gsr_densify_stats(const gsr_densify_inputs *in, void *stream);
+
 /* Stage timing (HIP events on the forward's stream, no extra synchronisation).
  * gsr_set_timing(1) starts recording one event set per forward (a ring of the last 256);
  * gsr_stage_times waits for the last timed forward and writes the MEAN per-stage time (ms)
