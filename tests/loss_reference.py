@@ -66,9 +66,9 @@ def loss_values(image, target, lam, conv_fn=conv):
     return (1.0 - lam) * l1 + lam * (1.0 - ssim), l1, ssim
 
 
-def saved_partials(image, target):
+def saved_partials(image, target, conv_fn=conv):
     """[3, C, H, W]: dm_dmu1, dm_ds1, dm_ds12 of map = Cc D / (A B)."""
-    mu1, mu2, A, B, Cc, D = statistics(image, target)
+    mu1, mu2, A, B, Cc, D = statistics(image, target, conv_fn)
     dm_dmu1 = (2.0 * mu2 * D / (A * B) - 2.0 * mu2 * Cc / (A * B)
                - 2.0 * mu1 * Cc * D / (A * A * B) + 2.0 * mu1 * Cc * D / (A * B * B))
     return torch.stack([dm_dmu1, -Cc * D / (A * B * B), 2.0 * Cc / (A * B)])
@@ -83,15 +83,15 @@ def manual_gradient(image, target, lam, gl=1.0, conv_fn=conv):
             + gl * (1.0 - lam) / N * torch.sign(image - target))
 
 
-def evaluate(image, target, lam, dtype=torch.float64) -> dict:
+def evaluate(image, target, lam, dtype=torch.float64, conv_fn=conv) -> dict:
     """Every output of the fused loss for numpy float32 images, evaluated in `dtype`:
     loss, l1, ssim (floats), dL_dimage (autograd of the definition) and saved [3, C, H, W]."""
     x = torch.tensor(np.asarray(image), dtype=dtype).requires_grad_(True)
     y = torch.tensor(np.asarray(target), dtype=dtype)
-    loss, l1, ssim = loss_values(x, y, lam)
+    loss, l1, ssim = loss_values(x, y, lam, conv_fn)
     (grad,) = torch.autograd.grad(loss, x)
     with torch.no_grad():
-        saved = saved_partials(x, y)
+        saved = saved_partials(x, y, conv_fn)
     return dict(loss=float(loss.detach()), l1=float(l1.detach()), ssim=float(ssim.detach()),
                 dL_dimage=grad.numpy(),
                 saved=saved.numpy())
@@ -173,3 +173,128 @@ def reference(name: str, lam: float) -> dict:
             _REFERENCES["images"] = loss_images()
         _REFERENCES[key] = evaluate(*_REFERENCES["images"][name], lam)
     return _REFERENCES[key]
+
+
+# ---- the seam tests (test_gpu_image_loss_seams.py): well-conditioned images, exact properties ---
+# Uniform random [0, 1] pairs: no cancellation in 1 - ssim or in the partials, so the float32
+# spread is near the format's own precision and a wrong tap, halo column or corner pixel shows.
+
+SEAM_SHAPES = ((3, 33, 129),    # the smallest shape with a tile that is interior in both directions
+               (2, 48, 192),    # 3 x 3 tiles: the locality pair
+               (5, 100, 1000),  # 560 blocks, ragged last row (4 rows) and column (40) of tiles
+               (1, 1, 130), (1, 70, 1),             # one pixel thick
+               (2, 5, 5), (1, 11, 11), (1, 12, 12))  # at and around the window's width
+SEAM_LAMBDAS = (0.2, 1.0)
+LOCALITY_SHAPE = (2, 48, 192)
+LOCALITY_PIXELS = ((0, 0), (47, 191), (15, 63), (16, 64), (16, 63), (24, 96))
+TRANSLATION_SHAPE, CROP_H, CROP_W = (2, 64, 256), 32, 128
+TRANSLATION_OFFSETS = ((0, 0), (1, 1), (15, 63), (16, 64), (17, 65), (7, 100), (32, 128))
+# shape -> blocks (C x tiles_y x tiles_x): k_loss_finish's loop boundaries at 256 and 512 pairs
+INTEGER_SHAPES = {(5, 100, 1000): 560, (1, 16, 16384): 256, (1, 16, 16385): 257,
+                  (2, 16, 16384): 512, (3, 17, 65): 12}
+
+
+def shape_name(shape) -> str:
+    return "x".join(str(int(n)) for n in shape)
+
+
+def blocks_of(shape) -> int:
+    """The grid of both kernels: one block per 16 x 64 tile and channel."""
+    C, H, W = shape
+    return C * ((H + TILE_H - 1) // TILE_H) * ((W + TILE_W - 1) // TILE_W)
+
+
+def random_pair(shape, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(0.0, 1.0, size=shape).astype(np.float32),
+            rng.uniform(0.0, 1.0, size=shape).astype(np.float32))
+
+
+def seam_images() -> dict:
+    """"CxHxW" -> (image, target), uniform random in [0, 1], one pair per SEAM_SHAPES."""
+    return {shape_name(s): random_pair(s, 7100 + i) for i, s in enumerate(SEAM_SHAPES)}
+
+
+def translation_pair():
+    """The 4 x 4-tile pair whose 32 x 128 crops are compared with it."""
+    return random_pair(TRANSLATION_SHAPE, 7200)
+
+
+def crop(pair, dy, dx):
+    return tuple(np.ascontiguousarray(a[:, dy:dy + CROP_H, dx:dx + CROP_W]) for a in pair)
+
+
+def integer_images(shape):
+    """(image, target) of float32 integers 0..8: every |x - y| and every partial sum of them is an
+    integer below 2^24, so the kernels' float sums are exact whatever their order."""
+    rng = np.random.default_rng(2)
+    return (rng.integers(0, 9, size=shape).astype(np.float32),
+            rng.integers(0, 9, size=shape).astype(np.float32))
+
+
+def outside_window(H, W, r, c, radius) -> np.ndarray:
+    """[H, W] bool: True where (r, c) is not within `radius` rows and columns."""
+    rr, cc = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    return (np.abs(rr - r) > radius) | (np.abs(cc - c) > radius)
+
+
+def pixel_err(got, ref) -> float:
+    """max |got - ref| / (|ref| + median|ref|): every entry on its own scale, small ones on the
+    tensor's typical scale (not on its maximum, as rel_err)."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    a = np.abs(ref)
+    return float((np.abs(got - ref) / (a + np.median(a))).max())
+
+
+# Measured as F32_SPREAD is: `evaluate` in float32 against float64, the largest over seam_images()
+# and over the 2-D and the separable form of the window (the kernels are separable); "max" is
+# rel_err, "pixel" is pixel_err.  test_loss_reference.py holds the table within a factor 2 of a
+# fresh measurement; the GPU tests allow BOUND_FACTOR x it.
+SEAM_SPREAD = {
+    "max": {"dm_dmu1": 9.7e-6, "dm_ds1": 1.3e-5, "dm_ds12": 4.4e-6,
+            "dL_dimage": {0.2: 1.1e-6, 1.0: 1.5e-6}},
+    "pixel": {"dm_dmu1": 8.8e-6, "dm_ds1": 5.6e-5, "dm_ds12": 3.8e-6,
+              "dL_dimage": {0.2: 1.9e-6, 1.0: 3.3e-6}},
+}
+SEAM_ERRORS = {"max": rel_err, "pixel": pixel_err}
+
+
+def seam_reference(name: str, lam: float) -> dict:
+    """`evaluate` in float64 of a seam_images() pair, computed once and shared (read-only)."""
+    key = ("seam", name, float(lam))
+    if key not in _REFERENCES:
+        if "seam_images" not in _REFERENCES:
+            _REFERENCES["seam_images"] = seam_images()
+        _REFERENCES[key] = evaluate(*_REFERENCES["seam_images"][name], lam)
+    return _REFERENCES[key]
+
+
+def measure_seam_spread(images=None, per_image=None) -> dict:
+    """SEAM_SPREAD as measured now (`per_image`: a dict that receives each image's own table)."""
+    shared = images is None  # the module's own images: their float64 references are cached
+    images = images or seam_images()
+    blank =lambda: {kind: {**{k: 0.0 for k in SAVED_NAMES},  # noqa: E731
+                            "dL_dimage": {lam: 0.0 for lam in SEAM_LAMBDAS}}
+                     for kind in SEAM_ERRORS}
+    f = blank()
+    for name, (image, target) in images.items():
+        own = blank()
+        for lam in SEAM_LAMBDAS:
+            ref = seam_reference(name, lam) if shared else evaluate(image, target, lam)
+            for conv_fn in (conv, conv_separable):
+                got = evaluate(image, target, lam, torch.float32, conv_fn)
+                for kind, err in SEAM_ERRORS.items():
+                    own[kind]["dL_dimage"][lam] = max(own[kind]["dL_dimage"][lam],
+                                                      err(got["dL_dimage"], ref["dL_dimage"]))
+                    if lam == SEAM_LAMBDAS[0]:
+                        for i, k in enumerate(SAVED_NAMES):
+                            own[kind][k] = max(own[kind][k], err(got["saved"][i], ref["saved"][i]))
+        for kind in SEAM_ERRORS:
+            for k in SAVED_NAMES:
+                f[kind][k] = max(f[kind][k], own[kind][k])
+            for lam in SEAM_LAMBDAS:
+                f[kind]["dL_dimage"][lam] = max(f[kind]["dL_dimage"][lam],
+                                                own[kind]["dL_dimage"][lam])
+        if per_image is not None:
+            per_image[name] = own
+    return f

@@ -1,7 +1,9 @@
 """CPU: the torch restatement of the fused image loss (tests/loss_reference.py) is right -- its
 manual backward against float64 autograd, the separable form against the 2-D window -- the
 committed float32 spread is what a fresh measurement finds, and the loaded library refuses bad
-arguments before any HIP call (include/gsr.h)."""
+arguments before any HIP call (include/gsr.h).  At the end, the helpers of the seam tests
+(test_gpu_image_loss_seams.py): their cases, their measured spread, and the locality of the
+float64 restatement that the translation test rests on."""
 import ctypes
 
 import numpy as np
@@ -179,3 +181,96 @@ def test_python_refusals_need_no_device():
         photometric_loss(x, x.clone().requires_grad_(True))
     with pytest.raises(ValueError, match="lambda_dssim"):
         photometric_loss(x, x.clone(), lambda_dssim=1.5)
+
+
+# ---- the helpers of the seam tests (test_gpu_image_loss_seams.py) -------------------------------
+
+def test_seam_cases_are_the_issue_s():
+    images = L.seam_images()
+    assert [v[0].shape for v in images.values()] == [
+        (3, 33, 129), (2, 48, 192), (5, 100, 1000), (1, 1, 130), (1, 70, 1), (2, 5, 5),
+        (1, 11, 11), (1, 12, 12)]
+    assert list(images) == [L.shape_name(s) for s in L.SEAM_SHAPES]
+    for image, target in images.values():
+        assert image.dtype == target.dtype == np.float32 and image.shape == target.shape
+        assert 0.0 <= min(image.min(), target.min()) and max(image.max(), target.max()) <= 1.0
+        assert not (image == target).all()
+    # a tile with neighbours on all four sides: 3 x 3 tiles at least, with C > 1
+    th, tw = L.TILE_H, L.TILE_W
+    assert (33 - 1) // th == 2 and (129 - 1) // tw == 2 and L.blocks_of((3, 33, 129)) == 27
+    assert L.blocks_of(L.LOCALITY_SHAPE) == 2 * 3 * 3 and L.LOCALITY_SHAPE in L.SEAM_SHAPES
+    assert L.LOCALITY_PIXELS == ((0, 0), (47, 191), (15, 63), (16, 64), (16, 63), (24, 96))
+    # the translation pair: 4 x 4 tiles, crops of a quarter of its elements that fit
+    assert L.TRANSLATION_SHAPE == (2, 64, 256) and (L.CROP_H, L.CROP_W) == (32, 128)
+    assert L.TRANSLATION_OFFSETS == ((0, 0), (1, 1), (15, 63), (16, 64), (17, 65), (7, 100),
+                                     (32, 128))
+    pair = L.translation_pair()
+    for dy, dx in L.TRANSLATION_OFFSETS:
+        x, y = L.crop(pair, dy, dx)
+        assert x.shape == y.shape == (2, 32, 128) and x.flags.c_contiguous
+        assert 4 * x.size == pair[0].size and x[1, 3, 4] == pair[0][1, dy + 3, dx + 4]
+    # the integer images: block counts around the finish loop's trips, sums that stay exact
+    assert L.INTEGER_SHAPES == {(5, 100, 1000): 560, (1, 16, 16384): 256, (1, 16, 16385): 257,
+                                (2, 16, 16384): 512, (3, 17, 65): 12}
+    workspace = _lib.image_loss_fns(_lib.load_library())[0]
+    for shape, blocks in L.INTEGER_SHAPES.items():
+        assert L.blocks_of(shape) == blocks and workspace(*shape) == 8 * blocks
+        x, y = L.integer_images(shape)
+        assert x.dtype == y.dtype == np.float32 and x.shape == y.shape == shape
+        for a in (x, y):
+            assert (a == np.round(a)).all() and a.min() == 0.0 and a.max() == 8.0
+        S = int(np.abs(x.astype(np.int64) - y.astype(np.int64)).sum())
+        N = np.float64(x.size)
+        assert 0 < S < 1 << 22
+        q = [np.float32(np.float64(s) / N) for s in (S - 1, S, S + 1)]
+        assert q[0] < q[1] < q[2]  # a dropped or doubled unit of |x - y| changes the bits
+    assert L.outside_window(48, 192, 0, 0, 5).sum() == 48 * 192 - 36
+    assert L.outside_window(48, 192, 24, 96, 10).sum() == 48 * 192 - 441
+    assert L.pixel_err(np.array([1.0, 2.0, 4.0]), np.array([1.0, 2.0, 3.0])) == 1.0 / 5.0
+
+
+def test_committed_seam_spread_is_the_measured_one():
+    """SEAM_SPREAD is measured, not chosen: within a factor 2 of a fresh measurement."""
+    got = L.measure_seam_spread()
+    print("measured float32 seam spread:", got)
+    assert set(got) == set(L.SEAM_SPREAD) == {"max", "pixel"}
+    for kind in got:
+        assert set(got[kind]) == set(L.SEAM_SPREAD[kind]) == set(L.SAVED_NAMES) | {"dL_dimage"}
+        for k in L.SAVED_NAMES:
+            have, want = L.SEAM_SPREAD[kind][k], got[kind][k]
+            assert want / 2.0 <= have <= want * 2.0, (kind, k, have, want)
+        assert set(got[kind]["dL_dimage"]) == set(L.SEAM_LAMBDAS)
+        for lam in L.SEAM_LAMBDAS:
+            have, want = L.SEAM_SPREAD[kind]["dL_dimage"][lam], got[kind]["dL_dimage"][lam]
+            assert want / 2.0 <= have <= want * 2.0, (kind, "dL_dimage", lam, have, want)
+    # well conditioned: orders of magnitude below the spread that `near` and `dark` set
+    assert L.SEAM_SPREAD["max"]["dm_dmu1"] < 1e-3 * L.F32_SPREAD["dm_dmu1"]
+    assert L.SEAM_SPREAD["max"]["dL_dimage"][1.0] < 1e-2 * L.F32_SPREAD["dL_dimage"][1.0]
+
+
+def test_float64_restatement_is_local():
+    """The design of the GPU translation test, on the reference: a 32 x 128 crop of the 64 x 256
+    pair has the full pair's saved planes 5 pixels inside its border and 4 x its gradient (N is a
+    quarter) 10 pixels inside.  Bound 1e-13 of each entry's scale (pixel_err): measured 0.0 here
+    (conv2d adds the 121 taps in one order wherever the window sits); 1e-13 leaves room for a
+    backend that groups them differently -- a few hundred float64 roundings of 1.1e-16 -- and is
+    six orders below the float32 ulp that the GPU test turns on."""
+    pair = L.translation_pair()
+    worst = 0.0
+    for lam in L.SEAM_LAMBDAS:
+        full = L.evaluate(*pair, lam)
+        for dy, dx in L.TRANSLATION_OFFSETS:
+            part = L.evaluate(*L.crop(pair, dy, dx), lam)
+            a = part["saved"][:, :, 5:-5, 5:-5]
+            b = full["saved"][:, :, dy + 5:dy + L.CROP_H - 5, dx + 5:dx + L.CROP_W - 5]
+            assert a.shape == b.shape == (3, 2, 22, 118)
+            g = part["dL_dimage"][:, 10:-10, 10:-10]
+            h = 4.0 * full["dL_dimage"][:, dy + 10:dy + L.CROP_H - 10, dx + 10:dx + L.CROP_W - 10]
+            assert g.shape == h.shape == (2, 12, 108)
+            worst = max([worst, L.pixel_err(g, h)] + [L.pixel_err(a[i], b[i]) for i in range(3)])
+            # and it is the border that differs: the crop's edge rows see zero padding
+            if (dy, dx) != (0, 0):
+                assert rel_err(part["saved"][0][:, :5], full["saved"][0][:, dy:dy + 5,
+                                                                        dx:dx + L.CROP_W]) > 1e-3
+    print(f"float64 locality: worst per-pixel difference {worst:.3g}")
+    assert worst <= 1e-13
