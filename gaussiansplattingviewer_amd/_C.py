@@ -72,6 +72,12 @@ in place, no bias correction); `_C.fused_adam_step(params, grads, exp_avgs, exp_
 epss, mask, b1, b2, bc1, bc2_sqrt)` is `gsr_adam_step` on up to 8 groups in one launch (mask: bool
 or uint8 (P), int32 radii (P), or empty); `_C.densification_stats(radii, means2D_grad, grad_accum,
 denom, max_radii)` is `gsr_densify_stats`.  All three work in place on torch's current stream.
+Density control (`densify.densify_and_prune`): `_C.densify_plan(grad_accum, denom, max_radii,
+scaling, opacity, thresholds, radius_threshold, scale_space, workspace, counts)` is
+`gsr_densify_plan` and `_C.densify_apply(<the same first eight>, seed, roles, has_moments,
+src_params, src_exp_avgs, src_exp_avg_sqs, dst_params, dst_exp_avgs, dst_exp_avg_sqs, workspace,
+source_index)` is `gsr_densify_apply`; the caller allocates every tensor, P_out is source_index's
+length, and a group with has_moments 0 passes any tensors in the moments' places.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -80,7 +86,7 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, adamUpdate, densification_stats,  # noqa: F401
-                          fused_adam_step, fused_image_loss, fused_image_loss_backward,
+                          densify_apply, densify_plan, fused_adam_step, fused_image_loss, fused_image_loss_backward,
                           mark_visible, rasterize_gaussians,
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,

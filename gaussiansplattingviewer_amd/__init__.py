@@ -18,6 +18,7 @@ from .camera import Camera, cuda_camera_inputs, look_at, orbit_eye, static_camer
 from .strips import strip_rows, render_strips
 from .losses import photometric_loss, ssim
 from .optim import SparseGaussianAdam, densification_stats
+from .densify import DensifyCounts, DensifyResult, densify_and_prune
 
 __all__ = [
     "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
@@ -26,5 +27,5 @@ __all__ = [
     "depth_argsort", "GaussianData", "naive_gaussian", "synthetic_gaussians", "Camera",
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
     "render_strips", "photometric_loss", "ssim", "SparseGaussianAdam",
-    "densification_stats",
+    "densification_stats", "densify_and_prune", "DensifyResult", "DensifyCounts",
 ]

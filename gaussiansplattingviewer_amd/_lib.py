@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
     "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
     "gsr_adam_step", "gsr_densify_stats",
+    "gsr_densify_workspace", "gsr_densify_plan", "gsr_densify_apply",
 )
 
 GSR_PACK_RGBA_F32 = 0
@@ -176,6 +177,32 @@ class GsrDensifyInputs(ctypes.Structure):
                 ("denom", ctypes.c_void_p), ("max_radii", ctypes.c_void_p)]
 
 
+# gsr_densify_group's `role` and gsr_densify_plan_inputs' `scale_space` (include/gsr.h)
+GSR_ROLE_NONE, GSR_ROLE_XYZ, GSR_ROLE_SCALING, GSR_ROLE_ROTATION, GSR_ROLE_OPACITY = range(5)
+GSR_SCALE_LINEAR, GSR_SCALE_LOG = 0, 1
+SPLIT_CHILDREN = 2  # GSR_SPLIT_CHILDREN
+
+
+class GsrDensifyGroup(ctypes.Structure):
+    """gsr_densify_group: one [rows, M] tensor of gsr_densify_apply, with both moments or neither."""
+    _fields_ = [("M", ctypes.c_int32), ("role", ctypes.c_int32), ("param", ctypes.c_void_p),
+                ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p)]
+
+
+class GsrDensifyPlanInputs(ctypes.Structure):
+    """gsr_densify_plan_inputs: the statistics, the thresholds (in the tensors' stored space), the
+    seed and the two tensors the classification reads; P_out and n_groups are the apply's."""
+    _fields_ = [("P", ctypes.c_int64), ("P_out", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("n_groups", ctypes.c_int32), ("scale_space", ctypes.c_int32),
+                ("grad_threshold", ctypes.c_float), ("scale_split_threshold", ctypes.c_float),
+                ("opacity_prune_threshold", ctypes.c_float),
+                ("scale_prune_threshold", ctypes.c_float),
+                ("radius_prune_threshold", ctypes.c_int32),
+                ("grad_accum", ctypes.c_void_p), ("denom", ctypes.c_void_p),
+                ("max_radii", ctypes.c_void_p), ("scaling", ctypes.c_void_p),
+                ("opacity", ctypes.c_void_p)]
+
+
 class GsrPlyInfo(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32), ("binary", ctypes.c_int32),
@@ -247,6 +274,15 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_adam_step.restype = i32
         lib.gsr_densify_stats.argtypes = [ctypes.POINTER(GsrDensifyInputs), vp]
         lib.gsr_densify_stats.restype = i32
+    if hasattr(lib, "gsr_densify_plan"):
+        plan_in = ctypes.POINTER(GsrDensifyPlanInputs)
+        lib.gsr_densify_workspace.argtypes = [i64]
+        lib.gsr_densify_workspace.restype = i64
+        lib.gsr_densify_plan.argtypes = [plan_in, vp, vp, vp]
+        lib.gsr_densify_plan.restype = i32
+        lib.gsr_densify_apply.argtypes = [plan_in, ctypes.POINTER(GsrDensifyGroup),
+                                          ctypes.POINTER(GsrDensifyGroup), vp, vp, vp]
+        lib.gsr_densify_apply.restype = i32
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
@@ -371,6 +407,13 @@ def optimizer_fns(lib: ctypes.CDLL):
     not have them."""
     return _optional_fn(lib, "gsr_adam_step / gsr_densify_stats",
                         "the fused Adam step and the densification statistics need")
+
+
+def densify_fns(lib: ctypes.CDLL):
+    """(gsr_densify_workspace, gsr_densify_plan, gsr_densify_apply) of a loaded library;
+    RuntimeError if that build does not have them."""
+    return _optional_fn(lib, "gsr_densify_workspace / gsr_densify_plan / gsr_densify_apply",
+                        "densify-and-prune needs")
 
 
 def check(rc: int, what: str) -> int:

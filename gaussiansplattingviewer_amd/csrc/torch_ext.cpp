@@ -85,6 +85,15 @@
 //   _C.densification_stats(radii, means2D_grad, grad_accum, denom, max_radii)
 //     gsr_densify_stats, upstream's add_densification_stats in place; max_radii int32 [P] or
 //     empty.  None of the three uses a context.
+//   _C.densify_plan(grad_accum, denom, max_radii, scaling, opacity, thresholds, radius_threshold,
+//                   scale_space, workspace, counts)
+//     gsr_densify_plan into the caller's int32 workspace and counts [4]; thresholds = (grad, scale
+//     split, opacity prune, scale prune) in the tensors' stored space, max_radii int32 [P] or empty.
+//   _C.densify_apply(<the same first eight>, seed, roles, has_moments, src_params, src_exp_avgs,
+//                    src_exp_avg_sqs, dst_params, dst_exp_avgs, dst_exp_avg_sqs, workspace,
+//                    source_index)
+//     gsr_densify_apply into the caller's dst tensors [P_out, M_i] and source_index [P_out]
+//     (int32; its length is P_out).  No context, no allocation, no synchronisation.
 #include <torch/extension.h>
 
 #include <c10/hip/HIPGuard.h>
@@ -770,6 +779,128 @@ void densification_stats(const torch::Tensor &radii, const torch::Tensor &means2
     TORCH_CHECK(rc == GSR_OK, "gsr_densify_stats failed (", rc, "): ", gsr_last_error());
 }
 
+// gsr_densify_plan_inputs of both densify entries: the statistics and the two tensors the
+// classification reads (checked), thresholds = (grad, scale split, opacity prune, scale prune) as
+// float32 values held in doubles.
+gsr_densify_plan_inputs densify_inputs(const torch::Tensor &grad_accum, const torch::Tensor &denom,
+                                       const torch::Tensor &max_radii,
+                                       const torch::Tensor &scaling, const torch::Tensor &opacity,
+                                       const std::vector<double> &thresholds,
+                                       int64_t radius_threshold, int64_t scale_space,
+                                       uint64_t seed) {
+    TORCH_CHECK(scaling.defined() && scaling.is_cuda(), "scaling must be a device (HIP) tensor");
+    TORCH_CHECK(scaling.dim() >= 1, "scaling must be [P, 3]");
+    TORCH_CHECK(thresholds.size() == 4, "thresholds: grad, scale split, opacity prune, scale prune");
+    const torch::Device dev = scaling.device();
+    const int64_t P = scaling.size(0);
+    gsr_densify_plan_inputs in{};
+    in.P = P;
+    in.seed = seed;
+    in.scale_space = (int32_t)scale_space;
+    in.grad_threshold = (float)thresholds[0];
+    in.scale_split_threshold = (float)thresholds[1];
+    in.opacity_prune_threshold = (float)thresholds[2];
+    in.scale_prune_threshold = (float)thresholds[3];
+    in.radius_prune_threshold = (int32_t)std::min<int64_t>(radius_threshold, INT32_MAX);
+    in.grad_accum = adam_buffer(grad_accum, dev, P, "grad_accum");
+    in.denom = adam_buffer(denom, dev, P, "denom");
+    in.scaling = adam_buffer(scaling, dev, 3 * P, "scaling");
+    in.opacity = adam_buffer(opacity, dev, P, "opacity");
+    if (max_radii.defined() && max_radii.numel() != 0) {
+        TORCH_CHECK(max_radii.is_cuda() && max_radii.device() == dev &&
+                        max_radii.scalar_type() == torch::kInt32 && max_radii.is_contiguous() &&
+                        max_radii.numel() == P,
+                    "max_radii must be a contiguous int32 tensor of ", P, " values on scaling's device");
+        in.max_radii = max_radii.data_ptr<int32_t>();
+    }
+    return in;
+}
+
+void *densify_workspace(const torch::Tensor &workspace, const torch::Device &dev, int64_t P) {
+    const int64_t bytes = gsr_densify_workspace(P);
+    TORCH_CHECK(bytes >= 0, "gsr_densify_workspace failed (", bytes, "): ", gsr_last_error());
+    TORCH_CHECK(workspace.defined() && workspace.is_cuda() && workspace.device() == dev &&
+                    workspace.is_contiguous() && workspace.scalar_type() == torch::kInt32 &&
+                    workspace.numel() * 4 >= bytes,
+                "workspace must be a contiguous int32 device tensor of at least ", bytes, " bytes");
+    return workspace.data_ptr();
+}
+
+void densify_plan(const torch::Tensor &grad_accum, const torch::Tensor &denom,
+                  const torch::Tensor &max_radii, const torch::Tensor &scaling,
+                  const torch::Tensor &opacity, const std::vector<double> &thresholds,
+                  int64_t radius_threshold, int64_t scale_space, torch::Tensor &workspace,
+                  torch::Tensor &counts) {
+    const gsr_densify_plan_inputs in = densify_inputs(grad_accum, denom, max_radii, scaling, opacity,
+                                                      thresholds, radius_threshold, scale_space, 0);
+    const torch::Device dev = scaling.device();
+    void *ws = densify_workspace(workspace, dev, in.P);
+    TORCH_CHECK(counts.defined() && counts.is_cuda() && counts.device() == dev &&
+                    counts.scalar_type() == torch::kInt32 && counts.is_contiguous() &&
+                    counts.numel() == 4,
+                "counts must be a contiguous int32 device tensor of 4 values");
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_densify_plan(&in, ws, counts.data_ptr<int32_t>(), st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_densify_plan failed (", rc, "): ", gsr_last_error());
+}
+
+void densify_apply(const torch::Tensor &grad_accum, const torch::Tensor &denom,
+                   const torch::Tensor &max_radii, const torch::Tensor &scaling,
+                   const torch::Tensor &opacity, const std::vector<double> &thresholds,
+                   int64_t radius_threshold, int64_t scale_space, uint64_t seed,
+                   const std::vector<int64_t> &roles, const std::vector<int64_t> &has_moments,
+                   const std::vector<torch::Tensor> &src_params,
+                   const std::vector<torch::Tensor> &src_exp_avgs,
+                   const std::vector<torch::Tensor> &src_exp_avg_sqs,
+                   const std::vector<torch::Tensor> &dst_params,
+                   const std::vector<torch::Tensor> &dst_exp_avgs,
+                   const std::vector<torch::Tensor> &dst_exp_avg_sqs,
+                   const torch::Tensor &workspace, torch::Tensor &source_index) {
+    gsr_densify_plan_inputs in = densify_inputs(grad_accum, denom, max_radii, scaling, opacity,
+                                                thresholds, radius_threshold, scale_space, seed);
+    const torch::Device dev = scaling.device();
+    const size_t n = src_params.size();
+    TORCH_CHECK(n >= 1 && n <= GSR_MAX_PARAM_GROUPS, "1..", GSR_MAX_PARAM_GROUPS,
+                " parameter groups per call, got ", n);
+    TORCH_CHECK(roles.size() == n && has_moments.size() == n && src_exp_avgs.size() == n && src_exp_avg_sqs.size() == n &&
+                    dst_params.size() == n && dst_exp_avgs.size() == n &&
+                    dst_exp_avg_sqs.size() == n,
+                "roles, has_moments and the six tensor lists must have one length");
+    TORCH_CHECK(source_index.defined() && source_index.is_cuda() && source_index.device() == dev &&
+                    source_index.scalar_type() == torch::kInt32 && source_index.is_contiguous(),
+                "source_index must be a contiguous int32 device tensor");
+    const int64_t P = in.P, Pout = source_index.numel();
+    in.P_out = Pout;
+    in.n_groups = (int32_t)n;
+    gsr_densify_group src[GSR_MAX_PARAM_GROUPS] = {}, dst[GSR_MAX_PARAM_GROUPS] = {};
+    // a group without moments (has_moments 0) passes any tensors in their places: NULL
+    auto moment = [&](size_t i, const torch::Tensor &t, int64_t numel, const char *name) {
+        return has_moments[i] ? adam_buffer(t, dev, numel, name) : nullptr;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const torch::Tensor &p = src_params[i], &q = dst_params[i];
+        TORCH_CHECK(p.defined() && p.dim() >= 1 && p.size(0) == P && q.defined() && q.dim() >= 1 &&
+                        q.size(0) == Pout,
+                    "a source's first dimension must be ", P, ", a destination's ", Pout);
+        const int64_t M = P > 0 ? p.numel() / P : (Pout > 0 ? q.numel() / Pout : 1);
+        TORCH_CHECK(M >= 1 && M < ((int64_t)1 << 31), "a parameter row of ", M, " floats");
+        src[i].M = dst[i].M = (int32_t)M;
+        src[i].role = dst[i].role = (int32_t)roles[i];
+        src[i].param = adam_buffer(p, dev, P * M, "a source parameter");
+        dst[i].param = adam_buffer(q, dev, Pout * M, "a destination parameter");
+        src[i].exp_avg = moment(i, src_exp_avgs[i], P * M, "a source exp_avg");
+        src[i].exp_avg_sq = moment(i, src_exp_avg_sqs[i], P * M, "a source exp_avg_sq");
+        dst[i].exp_avg = moment(i, dst_exp_avgs[i], Pout * M, "a destination exp_avg");
+        dst[i].exp_avg_sq = moment(i, dst_exp_avg_sqs[i], Pout * M, "a destination exp_avg_sq");
+    }
+    const void *ws = densify_workspace(workspace, dev, P);
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_densify_apply(&in, src, dst, ws, source_index.data_ptr<int32_t>(), st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_densify_apply failed (", rc, "): ", gsr_last_error());
+}
+
 void release_contexts() {
     std::lock_guard<std::mutex> lk(g_lock);
     for (gsr_context *&c : g_ctx) {
@@ -851,6 +982,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("densification_stats", &densification_stats,
           "radii (P) int32, means2D_grad (P, 3), grad_accum (P), denom (P), max_radii (P) int32 "
           "or empty: gsr_densify_stats, in place");
+    m.def("densify_plan", &densify_plan,
+          "grad_accum, denom, max_radii (int32 (P) or empty), scaling, opacity, thresholds (grad, "
+          "scale split, opacity prune, scale prune), radius_threshold, scale_space, workspace "
+          "(int32), counts (int32 (4)): gsr_densify_plan, into workspace and counts");
+    m.def("densify_apply", &densify_apply,
+          "the plan's first eight arguments, seed, roles, has_moments, src params / exp_avgs / "
+          "exp_avg_sqs, dst params / exp_avgs / exp_avg_sqs, workspace, source_index (int32 "
+          "(P_out)): gsr_densify_apply, into the dst tensors and source_index");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(
         "context_handle",

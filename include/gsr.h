@@ -768,6 +768,118 @@ typedef struct gsr_densify_inputs {
 } gsr_densify_inputs;
 int gsr_densify_stats(const gsr_densify_inputs *in, void *stream);
 
+/* ---- Adaptive density control: clone, split and prune a fitted scene ---- (additive to ABI 4;
+ * DESIGN.md §3p)
+ *
+ * Upstream's densify_and_prune (densify_and_clone, densify_and_split with N = 2, prune_points) on
+ * up to GSR_MAX_PARAM_GROUPS parameter tensors [P, M_i] and their Adam moments, as a plan (classify
+ * every row, scan, four counts) and an apply (write the P' output rows into the caller's new
+ * buffers).  The caller reads the counts between the two: it must size the outputs.
+ *
+ * Four groups carry a role: xyz (M = 3), scaling (M = 3), rotation (M = 4, (r, x, y, z), not
+ * normalised) and opacity (M = 1); all others are only copied.  Every threshold is in the space
+ * the tensors are STORED in (scale_space says whether the scaling words are sigma or log sigma;
+ * the opacity threshold is compared with the stored opacity word), so a row is classified by
+ * comparisons of stored words alone.
+ *
+ * Per source row i, from row i alone, in float32, with a correctly rounded divide:
+ *   avg   = grad_accum[i] / denom[i], NaN -> 0.0f        hot = avg >= grad_threshold
+ *   smax  = fmaxf(fmaxf(s0, s1), s2) of the stored scaling words
+ *   clone = hot && smax <= scale_split_threshold
+ *   split = hot && smax >  scale_split_threshold
+ *   pruned(o, s, r) = o < opacity_prune_threshold || s > scale_prune_threshold ||
+ *                     r > radius_prune_threshold      (the last only with max_radii and a
+ *                                                      threshold > 0; +inf switches the second off)
+ * A row that is not split survives iff !pruned(opacity, smax, max_radii[i]); its clone survives
+ * with it (same words, same decision).  A split row's source always goes; its GSR_SPLIT_CHILDREN
+ * children survive iff !pruned(opacity, child(smax), max_radii[i]) -- the child's scaling, the
+ * source's opacity and radius; both children share the decision.
+ * Deviation from upstream: upstream zeroes max_radii2D (densification_postfix) before its
+ * screen-size test reads it, so that test never fires there.  Here the test reads the caller's
+ * values as they are; radius_prune_threshold <= 0 or a NULL max_radii gives upstream's behaviour.
+ *
+ * Output order, upstream's: the surviving unsplit sources in source order, then the surviving
+ * clones in source order, then child 0 of every surviving split source in source order, then
+ * child 1 likewise.  counts = (n_kept, n_clone, n_split, n_removed): n_split counts the split
+ * sources whose children survive, n_removed the source rows of which nothing is left, so
+ * P = n_kept + n_split + n_removed and P' = n_kept + n_clone + 2 n_split <= 2 P.
+ *
+ * Rows: a kept row copies every parameter and both moments bit for bit.  A clone and a child copy
+ * every parameter of the source and get zero moments; two tensors of a child differ:
+ *   scaling  s - c in log space with c = (float)log(1.6) = 0x3EF0A451, s / 1.6f in linear
+ *            space: one float operation per word
+ *   xyz      with q = rotation / sqrtf(((r r + x x) + y y) + z z), R = upstream's build_rotation
+ *              R00 = 1 - 2 (y y + z z)  R01 = 2 (x y - r z)      R02 = 2 (x z + r y)
+ *              R10 = 2 (x y + r z)      R11 = 1 - 2 (x x + z z)  R12 = 2 (y z - r x)
+ *              R20 = 2 (x z - r y)      R21 = 2 (y z + r x)      R22 = 1 - 2 (x x + y y)
+ *            sigma = the SOURCE's stored scaling (expf of it in log space), v = sigma * z,
+ *            xyz_k = ((Rk0 v0 + Rk1 v1) + Rk2 v2) + xyz_k(source), without FMA contraction
+ *   z        from Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl 0x9E3779B9,
+ *            0xBB67AE85), key (seed low word, seed high word), counter (i, child, 0, 0), output
+ *            words x0..x3:  u_k = ((float)(x_k >> 8) + 0.5f) * 2^-24  (one rounded add: in (0, 1])
+ *              z0 = sqrtf(-2.0f * logf(u0)) * cosf(6.2831855f * u1)
+ *              z1 = sqrtf(-2.0f * logf(u0)) * sinf(6.2831855f * u1)
+ *              z2 = sqrtf(-2.0f * logf(u2)) * cosf(6.2831855f * u3)
+ * A sample is a function of (seed, source row, child) alone, never of the launch geometry, the
+ * stream or what ran before.  source_index[P'] gets the source row of every output row (for state
+ * that is not in these tensors).  Of a row of which nothing survives only the scaling, the opacity
+ * and the statistics are read; of a split source, no moment: a NaN elsewhere reaches nothing.
+ *
+ * Stateless like gsr_adam_step: no context, no allocation, no atomics, no synchronisation; all
+ * memory is the caller's, all work is enqueued on `stream`.  The scan is over integers, so every
+ * output has the same bits on every call with the same inputs.  `workspace` holds
+ * gsr_densify_workspace(P) bytes (4-byte aligned), written by the plan and read by the apply of the
+ * same `in`; counts_dev is four int32 on the device.  gsr_densify_apply takes in->P_out = P' (the
+ * plan ignores it); its kernels bound every write by P_out and every read by P, whatever the
+ * workspace holds.  src_groups and dst_groups are host arrays of in->n_groups entries, [P, M] and
+ * [P_out, M]; a group has both moments or neither, the same in both arrays.
+ *
+ * Refused with GSR_E_INVALID before any HIP call, nothing written: a NULL in, workspace,
+ * counts_dev, src_groups or dst_groups; P < 0 or P >= 2^30 (gsr_densify_workspace returns
+ * GSR_E_INVALID for those); n_groups outside 1..GSR_MAX_PARAM_GROUPS; an M < 1, or a role with the
+ * wrong M, an unknown role, a missing or duplicated role; one moment NULL and the other not, or
+ * moments in one of src / dst only (a destination of P_out == 0 rows may be all NULL); a NULL grad_accum, denom, scaling or opacity, or a NULL
+ * source buffer, with P > 0; the scaling or opacity role at another address than in->scaling /
+ * in->opacity; a NULL destination buffer or source_index with P_out > 0; a NaN threshold; a
+ * scale_space that is neither; P_out < 0, P_out > 2 P; sizes beyond 2^31 - 1 blocks.
+ * P_out == 0 (so also P == 0) is GSR_OK without a launch of the apply step; the plan of P == 0
+ * writes four zeros. */
+#define GSR_SPLIT_CHILDREN 2
+enum { GSR_ROLE_NONE = 0, GSR_ROLE_XYZ = 1, GSR_ROLE_SCALING = 2, GSR_ROLE_ROTATION = 3,
+       GSR_ROLE_OPACITY = 4 };
+enum { GSR_SCALE_LINEAR = 0, GSR_SCALE_LOG = 1 };
+typedef struct gsr_densify_group {
+    int32_t M;            /* floats per row, >= 1 */
+    int32_t role;         /* GSR_ROLE_* */
+    float *param;         /* [rows, M] contiguous float32; 4-byte alignment is enough */
+    float *exp_avg;       /* [rows, M], or NULL with exp_avg_sq for a tensor without moments */
+    float *exp_avg_sq;
+} gsr_densify_group;
+typedef struct gsr_densify_plan_inputs {
+    int64_t P;                     /* source rows, 0 <= P < 2^30 */
+    int64_t P_out;                 /* P', gsr_densify_apply only */
+    uint64_t seed;
+    int32_t n_groups;              /* 1..GSR_MAX_PARAM_GROUPS, gsr_densify_apply only */
+    int32_t scale_space;           /* GSR_SCALE_LINEAR or GSR_SCALE_LOG */
+    float grad_threshold;
+    float scale_split_threshold;
+    float opacity_prune_threshold;
+    float scale_prune_threshold;   /* +inf = off */
+    int32_t radius_prune_threshold; /* <= 0 = off */
+    const float *grad_accum;       /* [P] */
+    const float *denom;            /* [P] */
+    const int32_t *max_radii;      /* [P], or NULL = the radius test off */
+    const float *scaling;          /* [P, 3], the scaling role's source buffer */
+    const float *opacity;          /* [P], the opacity role's source buffer */
+} gsr_densify_plan_inputs;
+int64_t gsr_densify_workspace(int64_t P);
+int gsr_densify_plan(const gsr_densify_plan_inputs *in, void *workspace,
+                     int32_t *counts_dev /* [4] device */, void *stream);
+int gsr_densify_apply(const gsr_densify_plan_inputs *in,
+                      const gsr_densify_group *src_groups /* host */,
+                      const gsr_densify_group *dst_groups /* host */, const void *workspace,
+                      int32_t *source_index /* [P_out] device */, void *stream);
+
 /* Stage timing (HIP events on the forward's stream, no extra synchronisation).
  * gsr_set_timing(1) starts recording one event set per forward (a ring of the last 256);
  * gsr_stage_times waits for the last timed forward and writes the MEAN per-stage time (ms)
