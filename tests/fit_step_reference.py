@@ -251,29 +251,31 @@ def _adam(p, m, v2, names, lrs, rows):
             p[k].copy_(torch.where(sel, p1, p[k]))
 
 
-def densify_thresholds(parametrisation):
+def densify_thresholds(parametrisation, control=None):
     """((grad, scale split, opacity prune, scale prune), radius) in the stored space, and whether
-    that space is log space."""
+    that space is log space.  control: another fit's thresholds (default CONTROL's)."""
     from gaussiansplattingviewer_amd import densify
     activated = parametrisation == "activated"
-    thresholds, radius = densify.stored_thresholds(activated=activated, **CONTROL[parametrisation])
+    thresholds, radius = densify.stored_thresholds(activated=activated,
+                                                   **(control or CONTROL[parametrisation]))
     return thresholds, radius, not activated
 
 
-def _densify(parametrisation, p, m, v2, stats):
+def _densify(parametrisation, p, m, v2, stats, control=None, seed=None):
     """tests/densify_reference.py on the float32 roundings of the fit's state -> the new state in
-    the fit's dtype, and the counts."""
+    the fit's dtype, and the counts.  control, seed: another fit's (default CONTROL's and
+    DENSIFY_SEED)."""
     names = GROUPS[parametrisation]
     role_of = {v: k for k, v in ROLES[parametrisation].items()}
     f32 = lambda t: np.ascontiguousarray(t.detach().to(torch.float32).numpy())  # noqa: E731
     groups = [dict(name=k, role=role_of.get(k), p=f32(p[k]), m=f32(m[k]), v=f32(v2[k]))
               for k in names]
-    thresholds, radius, log_space = densify_thresholds(parametrisation)
+    thresholds, radius, log_space = densify_thresholds(parametrisation, control)
     before = dict(accum=stats[0].astype(F32), denom=stats[1].astype(F32), max_radii=stats[2].copy(),
                   scaling=groups[names.index(ROLES[parametrisation]["scaling"])]["p"].copy(),
                   opacity=groups[names.index(ROLES[parametrisation]["opacity"])]["p"].copy())
     r = D.densify(groups, before["accum"], before["denom"], before["max_radii"], thresholds, radius,
-                  log_space, DENSIFY_SEED)
+                  log_space, DENSIFY_SEED if seed is None else seed)
     dt = p[names[0]].dtype
     new = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=dt)  # noqa: E731
     p1 = {k: new(g["p"]).requires_grad_(True) for k, g in zip(names, r["groups"])}
@@ -345,11 +347,12 @@ def trajectory(parametrisation):
     return _TRAJECTORY[parametrisation]
 
 
-def densify_margins(parametrisation, before=None):
+def densify_margins(parametrisation, before=None, control=None):
     """The smallest relative distance of a statistic from its threshold, per test, in linear
-    units, on the reference's state before the densify (or a given one of that layout)."""
+    units, on the reference's state before the densify (or a given one of that layout, under
+    given thresholds)."""
     b = before or trajectory(parametrisation)["before_densify"]
-    ctl = CONTROL[parametrisation]
+    ctl = control or CONTROL[parametrisation]
     scaling, opacity = b["scaling"].astype(np.float64), b["opacity"].astype(np.float64).reshape(-1)
     if parametrisation == "stored":
         scaling, opacity = np.exp(scaling), 1.0 / (1.0 + np.exp(-opacity))
@@ -420,6 +423,7 @@ def chain_keys(parametrisation):
 
 
 def chain_f(parametrisation, key, table=None):
+    """table: JOINT_SPREAD, or another fit's table of either kind (default CHAIN_SPREAD)."""
     f = (CHAIN_SPREAD if table is None else table)[parametrisation][key]
     return max(f, gr.F32_SPREAD[SAME_TENSOR[key]]) if key in SAME_TENSOR else f
 
@@ -532,12 +536,13 @@ def check_loss(state, ref):
              L.BOUND_FACTOR * L.F32_SPREAD["loss"][LAMBDA])]
 
 
-def check_chain(state, ref, parametrisation):
+def check_chain(state, ref, parametrisation, table=None):
     """(c): every gradient against J64^T dL64(color of the state), rel_err per tensor within
-    BOUND_FACTOR x f."""
+    BOUND_FACTOR x f (of `table`, default CHAIN_SPREAD)."""
     return [(f"grad {k}", gr.rel_err(np.asarray(state["grads"][k]).reshape(ref["grads"][k].shape),
                                      ref["grads"][k]),
-             gr.BOUND_FACTOR * chain_f(parametrisation, k)) for k in chain_keys(parametrisation)]
+             gr.BOUND_FACTOR * chain_f(parametrisation, k, table))
+            for k in chain_keys(parametrisation)]
 
 
 def check_loss_gradient(state, ref):
@@ -547,14 +552,14 @@ def check_loss_gradient(state, ref):
              L.BOUND_FACTOR * L.F32_SPREAD["dL_dimage"][LAMBDA])]
 
 
-def check_joint(state, ref, parametrisation):
+def check_joint(state, ref, parametrisation, table=None):
     """Every gradient against J64^T (the state's own dL): the rasterizer's backward and the
     activations as they received the loss gradient, within BOUND_FACTOR x the spread measured
     with one dL on both sides -- several times tighter than check_chain, whose bound has to
     admit the float32 loss gradient's rounding."""
     return [(f"joint {k}", gr.rel_err(np.asarray(state["grads"][k]).reshape(ref["joint"][k].shape),
                                       ref["joint"][k]),
-             gr.BOUND_FACTOR * chain_f(parametrisation, k, JOINT_SPREAD))
+             gr.BOUND_FACTOR * chain_f(parametrisation, k, table or JOINT_SPREAD))
             for k in chain_keys(parametrisation)]
 
 
@@ -566,15 +571,17 @@ def _words(a, b):
     return float((a.view(np.uint32) != b.view(np.uint32)).sum())
 
 
-def check_adam(state, parametrisation):
+def check_adam(state, parametrisation, lrs=None):
     """(d): parameters and both moments after the step are optimizer_reference.adam_step of the
-    state's own parameters, moments and gradients, rows by radii > 0, bit for bit."""
+    state's own parameters, moments and gradients, rows by radii > 0, bit for bit.  lrs: another
+    fit's learning rates by group (default GROUP_LRS's)."""
+    lrs = lrs or GROUP_LRS[parametrisation]
     rows_on = O.row_mask(len(state["radii"]), radii=state["radii"])
     rows = []
     for k in GROUPS[parametrisation]:
         g = np.asarray(state["grads"][k], F32).reshape(state["params"][k].shape)
         p1, m1, v1 = O.adam_step(state["params"][k], g, state["m"][k], state["v"][k],
-                                 GROUP_LRS[parametrisation][k], EPS, BETAS[0], BETAS[1], rows=rows_on)
+                                 lrs[k], EPS, BETAS[0], BETAS[1], rows=rows_on)
         rows += [(f"adam param {k}", _words(state["params1"][k], p1), 0.0),
                  (f"adam exp_avg {k}", _words(state["m1"][k], m1), 0.0),
                  (f"adam exp_avg_sq {k}", _words(state["v1"][k], v1), 0.0)]
@@ -595,16 +602,16 @@ def check_stats(state):
             ("max_radii", _words(state["stats1"][2], r1), 0.0)]
 
 
-def check_all(sc, state, parametrisation, lists, radii, ref=None):
+def check_all(sc, state, parametrisation, lists, radii, ref=None, tables=(None, None), lrs=None):
     """-> (check name -> rows, ref); "chain" and "joint" are None where the reference is near a
-    gate."""
+    gate.  tables, lrs: another fit's (chain spread, joint spread) and learning rates."""
     ref = ref or reference_of(sc, state, lists, radii)
     clear = ref["near"] == (0, 0)
     return dict(forward=check_forward(state, ref), loss=check_loss(state, ref),
                 loss_gradient=check_loss_gradient(state, ref),
-                chain=check_chain(state, ref, parametrisation) if clear else None,
-                joint=check_joint(state, ref, parametrisation) if clear else None,
-                adam=check_adam(state, parametrisation), stats=check_stats(state)), ref
+                chain=check_chain(state, ref, parametrisation, tables[0]) if clear else None,
+                joint=check_joint(state, ref, parametrisation, tables[1]) if clear else None,
+                adam=check_adam(state, parametrisation, lrs), stats=check_stats(state)), ref
 
 
 # ---- a float32 restatement of one iteration, and its mutants -----------------------------------------
