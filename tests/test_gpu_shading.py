@@ -18,6 +18,7 @@ from gaussiansplattingviewer_amd.rasterizer import binning_state, rasterize_gaus
 from gaussiansplattingviewer_amd.renderer import HIPRenderer
 from gaussiansplattingviewer_amd.strips import strip_pixel_rows
 
+import pose_scenes
 import shading_reference as sr
 import shading_scenes as ss
 from gpu_helpers import set_option, to_dev
@@ -156,6 +157,26 @@ def test_shading_on_scene(gpu, oracle_mod, scenes, name):
     finally:
         set_option(gpu, _lib.GSR_OPT_BLEND_FAST, 1)
         set_option(gpu, _lib.GSR_OPT_BLEND_CULL, 1)
+
+
+@pytest.mark.parametrize("shading", (sr.BILLBOARD, sr.GAUSS_BALL), ids=("billboard", "ball"))
+def test_shading_at_the_oblique_pose(gpu, oracle_mod, shading):
+    """`mixed` seen from pose_scenes' oblique camera (a dense view rotation; every scene above
+    looks through the static camera): one billboard and one ball frame against the same reference
+    -- it reads the 2D records, whatever view made them -- under the same bounds."""
+    sc = dict(ss.build(oracle_mod, "mixed"))
+    view, proj, campos, tx, ty = pose_scenes.camera_inputs(sc["W"], sc["H"], "oblique")
+    sc["s"] = dict(sc["s"], view=view, proj=proj, campos=campos, tx=tx, ty=ty)
+    orc = ss.run(oracle_mod, sc)
+    ref = sr.reference(sc, orc, shading)
+    assert 0.2 <= float((ref["n_contrib"] > 0).mean()) < 1.0 and ref["stable"].mean() >= 0.95
+    hip = _render(sc, gpu, shading, binning=True)
+    assert hip["num_rendered"] == orc["num_rendered"] > 0
+    np.testing.assert_array_equal(hip["point_list"], orc["point_list"])
+    np.testing.assert_array_equal(hip["ranges"], orc["ranges"])
+    for k in ("means2D", "conic_opacity"):
+        np.testing.assert_array_equal(hip[k].view(np.uint32), orc[k].view(np.uint32))
+    _check_against_reference(hip, sc, orc, ref, shading, f"mixed@oblique shading {shading}")
 
 
 def test_splat_shading_is_gsr_forward_and_unknown_shadings_are_invalid(gpu, scenes):
