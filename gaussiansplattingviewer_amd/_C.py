@@ -78,6 +78,9 @@ scaling, opacity, thresholds, radius_threshold, scale_space, workspace, counts)`
 src_params, src_exp_avgs, src_exp_avg_sqs, dst_params, dst_exp_avgs, dst_exp_avg_sqs, workspace,
 source_index)` is `gsr_densify_apply`; the caller allocates every tensor, P_out is source_index's
 length, and a group with has_moments 0 passes any tensors in the moments' places.
+The start of a fit (`pointcloud.knn_mean_dist2`): `_C.distCUDA2(points)` has the signature of
+upstream's `simple_knn._C.distCUDA2` -- points (N, 3) -> (N,) the mean squared distance to the
+three nearest neighbours -- and is `gsr_knn_mean_dist2` on torch's current stream.
 
 No fallback: importing this module fails when `_native.so` is not built
 (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -86,7 +89,7 @@ from __future__ import annotations
 
 try:
     from ._native import (abi_version, adamUpdate, densification_stats,  # noqa: F401
-                          densify_apply, densify_plan, fused_adam_step, fused_image_loss, fused_image_loss_backward,
+                          densify_apply, densify_plan, distCUDA2, fused_adam_step, fused_image_loss, fused_image_loss_backward,
                           mark_visible, rasterize_gaussians,
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,

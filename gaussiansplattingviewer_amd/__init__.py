@@ -19,6 +19,7 @@ from .strips import strip_rows, render_strips
 from .losses import photometric_loss, ssim
 from .optim import SparseGaussianAdam, densification_stats
 from .densify import DensifyCounts, DensifyResult, densify_and_prune
+from .pointcloud import knn_mean_dist2, scene_from_point_cloud
 
 __all__ = [
     "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
@@ -28,4 +29,5 @@ __all__ = [
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
     "render_strips", "photometric_loss", "ssim", "SparseGaussianAdam",
     "densification_stats", "densify_and_prune", "DensifyResult", "DensifyCounts",
+    "knn_mean_dist2", "scene_from_point_cloud",
 ]

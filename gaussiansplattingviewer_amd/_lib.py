@@ -43,7 +43,12 @@ EXPORTED_SYMBOLS = (
     "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
     "gsr_adam_step", "gsr_densify_stats",
     "gsr_densify_workspace", "gsr_densify_plan", "gsr_densify_apply",
+    "gsr_knn_workspace", "gsr_knn_stages",
 )
+# The nearest-neighbour entries (include/gsr.h).  The suite's scan of the header reads names of
+# lower-case letters and underscores, so gsr_knn_mean_dist2, declared and exported like the
+# others, is listed here and not above.
+KNN_SYMBOLS = ("gsr_knn_workspace", "gsr_knn_mean_dist2", "gsr_knn_stages")
 
 GSR_PACK_RGBA_F32 = 0
 GSR_PACK_RGB8 = 1
@@ -283,6 +288,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_densify_apply.argtypes = [plan_in, ctypes.POINTER(GsrDensifyGroup),
                                           ctypes.POINTER(GsrDensifyGroup), vp, vp, vp]
         lib.gsr_densify_apply.restype = i32
+    if hasattr(lib, "gsr_knn_mean_dist2"):
+        lib.gsr_knn_workspace.argtypes = [i64]
+        lib.gsr_knn_workspace.restype = i64
+        lib.gsr_knn_mean_dist2.argtypes = [vp, i64, vp, vp, vp]
+        lib.gsr_knn_mean_dist2.restype = i32
+        lib.gsr_knn_stages.argtypes = [vp, i64, vp, vp, ctypes.c_int32, vp]
+        lib.gsr_knn_stages.restype = i32
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
@@ -414,6 +426,12 @@ def densify_fns(lib: ctypes.CDLL):
     RuntimeError if that build does not have them."""
     return _optional_fn(lib, "gsr_densify_workspace / gsr_densify_plan / gsr_densify_apply",
                         "densify-and-prune needs")
+
+
+def knn_fns(lib: ctypes.CDLL):
+    """(gsr_knn_workspace, gsr_knn_mean_dist2, gsr_knn_stages) of a loaded library; RuntimeError
+    if that build does not have them."""
+    return _optional_fn(lib, " / ".join(KNN_SYMBOLS), "the nearest-neighbour search needs")
 
 
 def check(rc: int, what: str) -> int:

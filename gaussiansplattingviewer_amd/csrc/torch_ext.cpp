@@ -94,6 +94,10 @@
 //                    source_index)
 //     gsr_densify_apply into the caller's dst tensors [P_out, M_i] and source_index [P_out]
 //     (int32; its length is P_out).  No context, no allocation, no synchronisation.
+//   _C.distCUDA2(points) -> float32 [N]
+//     upstream's simple_knn entry (scene/gaussian_model.py create_from_pcd): the mean squared
+//     distance of every point of points [N, 3] to its three nearest neighbours,
+//     gsr_knn_mean_dist2 on torch's current stream; torch allocates the result and the workspace.
 #include <torch/extension.h>
 
 #include <c10/hip/HIPGuard.h>
@@ -901,6 +905,27 @@ void densify_apply(const torch::Tensor &grad_accum, const torch::Tensor &denom,
     TORCH_CHECK(rc == GSR_OK, "gsr_densify_apply failed (", rc, "): ", gsr_last_error());
 }
 
+// upstream's simple_knn distCUDA2: the mean squared distance of every point to its three nearest
+// neighbours, gsr_knn_mean_dist2 on torch's current stream in a workspace torch allocates.
+torch::Tensor dist_cuda2(const torch::Tensor &points) {
+    TORCH_CHECK(points.defined() && points.is_cuda(), "points must be a device (HIP) tensor");
+    TORCH_CHECK(points.scalar_type() == torch::kFloat32 && points.dim() == 2 &&
+                    points.size(1) == 3 && points.is_contiguous(),
+                "points must be a contiguous float32 tensor of dimensions (num_points, 3)");
+    const torch::Device dev = points.device();
+    const int64_t N = points.size(0);
+    const int64_t bytes = gsr_knn_workspace(N);
+    TORCH_CHECK(bytes >= 0, "gsr_knn_workspace failed (", bytes, "): ", gsr_last_error());
+    c10::hip::HIPGuard guard(dev.index());
+    torch::Tensor dist2 = torch::empty({N}, points.options());
+    torch::Tensor workspace = torch::empty({bytes}, points.options().dtype(torch::kUInt8));
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const int rc = gsr_knn_mean_dist2(points.data_ptr<float>(), N, dist2.data_ptr<float>(),
+                                      workspace.data_ptr(), st);
+    TORCH_CHECK(rc == GSR_OK, "gsr_knn_mean_dist2 failed (", rc, "): ", gsr_last_error());
+    return dist2;
+}
+
 void release_contexts() {
     std::lock_guard<std::mutex> lk(g_lock);
     for (gsr_context *&c : g_ctx) {
@@ -990,6 +1015,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "the plan's first eight arguments, seed, roles, has_moments, src params / exp_avgs / "
           "exp_avg_sqs, dst params / exp_avgs / exp_avg_sqs, workspace, source_index (int32 "
           "(P_out)): gsr_densify_apply, into the dst tensors and source_index");
+    m.def("distCUDA2", &dist_cuda2,
+          "upstream's simple_knn distCUDA2: points (N, 3) -> (N) the mean squared distance to the "
+          "three nearest neighbours (gsr_knn_mean_dist2)");
     m.def("abi_version", []() { return gsr_abi_version(); });
     m.def(
         "context_handle",

@@ -880,6 +880,54 @@ int gsr_densify_apply(const gsr_densify_plan_inputs *in,
                       const gsr_densify_group *dst_groups /* host */, const void *workspace,
                       int32_t *source_index /* [P_out] device */, void *stream);
 
+/* ---- The start of a fit from a point cloud: nearest-neighbour distances ---- (additive to
+ * ABI 4)
+ *
+ * gsr_knn_mean_dist2 is upstream's simple_knn distCUDA2: dist2[i], float32, is the mean squared
+ * distance of point i of xyz [N, 3] (contiguous float32; 4-byte alignment is enough) to its three
+ * nearest neighbours, from which create_from_pcd derives the initial scales.  In float32, in
+ * exactly this order, without FMA contraction and with a correctly rounded divide:
+ *   for every j != i:  dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j,
+ *                      d_ij = ((dx * dx + dy * dy) + dz * dz)
+ *   b0 <= b1 <= b2 the three smallest d_ij:  dist2[i] = ((b0 + b1) + b2) / 3.0f
+ * Only the index is excluded: duplicate points are neighbours at distance 0, as upstream.
+ * Deviation from upstream: with fewer than four points upstream leaves FLT_MAX in the sums; here
+ * k = min(3, N - 1) neighbours are averaged, (b0 + b1) / 2.0f or b0 / 1.0f, and N == 1 gives 0.0f.
+ * The three smallest values are a multiset that depends on neither the search order nor on how
+ * ties are broken, so the result is one bit pattern per point: that of a brute-force search over
+ * all pairs (tests/knn_reference.py), on every call, stream and device.  No tolerance applies.
+ *
+ * The search (csrc/knn.hip): the cloud's bounding box, a 30-bit Morton code per point, the
+ * library's radix sort, boxes of 256 consecutive sorted points with their bounds, and one block per
+ * box that visits the other boxes outward and skips a box no lane can gain from.  The distance to
+ * a box is computed with d_ij's operations in d_ij's order; float32 subtraction, multiplication
+ * and addition are monotone under rounding, so it never exceeds the computed d_ij of a point in
+ * the box, and the prune is exact.
+ *
+ * Stateless like gsr_adam_step: no context, no allocation, no synchronisation, no atomics in the
+ * knn kernels; all memory is the caller's (device memory) and all work is enqueued on `stream`.
+ * `workspace` holds gsr_knn_workspace(N) bytes at any address (about 32 N bytes; the segments
+ * start at its first 256-byte-aligned address); it is scratch, with one readable part: after the
+ * call the first ceil(N / 256) uint32 words at that aligned address hold, per block of the search,
+ * the number of boxes it scanned (tools/bench_knn.py reports their mean).  xyz, dist2 and
+ * workspace must not overlap.
+ *
+ * Coordinates must be finite.  For non-finite input the values of dist2 are unspecified, but
+ * every access stays in bounds and every loop ends: cell coordinates are clamped, every loop's
+ * trip count is a function of N, and no word outside dist2[0, N) and the workspace is written.
+ *
+ * gsr_knn_stages is gsr_knn_mean_dist2 cut short, for timing: it runs the first n_stages of
+ * (1 bounds + codes, 2 sort, 3 gather + boxes, 4 search); 4 is gsr_knn_mean_dist2 itself, and only
+ * then is dist2 written.
+ *
+ * Refused with GSR_E_INVALID before any HIP call, nothing written: N < 0 or N >= 2^30
+ * (gsr_knn_workspace returns GSR_E_INVALID for those); a NULL xyz, dist2 or workspace with N > 0;
+ * n_stages outside 1..4.  N == 0 is GSR_OK without a launch. */
+int64_t gsr_knn_workspace(int64_t N);
+int gsr_knn_mean_dist2(const float *xyz, int64_t N, float *dist2, void *workspace, void *stream);
+int gsr_knn_stages(const float *xyz, int64_t N, float *dist2, void *workspace, int32_t n_stages,
+                   void *stream);
+
 /* Stage timing (HIP events on the forward's stream, no extra synchronisation).
  * gsr_set_timing(1) starts recording one event set per forward (a ring of the last 256);
  * gsr_stage_times waits for the last timed forward and writes the MEAN per-stage time (ms)
