@@ -20,6 +20,7 @@ from .losses import photometric_loss, ssim
 from .optim import SparseGaussianAdam, densification_stats
 from .densify import DensifyCounts, DensifyResult, densify_and_prune
 from .pointcloud import knn_mean_dist2, scene_from_point_cloud
+from .ply import load_ply, load_scene_ply, save_ply
 
 __all__ = [
     "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
@@ -29,5 +30,5 @@ __all__ = [
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
     "render_strips", "photometric_loss", "ssim", "SparseGaussianAdam",
     "densification_stats", "densify_and_prune", "DensifyResult", "DensifyCounts",
-    "knn_mean_dist2", "scene_from_point_cloud",
+    "knn_mean_dist2", "scene_from_point_cloud", "load_ply", "load_scene_ply", "save_ply",
 ]

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "gsr_adam_step", "gsr_densify_stats",
     "gsr_densify_workspace", "gsr_densify_plan", "gsr_densify_apply",
     "gsr_knn_workspace", "gsr_knn_stages",
+    "gsr_ply_save", "gsr_ply_probe_scene", "gsr_ply_load_scene",
 )
 # The nearest-neighbour entries (include/gsr.h).  The suite's scan of the header reads names of
 # lower-case letters and underscores, so gsr_knn_mean_dist2, declared and exported like the
@@ -216,6 +217,15 @@ class GsrPlyInfo(ctypes.Structure):
     ]
 
 
+class GsrPlyScene(ctypes.Structure):
+    """gsr_ply_scene: the raw tensors of a fit for gsr_ply_save / gsr_ply_load_scene."""
+    _fields_ = [("P", ctypes.c_int64), ("sh_coeffs", ctypes.c_int32),
+                ("file_sh_coeffs", ctypes.c_int32), ("chunk_rows", ctypes.c_int64),
+                ("xyz", ctypes.c_void_p), ("f_dc", ctypes.c_void_p), ("f_rest", ctypes.c_void_p),
+                ("opacity", ctypes.c_void_p), ("scaling", ctypes.c_void_p),
+                ("rotation", ctypes.c_void_p)]
+
+
 # The entries added to ABI 4 one by one: the structs between (ctx, gaussians, settings) and the
 # stream.
 _ADDITIVE = {
@@ -295,6 +305,13 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_knn_mean_dist2.restype = i32
         lib.gsr_knn_stages.argtypes = [vp, i64, vp, vp, ctypes.c_int32, vp]
         lib.gsr_knn_stages.restype = i32
+    if hasattr(lib, "gsr_ply_save"):
+        ply_scene = ctypes.POINTER(GsrPlyScene)
+        lib.gsr_ply_save.argtypes = [ctypes.c_char_p, ply_scene, i32, vp]
+        lib.gsr_ply_probe_scene.argtypes = [ctypes.c_char_p, ply_scene]
+        lib.gsr_ply_load_scene.argtypes = [ctypes.c_char_p, ply_scene, i32, vp]
+        for name in ("gsr_ply_save", "gsr_ply_probe_scene", "gsr_ply_load_scene"):
+            getattr(lib, name).restype = i32
     if hasattr(lib, "gsr_backward"):
         lib.gsr_backward_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32]
         lib.gsr_backward_times.restype = i32
@@ -432,6 +449,13 @@ def knn_fns(lib: ctypes.CDLL):
     """(gsr_knn_workspace, gsr_knn_mean_dist2, gsr_knn_stages) of a loaded library; RuntimeError
     if that build does not have them."""
     return _optional_fn(lib, " / ".join(KNN_SYMBOLS), "the nearest-neighbour search needs")
+
+
+def ply_scene_fns(lib: ctypes.CDLL):
+    """(gsr_ply_save, gsr_ply_probe_scene, gsr_ply_load_scene) of a loaded library; RuntimeError
+    if that build does not have them."""
+    return _optional_fn(lib, "gsr_ply_save / gsr_ply_probe_scene / gsr_ply_load_scene",
+                        "saving and loading a raw scene needs")
 
 
 def check(rc: int, what: str) -> int:

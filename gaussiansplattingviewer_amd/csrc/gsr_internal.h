@@ -9,6 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
+#include <string>
+#include <vector>
+
 #pragma clang fp contract(off)
 
 #define GSR_TILE_X 16
@@ -757,3 +761,80 @@ struct GsrPreprocessBwdExtras {
 // hipErrorInvalidValue for a camera without partials or without an output; P == 0 launches nothing.
 hipError_t gsr_launch_preprocess_bwd(const GsrPreprocessBwdArgs &a,
                                      const GsrPreprocessBwdExtras &x, hipStream_t s);
+
+// ---- the PLY reader's header parser and value conversion (host code, defined in ply_loader.hip;
+// shared with the scene reader in ply_writer.hip) ---------------------------------------------
+#define GSR_TRY_PLY(expr)             \
+    do {                              \
+        const int rc_ = (expr);       \
+        if (rc_ != GSR_OK) return rc_; \
+    } while (0)
+
+namespace gsr_ply {
+
+enum class PType { I8, U8, I16, U16, I32, U32, F32, F64 };
+
+struct Prop {
+    std::string name;
+    PType type;
+    int size;
+    int offset;  // within the binary vertex record
+};
+
+struct Header {
+    enum Format { ASCII, BLE, BBE } format = BLE;
+    int64_t count = 0;
+    std::vector<Prop> props;
+    int stride = 0;
+    size_t data_offset = 0;  // first byte of the vertex element
+};
+
+// A read-only mapping of the whole file, unmapped by the destructor.
+struct Mapped {
+    const unsigned char *p = nullptr;
+    size_t size = 0;
+    ~Mapped();
+};
+
+// gsr_set_error(code, "PLY: " + msg).
+int fail(int code, const std::string &msg);
+int map_file(const char *path, Mapped &m);
+// The vertex element's properties, count, stride and first byte; every count and stride of the
+// (untrusted) header is bounded by the file size.
+int parse_header(const Mapped &m, Header &h);
+int find_prop(const Header &h, const std::string &name);
+// Properties whose name starts with `prefix`, sorted by their integer suffix.
+std::vector<int> prefixed(const Header &h, const std::string &prefix);
+// The next whitespace-separated number of an ascii body, parsed as float64 and then taken to the
+// property's type as plyfile's text path does; s moves past it.
+int ascii_value(const char *&s, const char *end, PType type, double &out);
+
+// A value of a property as double (exact for every PLY scalar type).
+inline double read_value(const unsigned char *p, PType t, bool swap) {
+    unsigned char b[8];
+    int n = 0;
+    switch (t) {
+        case PType::I8: case PType::U8: n = 1; break;
+        case PType::I16: case PType::U16: n = 2; break;
+        case PType::I32: case PType::U32: case PType::F32: n = 4; break;
+        case PType::F64: n = 8; break;
+    }
+    for (int i = 0; i < n; ++i) b[i] = swap ? p[n - 1 - i] : p[i];
+    switch (t) {
+        case PType::I8: { int8_t v; std::memcpy(&v, b, 1); return v; }
+        case PType::U8: { uint8_t v; std::memcpy(&v, b, 1); return v; }
+        case PType::I16: { int16_t v; std::memcpy(&v, b, 2); return v; }
+        case PType::U16: { uint16_t v; std::memcpy(&v, b, 2); return v; }
+        case PType::I32: { int32_t v; std::memcpy(&v, b, 4); return v; }
+        case PType::U32: { uint32_t v; std::memcpy(&v, b, 4); return v; }
+        case PType::F32: { float v; std::memcpy(&v, b, 4); return v; }
+        case PType::F64: { double v; std::memcpy(&v, b, 8); return v; }
+    }
+    return 0.0;
+}
+
+// The reference builds xyz / opacity from the property arrays as read (float32 for float
+// properties) and the other fields in float64: value as float32 = numpy astype(float32).
+inline float as_f32(double v) { return (float)v; }
+
+}  // namespace gsr_ply

@@ -38,20 +38,27 @@
 #include <hip/hip_runtime.h>
 
 #include "gsr.h"
-
-#define GSR_TRY_PLY(expr)             \
-    do {                              \
-        const int rc_ = (expr);       \
-        if (rc_ != GSR_OK) return rc_; \
-    } while (0)
+#include "gsr_internal.h"
 
 int gsr_set_error(int code, const std::string &msg);  // api.hip
 
+// The header parser and the value conversion are shared with the scene reader
+// (ply_writer.hip) through gsr_internal.h: the types and read_value live there.
+namespace gsr_ply {
+
+int fail(int code, const std::string &msg) { return gsr_set_error(code, "PLY: " + msg); }
+
+Mapped::~Mapped() {
+    if (p) munmap(const_cast<unsigned char *>(p), size);
+}
+
+}  // namespace gsr_ply
+
+using namespace gsr_ply;
+
 namespace {
 
-int ply_fail(int code, const std::string &msg) { return gsr_set_error(code, "PLY: " + msg); }
-
-enum class PType { I8, U8, I16, U16, I32, U32, F32, F64 };
+int ply_fail(int code, const std::string &msg) { return gsr_ply::fail(code, msg); }
 
 bool ptype_of(const std::string &t, PType &out, int &size) {
     struct E {
@@ -76,62 +83,15 @@ bool ptype_of(const std::string &t, PType &out, int &size) {
     return false;
 }
 
-struct Prop {
-    std::string name;
-    PType type;
-    int size;
-    int offset;  // within the binary vertex record
-};
-
-struct Header {
-    enum Format { ASCII, BLE, BBE } format = BLE;
-    int64_t count = 0;
-    std::vector<Prop> props;
-    int stride = 0;
-    size_t data_offset = 0;  // first byte of the vertex element
-};
-
 // Field indices into Header::props of everything the loader reads.
 struct Layout {
     int xyz[3], dc[3], rest[45], opacity, scale[3], rot[4];
     int n_scale = 0, n_rot = 0;
 };
 
-// A value of a property as double (exact for every PLY scalar type).
-inline double read_value(const unsigned char *p, PType t, bool swap) {
-    unsigned char b[8];
-    int n = 0;
-    switch (t) {
-        case PType::I8: case PType::U8: n = 1; break;
-        case PType::I16: case PType::U16: n = 2; break;
-        case PType::I32: case PType::U32: case PType::F32: n = 4; break;
-        case PType::F64: n = 8; break;
-    }
-    for (int i = 0; i < n; ++i) b[i] = swap ? p[n - 1 - i] : p[i];
-    switch (t) {
-        case PType::I8: { int8_t v; std::memcpy(&v, b, 1); return v; }
-        case PType::U8: { uint8_t v; std::memcpy(&v, b, 1); return v; }
-        case PType::I16: { int16_t v; std::memcpy(&v, b, 2); return v; }
-        case PType::U16: { uint16_t v; std::memcpy(&v, b, 2); return v; }
-        case PType::I32: { int32_t v; std::memcpy(&v, b, 4); return v; }
-        case PType::U32: { uint32_t v; std::memcpy(&v, b, 4); return v; }
-        case PType::F32: { float v; std::memcpy(&v, b, 4); return v; }
-        case PType::F64: { double v; std::memcpy(&v, b, 8); return v; }
-    }
-    return 0.0;
-}
+}  // namespace
 
-// The reference builds xyz / opacity from the property arrays as read (float32 for float
-// properties) and the other fields in float64: value as float32 = numpy astype(float32).
-inline float as_f32(double v) { return (float)v; }
-
-struct Mapped {
-    const unsigned char *p = nullptr;
-    size_t size = 0;
-    ~Mapped() {
-        if (p) munmap(const_cast<unsigned char *>(p), size);
-    }
-};
+namespace gsr_ply {
 
 int map_file(const char *path, Mapped &m) {
     const int fd = open(path, O_RDONLY);
@@ -276,6 +236,35 @@ std::vector<int> prefixed(const Header &h, const std::string &prefix) {
     for (auto &e : v) out.push_back(e.second);
     return out;
 }
+
+// The next whitespace-separated number of an ascii body as the value of a property of type t.
+int ascii_value(const char *&s, const char *end, PType type, double &out) {
+    while (s < end && (*s == ' ' || *s == '\n' || *s == '\r' || *s == '\t')) ++s;
+    if (s >= end) return ply_fail(GSR_E_INVALID, "ascii PLY shorter than its vertex data");
+    // the token, copied out NUL-terminated: strtod must not run past the mapping
+    const char *t = s;
+    while (t < end && !(*t == ' ' || *t == '\n' || *t == '\r' || *t == '\t')) ++t;
+    char tok[64];
+    const size_t len = (size_t)(t - s);
+    if (len >= sizeof(tok)) return ply_fail(GSR_E_INVALID, "bad number in ascii PLY");
+    std::memcpy(tok, s, len);
+    tok[len] = '\0';
+    char *stop = nullptr;
+    // like plyfile (numpy text parsing): as float64, then the property's type
+    const double d = std::strtod(tok, &stop);
+    if (stop != tok + len || len == 0) return ply_fail(GSR_E_INVALID, "bad number in ascii PLY");
+    s = t;
+    switch (type) {
+        case PType::F32: out = (double)(float)d; break;
+        case PType::F64: out = d; break;
+        default: out = std::trunc(d); break;
+    }
+    return GSR_OK;
+}
+
+}  // namespace gsr_ply
+
+namespace {
 
 int make_layout(const Header &h, Layout &L) {
     const char *xyz[3] = {"x", "y", "z"};
@@ -460,27 +449,8 @@ int convert_ascii(const Mapped &m, const Header &h, const Layout &L, float *xyz,
     Row r;
     for (int64_t i = 0; i < h.count; ++i) {
         for (size_t k = 0; k < h.props.size(); ++k) {
-            while (s < end && (*s == ' ' || *s == '\n' || *s == '\r' || *s == '\t')) ++s;
-            if (s >= end) return ply_fail(GSR_E_INVALID, "ascii PLY shorter than its vertex data");
-            // the token, copied out NUL-terminated: strtod must not run past the mapping
-            const char *t = s;
-            while (t < end && !(*t == ' ' || *t == '\n' || *t == '\r' || *t == '\t')) ++t;
-            char tok[64];
-            const size_t len = (size_t)(t - s);
-            if (len >= sizeof(tok)) return ply_fail(GSR_E_INVALID, "bad number in ascii PLY");
-            std::memcpy(tok, s, len);
-            tok[len] = '\0';
-            char *stop = nullptr;
-            // like plyfile (numpy text parsing): as float64, then the property's type
-            const double d = std::strtod(tok, &stop);
-            if (stop != tok + len || len == 0) return ply_fail(GSR_E_INVALID, "bad number in ascii PLY");
-            s = t;
-            double val = d;
-            switch (h.props[k].type) {
-                case PType::F32: val = (double)(float)d; break;
-                case PType::F64: break;
-                default: val = std::trunc(d); break;
-            }
+            double val;
+            GSR_TRY_PLY(ascii_value(s, end, h.props[k].type, val));
             v[k] = val;
         }
         activate(v.data(), L, h.props[L.opacity].type == PType::F32, r);

@@ -626,6 +626,68 @@ int gsr_ply_probe(const char *path, gsr_ply_info *info);
 int gsr_ply_load(const char *path, gsr_ply_info *info, float *xyz, float *rot, float *scale,
                  float *opacity, float *sh, int device, void *stream);
 
+/* ---- Scene files: a fit's raw tensors as upstream's save_ply writes them, and back ----------
+ * The scene is the fit's own tensors, not activated: xyz[P*3], f_dc[P*1*3], f_rest[P*(M-1)*3],
+ * opacity[P], scaling[P*3], rotation[P*4], M = (d + 1)^2 coefficients for a degree d = 0..4.
+ *
+ * The file: the header plyfile writes for upstream's save_ply ("ply", "format
+ * binary_little_endian 1.0", "element vertex <P>", one "property float <name>" line for each of
+ * x y z nx ny nz f_dc_0..2 f_rest_0..3(Mo-1)-1 opacity scale_0..2 rot_0..3, "end_header"; '\n'
+ * line ends, no comment), then P rows of R = 17 + 3 (Mo - 1) little-endian float32 words:
+ *   columns 0..2               xyz[p][:]
+ *   columns 3..5               +0.0 (the normals)
+ *   column  6 + c              f_dc[p][0][c]
+ *   column  9 + c (Mo-1) + j   f_rest[p][j][c] for j < M - 1, else +0.0
+ *                              (upstream's transpose(1, 2).flatten(1): c the channel, j the
+ *                              coefficient)
+ *   column  9 + 3 (Mo-1)       opacity[p], then scaling[p][:], then rotation[p][:]
+ * Every word is a bit copy of a word of the scene or the bits of +0.0f: NaN payloads, infinities
+ * and -0.0 survive.  Mo = file_sh_coeffs is the file's coefficient count: 0 means M; a larger
+ * square pads the f_rest columns with +0.0 (Mo = 16 makes a degree-0..2 scene a file that
+ * gsr_ply_load accepts); Mo < M is refused.
+ *
+ * gsr_ply_save: device == 0: the pointers are host memory and the rows are packed in plain C++.
+ * Otherwise they are device memory of the calling thread's current device: k_ply_pack writes
+ * chunk_rows packed rows into one of two device slots, hipMemcpyAsync copies the slot into one
+ * of two pinned host slots, and the host write()s one slot while the next chunk packs and
+ * copies -- 2 x chunk_rows x 4R bytes on either side whatever P is, no full-size host copy.  The
+ * stream is synchronised before return.  The scene is only read; pointers need 4-byte alignment
+ * only.  chunk_rows == 0 is the library's default (GSR_PLY_CHUNK_ROWS); values above
+ * GSR_PLY_MAX_CHUNK_ROWS are taken as that.  The bytes go to "<path>.tmp.<pid>", renamed over
+ * `path` after the last one; any failure removes the temporary file and leaves a file already
+ * at `path` as it was.  P == 0 writes the header alone.
+ *
+ * gsr_ply_probe_scene fills info->P and info->sh_coeffs from the header alone.
+ * gsr_ply_load_scene fills the six tensors (f_rest may be NULL when M == 1) with the raw
+ * values: the inverse of the column table, no activation, no bounding box.  scene->P and
+ * scene->sh_coeffs must be what the probe reported.  It reads what gsr_ply_load reads, by the
+ * same rules (either endianness or ascii, any scalar type per property converted like numpy's
+ * astype(float32) -- float properties are bit copies --, any property order, f_rest_* / scale_* /
+ * rot* sorted by integer suffix, other properties ignored), with 3 (M - 1) f_rest properties for
+ * any M above.  device != 0: a little-endian file whose vertex properties are all float goes in
+ * row chunks through pinned staging to the device, where k_ply_unpack scatters them into the
+ * tensors; every other file is converted on the host and uploaded.  Both give the same bits;
+ * the stream is synchronised before return.
+ *
+ * Refused with GSR_E_INVALID before any HIP call and before the file is touched: a NULL path,
+ * scene / info or required pointer (P == 0 needs none); P < 0 or P >= 2^30; sh_coeffs or
+ * file_sh_coeffs that is no square of 1..5; file_sh_coeffs < sh_coeffs; chunk_rows < 0.
+ * GSR_E_INVALID too: a file that cannot be created or opened, a short write or a short file, an
+ * f_rest count that is not 3 (M - 1) for such an M, a P or sh_coeffs that is not the file's. */
+#define GSR_PLY_CHUNK_ROWS 65536
+#define GSR_PLY_MAX_CHUNK_ROWS 1048576
+typedef struct gsr_ply_scene {
+    int64_t P;
+    int32_t sh_coeffs;      /* M of the tensors */
+    int32_t file_sh_coeffs; /* Mo of the file written; 0 = M (gsr_ply_save only) */
+    int64_t chunk_rows;     /* rows per staging slot; 0 = the library's default */
+    float *xyz, *f_dc, *f_rest, *opacity, *scaling, *rotation;
+} gsr_ply_scene;
+
+int gsr_ply_save(const char *path, const gsr_ply_scene *scene, int device, void *stream);
+int gsr_ply_probe_scene(const char *path, gsr_ply_scene *info);
+int gsr_ply_load_scene(const char *path, gsr_ply_scene *scene, int device, void *stream);
+
 /* ---- Stereo dataset outputs ----
  * gsr_disparity_colors: colors[3*i..3*i+2] = d_i for every Gaussian, with
  *   d = |(ndc_x(p) + 1)/2 - (ndc_x(p + (baseline, 0, 0)) + 1)/2|, ndc_x(q) = (P V [q;1]).x /
