@@ -1562,45 +1562,107 @@ int gsr_forward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_ras
     return forward_entry(ctx, g, st, out, stream, rq);
 }
 
-// The gradients of the splat composite.  Everything is rebuilt from the arguments -- the
-// per-Gaussian stage, the depth sort and upstream's (untight) lists, the direct way: no recorded
-// graph is replayed, none is invalidated beyond what a forward of the same shape would -- so
-// nothing of an earlier forward on this context is read; then backward.hip's two kernels.
-// pl: gsr_backward_planes' struct, or NULL (gsr_backward).  With one of its three plane gradients
-// the two kernels are backward.hip's planes instantiations; without, they are gsr_backward's.
-// cam: gsr_backward_camera's struct, or NULL.  With one of its three buffers the per-Gaussian
-// backward is the camera instantiation (with or without the planes) and k_camera_finish follows
-// it, inside the third timed stage; without, nothing differs from the call without it.
-// deterministic: gsr_backward_ordered's mode -- the blend's backward stores every
-// (Gaussian, tile, quadrant)'s sums to a slot of its own and a gather fills the 2D gradient rows in
-// a fixed order, both inside the second timed stage; nothing else of the call differs.
-// strips: gsr_backward_strip -- a tile row strip of the settings is honoured instead
-// of refused: the rebuild is the strip's, the blend's backward runs the strip's tiles with the
-// strip-local image gradients, and on a proper subset of the rows the Gaussians without a tile in
-// it are gated out of the per-Gaussian stage.  Without a strip in the settings nothing differs.
-static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
-                    const gsr_backward_inputs *in, const gsr_plane_gradients *pl,
-                    const gsr_camera_gradients *cam, gsr_gradients *gr, void *stream,
-                    const std::string &fn, bool antialiasing = false,
-                    bool deterministic = false, bool strips = false,
-                    const gsr_feature_gradients *ft = nullptr) {
-    if (!ctx || !g || !st || !in || !gr) return fail(GSR_E_INVALID, fn + ": NULL argument");
-    const bool strip = st->tile_row_begin != 0 || st->tile_row_end != 0;
-    if (strip && !strips)
+// ---- the backward: the gradients of the splat composite ----------------------------------------
+// Everything is rebuilt from the arguments -- the per-Gaussian stage, the depth sort and upstream's
+// (untight) lists, the direct way: no recorded graph is replayed, none is invalidated beyond what a
+// forward of the same shape would -- so nothing of an earlier forward on this context is read; then
+// backward.hip's two kernels.
+
+// What a public backward was called with, as FrameRequest holds a forward's: NULL for each
+// optional struct the entry does not take.
+struct BackwardRequest {
+    // the entry a message names while none of filter, order, a strip and feat is in use: the entry
+    // itself up to gsr_backward_camera, which every later entry is without its own option
+    const char *fn;
+    const gsr_gaussians *g;
+    const gsr_raster_settings *st;
+    const gsr_backward_inputs *in;
+    gsr_gradients *gr;
+    const gsr_plane_gradients *planes = nullptr;
+    const gsr_camera_gradients *camera = nullptr;
+    const gsr_filter_settings *filter = nullptr;
+    const gsr_backward_order *order = nullptr;
+    const gsr_feature_gradients *feat = nullptr;
+    bool strips = false;  // gsr_backward_strip on: a strip of the settings is honoured, not refused
+};
+
+// What the call does, decided once, before the context is touched.
+struct BackwardPlan {
+    // the entry the messages name: the last of gsr_backward_filtered, _ordered, _strip and
+    // _features whose option is in use (an option at 0 is the entry below), else rq.fn
+    std::string fn;
+    hipStream_t s = nullptr;
+    bool planes = false;  // a plane gradient is given: the planes instantiations of both kernels
+    bool camera = false;  // a camera buffer is given: the camera instantiation and k_camera_finish
+    bool aa = false;      // gsr_backward_filtered: the antialiased per-Gaussian twins
+    // gsr_backward_ordered: the blend's backward stores every (Gaussian, tile,
+    // quadrant)'s sums to a slot of its own and a gather fills the 2D gradient rows in a fixed order
+    bool det = false;
+    // the settings hold a strip: the rebuild and the blend's backward are the strip's, and on a
+    // proper subset of the rows the Gaussians without a tile in it are gated out of the third stage
+    bool strip = false;
+    const gsr_feature_gradients *ft = nullptr;  // rq.feat when it holds a dL_dfeature_map
+};
+
+static bool backward_null(const gsr_context *ctx, const BackwardRequest &rq) {
+    return !ctx || !rq.g || !rq.st || !rq.in || !rq.gr;
+}
+
+// The optional structs -> p.aa, p.det, p.ft and the name the call speaks under.  ctx is compared
+// with NULL only.
+static int backward_parse(const gsr_context *ctx, const BackwardRequest &rq, BackwardPlan &p) {
+    const int aa = rq.filter ? rq.filter->antialiasing : 0;
+    const int det = rq.order ? rq.order->deterministic : 0;
+    if (rq.feat && rq.feat->dL_dfeature_map) p.ft = rq.feat;
+    p.fn = aa == 0 ? rq.fn : "gsr_backward_filtered";
+    if (det != 0) p.fn = "gsr_backward_ordered";
+    if (rq.strips) {  // the two entries that read the settings here check their pointers first
+        if (backward_null(ctx, rq))
+            return fail(GSR_E_INVALID, std::string(p.ft ? "gsr_backward_features"
+                                                        : "gsr_backward_strip") + ": NULL argument");
+        if (rq.st->tile_row_begin != 0 || rq.st->tile_row_end != 0) p.fn = "gsr_backward_strip";
+    }
+    if (p.ft) {
+        p.fn = "gsr_backward_features";
+        if (const char *why = feature_fault(p.ft->C, p.ft->features, rq.g->P))
+            return fail(GSR_E_INVALID, p.fn + ": " + why + " (C = " + std::to_string(p.ft->C) + ")");
+        if (det == 1)
+            return fail(GSR_E_INVALID, p.fn + ": deterministic == 1 with a feature gradient: the "
+                                              "deterministic slots hold 9 or 10 sums and have no "
+                                              "room for C more");
+    }
+    if (det != 0 && det != 1)
+        return fail(GSR_E_INVALID, p.fn + ": deterministic must be 0 or 1, got " +
+                                       std::to_string(det));
+    if (aa != 0 && aa != 1)
+        return fail(GSR_E_INVALID, p.fn + ": antialiasing must be 0 or 1, got " +
+                                       std::to_string(aa));
+    p.aa = aa == 1, p.det = det == 1;
+    return GSR_OK;
+}
+
+// The arguments themselves -> p.strip, p.planes, p.camera.  ctx is compared with NULL only.
+static int backward_validate(const gsr_context *ctx, const BackwardRequest &rq, BackwardPlan &p) {
+    const std::string &fn = p.fn;
+    if (backward_null(ctx, rq)) return fail(GSR_E_INVALID, fn + ": NULL argument");
+    const gsr_gaussians *g = rq.g;
+    const gsr_raster_settings *st = rq.st;
+    p.strip = st->tile_row_begin != 0 || st->tile_row_end != 0;
+    if (p.strip && !rq.strips)
         return fail(GSR_E_INVALID, fn + ": whole frames only (a tile row strip is set)");
-    const int64_t P = g->P;
-    if (P < 0 || P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, fn + ": bad P");
+    if (g->P < 0 || g->P > (int64_t)UINT32_MAX) return fail(GSR_E_INVALID, fn + ": bad P");
     if (st->image_width <= 0 || st->image_height <= 0)
         return fail(GSR_E_INVALID, fn + ": image size must be positive");
-    // (before anything is written: the P == 0 path below zeroes the camera's buffers)
-    if (strip && (st->tile_row_begin < 0 || st->tile_row_begin >= st->tile_row_end ||
-                  st->tile_row_end > (st->image_height + GSR_TILE_Y - 1) / GSR_TILE_Y))
+    // (before anything is written: the P == 0 path zeroes the camera's buffers)
+    if (p.strip && (st->tile_row_begin < 0 || st->tile_row_begin >= st->tile_row_end ||
+                    st->tile_row_end > (st->image_height + GSR_TILE_Y - 1) / GSR_TILE_Y))
         return fail(GSR_E_INVALID, fn + ": bad tile row strip");
-    const bool planes =
-        pl && (pl->dL_ddepth_map || pl->dL_dinv_depth_map || pl->dL_dfinal_T);
-    float *const dL_ddepths = pl ? pl->dL_ddepths : nullptr;
-    if (P > 0) {
-        if (!in->dL_dcolor && !planes && !ft)
+    const gsr_plane_gradients *pl = rq.planes;
+    p.planes = pl && (pl->dL_ddepth_map || pl->dL_dinv_depth_map || pl->dL_dfinal_T);
+    const gsr_camera_gradients *cam = rq.camera;
+    p.camera = cam && (cam->dL_dviewmatrix || cam->dL_dprojmatrix || cam->dL_dcampos);
+    if (g->P > 0) {
+        if (!rq.in->dL_dcolor && !p.planes && !p.ft)
             return fail(GSR_E_INVALID, fn + (pl ? ": dL_dcolor or a plane gradient is required"
                                                 : ": dL_dcolor is required"));
         if ((g->shs == nullptr) == (g->colors_precomp == nullptr))
@@ -1611,65 +1673,69 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
             return fail(GSR_E_INVALID, "Please provide exactly one of either scale/rotation pair "
                                        "or precomputed 3D covariance!");
     }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GSR_TRY(order_stream(ctx, s));
-    const bool camera =
-        cam && (cam->dL_dviewmatrix || cam->dL_dprojmatrix || cam->dL_dcampos);
-    if (P == 0) {  // no Gaussian, no gradient: the camera's buffers, of a fixed size, are zeros
-        if (camera) {
-            const struct {
-                float *p;
-                size_t n;
-                const char *what;
-            } sums[] = {{cam->dL_dviewmatrix, 16, "hipMemsetAsync(dL_dviewmatrix)"},
-                        {cam->dL_dprojmatrix, 16, "hipMemsetAsync(dL_dprojmatrix)"},
-                        {cam->dL_dcampos, 3, "hipMemsetAsync(dL_dcampos)"}};
-            for (const auto &m : sums)
-                if (m.p) GSR_HIP(hipMemsetAsync(m.p, 0, m.n * sizeof(float), s), m.what);
-        }
-        return GSR_OK;
-    }
-    if (camera)
-        GSR_TRY(grow(ctx, ctx->cam_partials,
-                     (size_t)kCameraSums * gsr_preprocess_blocks(P) * sizeof(float), s));
-    GSR_TRY(grow(ctx, ctx->grad2d, (size_t)P * kGradRow * sizeof(float), s));
-    GSR_TRY(grow(ctx, ctx->bwd_radii, (size_t)P * sizeof(int32_t), s));
-    if (deterministic) {
-        GSR_TRY(grow(ctx, ctx->det_slab, (size_t)P * sizeof(uint64_t), s));
-        GSR_TRY(grow(ctx, ctx->det_partials, (size_t)gsr_slab_blocks(P) * sizeof(uint64_t), s));
-    }
+    return GSR_OK;
+}
 
-    // the rebuild: a forward without its blend, with upstream's lists, launched directly and
-    // untimed; the context's options are the caller's again afterwards
+// The workspace whose size P decides (the deterministic slots' follows the rebuild's K).
+static int backward_reserve(gsr_context *ctx, const BackwardRequest &rq, const BackwardPlan &p) {
+    const int64_t P = rq.g->P;
+    if (p.camera)
+        GSR_TRY(grow(ctx, ctx->cam_partials,
+                     (size_t)kCameraSums * gsr_preprocess_blocks(P) * sizeof(float), p.s));
+    GSR_TRY(grow(ctx, ctx->grad2d, (size_t)P * kGradRow * sizeof(float), p.s));
+    GSR_TRY(grow(ctx, ctx->bwd_radii, (size_t)P * sizeof(int32_t), p.s));
+    if (p.det) {
+        GSR_TRY(grow(ctx, ctx->det_slab, (size_t)P * sizeof(uint64_t), p.s));
+        GSR_TRY(grow(ctx, ctx->det_partials, (size_t)gsr_slab_blocks(P) * sizeof(uint64_t), p.s));
+    }
+    return GSR_OK;
+}
+
+// The i-th of the four events around the three timed stages.
+static int backward_mark(gsr_context *ctx, const BackwardPlan &p, int i) {
+    if (ctx->timing) GSR_HIP(hipEventRecord(ctx->ev_bwd[i], p.s), "hipEventRecord");
+    return GSR_OK;
+}
+
+static int backward_stage_check(const BackwardRequest &rq, const BackwardPlan &p, const char *what) {
+    if (!rq.st->debug) return GSR_OK;
+    GSR_HIP(hipStreamSynchronize(p.s), what);
+    GSR_HIP(hipGetLastError(), what);
+    return GSR_OK;
+}
+
+// The caller's options, set aside for the rebuild and put back on every way out of it.
+struct RebuildOptions {
+    gsr_context *ctx;
+    const int tight = ctx->tight, graphs = ctx->graphs, timing = ctx->timing;
+    ~RebuildOptions() { ctx->tight = tight, ctx->graphs = graphs, ctx->timing = timing; }
+};
+
+// The first timed stage, the rebuild: a forward without its blend, with upstream's lists,
+// launched directly and untimed.
+static int backward_rebuild(gsr_context *ctx, const BackwardRequest &rq, const BackwardPlan &p) {
     gsr_outputs out{};
     out.color = ctx->grad2d.get();  // (required by the argument check; never written: no_blend)
     out.radii = ctx->bwd_radii.get();
-    const int tight = ctx->tight, graphs = ctx->graphs, timing = ctx->timing;
     ctx->bwd_timed = false;
-    if (timing)
+    if (ctx->timing)
         for (auto &e : ctx->ev_bwd)
             if (!e) GSR_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence), "hipEventCreate");
-    auto mark = [&](int i) -> int {
-        if (timing) GSR_HIP(hipEventRecord(ctx->ev_bwd[i], s), "hipEventRecord");
-        return GSR_OK;
-    };
-    GSR_TRY(mark(0));
+    GSR_TRY(backward_mark(ctx, p, 0));
+    RebuildOptions restore{ctx};
     ctx->tight = ctx->graphs = ctx->timing = 0;
     FrameRequest rebuild;
-    rebuild.antialiasing = antialiasing;
+    rebuild.antialiasing = p.aa;
     rebuild.no_blend = true;
-    const int rc = forward(ctx, g, st, &out, s, rebuild);
-    ctx->tight = tight, ctx->graphs = graphs, ctx->timing = timing;
-    GSR_TRY(rc);
+    return forward(ctx, rq.g, rq.st, &out, p.s, rebuild);
+}
 
-    const bool dbg = st->debug != 0;
-    auto stage_check = [&](const char *what) -> int {
-        if (!dbg) return GSR_OK;
-        GSR_HIP(hipStreamSynchronize(s), what);
-        GSR_HIP(hipGetLastError(), what);
-        return GSR_OK;
-    };
+// The second timed stage, the blend's backward: ctx->grad2d's rows from the image-like gradients.
+static int backward_blend(gsr_context *ctx, const BackwardRequest &rq, const BackwardPlan &p) {
+    const gsr_raster_settings *st = rq.st;
+    const gsr_feature_gradients *ft = p.ft;
+    const int64_t P = rq.g->P;
+    hipStream_t s = p.s;
     const gsr_context::LastFrame &l = ctx->last;
     // the strip the rebuild binned (the whole frame's rows without one), as launch_blend offsets
     // the forward's
@@ -1677,24 +1743,24 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     sa.row_begin = l.rb;
     sa.y0 = (int)(l.rb * GSR_TILE_Y);
     sa.rows_out = std::min(st->image_height, (int)(l.re * GSR_TILE_Y)) - sa.y0;
-    const GsrStripBwdArgs *const sp = strip ? &sa : nullptr;
+    const GsrStripBwdArgs *const sp = p.strip ? &sa : nullptr;
     GsrDetBwdArgs da{};
-    if (deterministic) {
+    if (p.det) {
         // the slots: one per (list entry, quadrant); the lists are upstream's, K = num_rendered
         const uint64_t K = (uint64_t)l.list;
         if (l.tight || l.list != l.K)
-            return fail(GSR_E_STATE, fn + ": the rebuild left tight lists");
+            return fail(GSR_E_STATE, p.fn + ": the rebuild left tight lists");
         if (K >= (1ull << 30))
-            return fail(GSR_E_INVALID, fn + ": deterministic needs num_rendered < 2^30, got " +
+            return fail(GSR_E_INVALID, p.fn + ": deterministic needs num_rendered < 2^30, got " +
                                            std::to_string(K));
-        const size_t sums = planes ? 10 : 9;
+        const size_t sums = p.planes ? 10 : 9;
         GSR_TRY(grow(ctx, ctx->det_marks, std::max<size_t>(4 * K, 1), s));
         GSR_TRY(grow(ctx, ctx->det_sums, std::max<size_t>(4 * K * sums * sizeof(float), 1), s));
         da = {ctx->strip_rect.get(), ctx->det_slab.get(), ctx->det_sums.get(),
               ctx->det_marks.get(), (uint32_t)K};
     }
-    GSR_TRY(mark(1));
-    if (deterministic) {
+    GSR_TRY(backward_mark(ctx, p, 1));
+    if (p.det) {
         if (da.K > 0)
             GSR_HIP(hipMemsetAsync(da.marks, 0, 4 * (size_t)da.K, s), "hipMemsetAsync(marks)");
         GSR_HIP(gsr_launch_slab_scan(da.strip_rect, P, ctx->det_partials.get(),
@@ -1716,7 +1782,7 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     ba.grid_x = l.gx;
     ba.n_tiles = l.gx * (l.re - l.rb);  // (the whole frame: l.gy rows)
     ba.bg = st->bg;
-    ba.dL_dcolor = in->dL_dcolor;
+    ba.dL_dcolor = rq.in->dL_dcolor;
     ba.id_mask = l.id_mask;
     ba.cull = ctx->cull;
     ba.grad2d = ctx->grad2d.get();
@@ -1724,30 +1790,38 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
         // z by Gaussian id from the rebuild's depth keys, as launch_blend hands them to the
         // forward's planes: written by the rebuild's preprocess on s and only read since
         GsrPlaneBwdArgs pa{};
-        if (planes)
-            pa = {ctx->sort_keys.get(), pl->dL_ddepth_map, pl->dL_dinv_depth_map,
-                  pl->dL_dfinal_T};
-        if (deterministic)
-            GSR_HIP(gsr_launch_blend_bwd_det(ba, planes ? &pa : nullptr, da, s, sp),
+        if (p.planes)
+            pa = {ctx->sort_keys.get(), rq.planes->dL_ddepth_map, rq.planes->dL_dinv_depth_map,
+                  rq.planes->dL_dfinal_T};
+        // (neither: a feature gradient alone, no colour pass)
+        if (p.planes || ba.dL_dcolor)
+            GSR_HIP(gsr_launch_blend_bwd(ba, p.planes ? &pa : nullptr, p.det ? &da : nullptr, sp,
+                                         s),
                     "blend backward launch");
-        else if (planes)
-            GSR_HIP(gsr_launch_blend_bwd_planes(ba, pa, s, sp), "blend backward launch");
-        else if (ba.dL_dcolor)  // (NULL: a feature gradient alone, no colour pass)
-            GSR_HIP(gsr_launch_blend_bwd(ba, s, sp), "blend backward launch");
         // gsr_backward_features: beside the pass above, into the same zeroed rows
         if (ft)
             GSR_HIP(gsr_launch_blend_bwd_features(ba, ft->features, ft->C, ft->dL_dfeature_map,
                                                   ft->dL_dfeatures, s, sp),
                     "feature blend backward launch");
     }
-    if (deterministic)  // every word of every row, zeros where nothing was stored
-        GSR_HIP(gsr_launch_grad_rows_gather(da, P, planes, ctx->grad2d.get(), s),
+    if (p.det)  // every word of every row, zeros where nothing was stored
+        GSR_HIP(gsr_launch_grad_rows_gather(da, P, p.planes, ctx->grad2d.get(), s),
                 "gradient rows gather launch");
-    GSR_TRY(mark(2));
-    GSR_TRY(stage_check("stage blend backward"));
+    GSR_TRY(backward_mark(ctx, p, 2));
+    return backward_stage_check(rq, p, "stage blend backward");
+}
+
+// The third timed stage, the per-Gaussian backward: the caller's gradients from ctx->grad2d's rows.
+static int backward_gaussians(gsr_context *ctx, const BackwardRequest &rq, const BackwardPlan &p) {
+    const gsr_gaussians *g = rq.g;
+    const gsr_raster_settings *st = rq.st;
+    const gsr_gradients *gr = rq.gr;
+    const int64_t P = g->P;
+    hipStream_t s = p.s;
+    const gsr_context::LastFrame &l = ctx->last;
     // a proper subset of the rows: the Gaussians without a tile in it read as culled from here on
     // (the strip (0, grid_y) gates nothing: the whole frame's per-Gaussian stage, bit for bit)
-    if (strip && l.re - l.rb < l.gy)
+    if (p.strip && l.re - l.rb < l.gy)
         GSR_HIP(gsr_launch_strip_gate(ctx->strip_rect.get(), P, ctx->bwd_radii.get(), s),
                 "strip gate launch");
 
@@ -1782,90 +1856,96 @@ static int backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_s
     pb.dL_dscales = gr->dL_dscales;
     pb.dL_drotations = gr->dL_drotations;
     pb.dL_dcov3D = gr->dL_dcov3D;
+    float *const dL_ddepths = rq.planes ? rq.planes->dL_ddepths : nullptr;
     GsrPreprocessBwdExtras extras;
-    extras.planes = planes;
+    extras.planes = p.planes;
     extras.dL_ddepths = dL_ddepths;
     // (an empty list leaves the rows zero: every product, and so every sum of the camera's, is 0)
     GsrCameraBwdArgs ca{};
-    if (camera) {
-        ca = {ctx->cam_partials.get(), cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos};
+    if (p.camera) {
+        ca = {ctx->cam_partials.get(), rq.camera->dL_dviewmatrix, rq.camera->dL_dprojmatrix,
+              rq.camera->dL_dcampos};
         extras.camera = &ca;
     }
     // gsr_backward_filtered: the antialiased twins, which also read the opacities
-    extras.aa_opacities = antialiasing ? g->opacities : nullptr;
+    extras.aa_opacities = p.aa ? g->opacities : nullptr;
     GSR_HIP(gsr_launch_preprocess_bwd(pb, extras, s), "per-Gaussian backward launch");
-    if (!planes && dL_ddepths)  // no plane gradient: nothing reaches the features
+    if (!p.planes && dL_ddepths)  // no plane gradient: nothing reaches the features
         GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
                 "hipMemsetAsync(dL_ddepths)");
-    GSR_TRY(mark(3));
-    ctx->bwd_timed = timing != 0;
-    return stage_check("stage per-Gaussian backward");
+    GSR_TRY(backward_mark(ctx, p, 3));
+    ctx->bwd_timed = ctx->timing != 0;
+    return backward_stage_check(rq, p, "stage per-Gaussian backward");
+}
+
+// Every public backward: the request's parse and checks, the context's lock, the stream's order,
+// the three timed stages.
+static int backward_entry(gsr_context *ctx, void *stream, const BackwardRequest &rq) {
+    BackwardPlan p;
+    GSR_TRY(backward_parse(ctx, rq, p));
+    GSR_TRY(backward_validate(ctx, rq, p));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    p.s = static_cast<hipStream_t>(stream);
+    GSR_TRY(order_stream(ctx, p.s));
+    if (rq.g->P == 0) {  // no Gaussian, no gradient: the camera's buffers, of a fixed size, are zeros
+        if (p.camera) {
+            const struct {
+                float *p;
+                size_t n;
+                const char *what;
+            } sums[] = {{rq.camera->dL_dviewmatrix, 16, "hipMemsetAsync(dL_dviewmatrix)"},
+                        {rq.camera->dL_dprojmatrix, 16, "hipMemsetAsync(dL_dprojmatrix)"},
+                        {rq.camera->dL_dcampos, 3, "hipMemsetAsync(dL_dcampos)"}};
+            for (const auto &m : sums)
+                if (m.p) GSR_HIP(hipMemsetAsync(m.p, 0, m.n * sizeof(float), p.s), m.what);
+        }
+        return GSR_OK;
+    }
+    GSR_TRY(backward_reserve(ctx, rq, p));
+    GSR_TRY(backward_rebuild(ctx, rq, p));
+    GSR_TRY(backward_blend(ctx, rq, p));
+    return backward_gaussians(ctx, rq, p);
 }
 
 int gsr_backward(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                  const gsr_backward_inputs *in, gsr_gradients *gr, void *stream) {
-    return backward(ctx, g, st, in, nullptr, nullptr, gr, stream, "gsr_backward");
+    return backward_entry(ctx, stream, {"gsr_backward", g, st, in, gr});
 }
 
 int gsr_backward_planes(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         gsr_gradients *gr, void *stream) {
-    return backward(ctx, g, st, in, planes, nullptr, gr, stream, "gsr_backward_planes");
+    return backward_entry(ctx, stream, {"gsr_backward_planes", g, st, in, gr, planes});
 }
 
 int gsr_backward_camera(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                         const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                         const gsr_camera_gradients *camera, gsr_gradients *gr, void *stream) {
-    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_camera");
+    return backward_entry(ctx, stream, {"gsr_backward_camera", g, st, in, gr, planes, camera});
 }
 
 int gsr_backward_filtered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                           const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                           const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                           gsr_gradients *gr, void *stream) {
-    const int aa = filter_antialiasing(filter);
-    if (aa < 0)
-        return fail(GSR_E_INVALID, "gsr_backward_filtered: antialiasing must be 0 or 1, got " +
-                                       std::to_string(filter->antialiasing));
-    if (!aa) return gsr_backward_camera(ctx, g, st, in, planes, camera, gr, stream);
-    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_filtered", true);
+    return backward_entry(ctx, stream,
+                          {"gsr_backward_camera", g, st, in, gr, planes, camera, filter});
 }
 
 int gsr_backward_ordered(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                          const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                          const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                          const gsr_backward_order *order, gsr_gradients *gr, void *stream) {
-    const int det = order ? order->deterministic : 0;
-    if (det != 0 && det != 1)
-        return fail(GSR_E_INVALID, "gsr_backward_ordered: deterministic must be 0 or 1, got " +
-                                       std::to_string(det));
-    if (!det) return gsr_backward_filtered(ctx, g, st, in, planes, camera, filter, gr, stream);
-    const int aa = filter_antialiasing(filter);
-    if (aa < 0)
-        return fail(GSR_E_INVALID, "gsr_backward_ordered: antialiasing must be 0 or 1, got " +
-                                       std::to_string(filter->antialiasing));
-    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_ordered", aa != 0,
-                    true);
+    return backward_entry(ctx, stream,
+                          {"gsr_backward_camera", g, st, in, gr, planes, camera, filter, order});
 }
 
 int gsr_backward_strip(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
                        const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
                        const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                        const gsr_backward_order *order, gsr_gradients *gr, void *stream) {
-    if (!ctx || !g || !st || !in || !gr)
-        return fail(GSR_E_INVALID, "gsr_backward_strip: NULL argument");
-    if (st->tile_row_begin == 0 && st->tile_row_end == 0)
-        return gsr_backward_ordered(ctx, g, st, in, planes, camera, filter, order, gr, stream);
-    const int det = order ? order->deterministic : 0;
-    if (det != 0 && det != 1)
-        return fail(GSR_E_INVALID, "gsr_backward_strip: deterministic must be 0 or 1, got " +
-                                       std::to_string(det));
-    const int aa = filter_antialiasing(filter);
-    if (aa < 0)
-        return fail(GSR_E_INVALID, "gsr_backward_strip: antialiasing must be 0 or 1, got " +
-                                       std::to_string(filter->antialiasing));
-    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_strip", aa != 0,
-                    det != 0, true);
+    return backward_entry(ctx, stream, {"gsr_backward_camera", g, st, in, gr, planes, camera,
+                                        filter, order, nullptr, true});
 }
 
 int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
@@ -1873,27 +1953,8 @@ int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_ra
                           const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                           const gsr_backward_order *order, const gsr_feature_gradients *feat,
                           gsr_gradients *gr, void *stream) {
-    if (!feat || !feat->dL_dfeature_map)
-        return gsr_backward_strip(ctx, g, st, in, planes, camera, filter, order, gr, stream);
-    if (!ctx || !g || !st || !in || !gr)
-        return fail(GSR_E_INVALID, "gsr_backward_features: NULL argument");
-    if (const char *why = feature_fault(feat->C, feat->features, g->P))
-        return fail(GSR_E_INVALID, std::string("gsr_backward_features: ") + why + " (C = " +
-                                       std::to_string(feat->C) + ")");
-    const int det = order ? order->deterministic : 0;
-    if (det == 1)
-        return fail(GSR_E_INVALID,
-                    "gsr_backward_features: deterministic == 1 with a feature gradient: the "
-                    "deterministic slots hold 9 or 10 sums and have no room for C more");
-    if (det != 0)
-        return fail(GSR_E_INVALID, "gsr_backward_features: deterministic must be 0 or 1, got " +
-                                       std::to_string(det));
-    const int aa = filter_antialiasing(filter);
-    if (aa < 0)
-        return fail(GSR_E_INVALID, "gsr_backward_features: antialiasing must be 0 or 1, got " +
-                                       std::to_string(filter->antialiasing));
-    return backward(ctx, g, st, in, planes, camera, gr, stream, "gsr_backward_features", aa != 0,
-                    false, true, feat);
+    return backward_entry(ctx, stream, {"gsr_backward_camera", g, st, in, gr, planes, camera,
+                                        filter, order, feat, true});
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

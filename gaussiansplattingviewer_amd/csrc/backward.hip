@@ -890,28 +890,30 @@ static bool strip_ok(const GsrBlendBwdArgs &a, const GsrStripBwdArgs *r) {
     return r->y0 < a.H && r->rows_out == (int)std::min<int64_t>(a.H, end) - r->y0;
 }
 
-hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s,
-                                const GsrStripBwdArgs *strip) {
-    if (a.n_tiles == 0) return hipSuccess;
-    if (!a.dL_dcolor || !strip_ok(a, strip)) return hipErrorInvalidValue;
-    if (strip)
-        hipLaunchKernelGGL(k_blend_bwd_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, *strip);
-    else
-        hipLaunchKernelGGL(k_blend_bwd_q, dim3(a.n_tiles), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
-                                       hipStream_t s, const GsrStripBwdArgs *strip) {
-    if (!p.z_bits || (!p.dL_ddepth_map && !p.dL_dinv_depth_map && !p.dL_dfinal_T))
+hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
+                                const GsrDetBwdArgs *d, const GsrStripBwdArgs *strip,
+                                hipStream_t s) {
+    if (p && (!p->z_bits || (!p->dL_ddepth_map && !p->dL_dinv_depth_map && !p->dL_dfinal_T)))
+        return hipErrorInvalidValue;
+    const bool no_gradient = !p && !a.dL_dcolor;
+    if (d && (no_gradient || !d->strip_rect || !d->slab || !d->sums || !d->marks ||
+              d->K >= (1u << 30)))
         return hipErrorInvalidValue;
     if (a.n_tiles == 0) return hipSuccess;
-    if (!strip_ok(a, strip)) return hipErrorInvalidValue;
-    if (strip)
-        hipLaunchKernelGGL(k_blend_bwd_planes_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, p,
-                           *strip);
-    else
-        hipLaunchKernelGGL(k_blend_bwd_planes_q, dim3(a.n_tiles), dim3(256), 0, s, a, p);
+    if (no_gradient || !strip_ok(a, strip)) return hipErrorInvalidValue;
+    auto launch = [&](auto kernel, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3(a.n_tiles), dim3(256), 0, s, a, more...);
+    };
+    switch ((p ? 1 : 0) | (d ? 2 : 0) | (strip ? 4 : 0)) {
+        case 0: launch(k_blend_bwd_q); break;
+        case 1: launch(k_blend_bwd_planes_q, *p); break;
+        case 2: launch(k_blend_bwd_det_q, *d); break;
+        case 3: launch(k_blend_bwd_planes_det_q, *p, *d); break;
+        case 4: launch(k_blend_bwd_strip_q, *strip); break;
+        case 5: launch(k_blend_bwd_planes_strip_q, *p, *strip); break;
+        case 6: launch(k_blend_bwd_det_strip_q, *d, *strip); break;
+        case 7: launch(k_blend_bwd_planes_det_strip_q, *p, *d, *strip); break;
+    }
     return hipGetLastError();
 }
 
@@ -948,29 +950,6 @@ hipError_t gsr_launch_blend_bwd_features(const GsrBlendBwdArgs &a, const float *
         ft.c0 += w;
     }
     return hipSuccess;
-}
-
-hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
-                                    const GsrDetBwdArgs &d, hipStream_t s,
-                                    const GsrStripBwdArgs *strip) {
-    if (p && (!p->z_bits || (!p->dL_ddepth_map && !p->dL_dinv_depth_map && !p->dL_dfinal_T)))
-        return hipErrorInvalidValue;
-    if (!p && !a.dL_dcolor) return hipErrorInvalidValue;
-    if (!d.strip_rect || !d.slab || !d.sums || !d.marks || d.K >= (1u << 30))
-        return hipErrorInvalidValue;
-    if (a.n_tiles == 0) return hipSuccess;
-    if (!strip_ok(a, strip)) return hipErrorInvalidValue;
-    if (p && strip)
-        hipLaunchKernelGGL(k_blend_bwd_planes_det_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, *p,
-                           d, *strip);
-    else if (strip)
-        hipLaunchKernelGGL(k_blend_bwd_det_strip_q, dim3(a.n_tiles), dim3(256), 0, s, a, d,
-                           *strip);
-    else if (p)
-        hipLaunchKernelGGL(k_blend_bwd_planes_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, *p, d);
-    else
-        hipLaunchKernelGGL(k_blend_bwd_det_q, dim3(a.n_tiles), dim3(256), 0, s, a, d);
-    return hipGetLastError();
 }
 
 hipError_t gsr_launch_strip_gate(const uint2 *strip_rect, int64_t P, int32_t *radii,

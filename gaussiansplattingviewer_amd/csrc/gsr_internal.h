@@ -651,14 +651,12 @@ struct GsrBlendBwdArgs {
 // its global tile row) while a.dL_dcolor ([3, rows_out, W]) and the plane gradients ([rows_out, W])
 // are strip-local, read at (py - y0) * W + px, as blend.hip writes the forward's strip.  The
 // deterministic slot takes the strip-local tile row against the strip-local strip_rect.  Passed to
-// the three launchers below it selects the k_blend_bwd*_strip_q instantiations; NULL launches the
+// the two launchers below it selects the k_blend_bwd*_strip_q instantiations; NULL launches the
 // whole-frame kernels, which have no such argument (profiles/backward_strips_resources.txt).
 struct GsrStripBwdArgs {
     uint32_t row_begin;
     int y0, rows_out;
 };
-hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, hipStream_t s,
-                                const GsrStripBwdArgs *strip = nullptr);
 // gsr_backward_planes (k_blend_bwd_planes_q): the gradients of depth_map, inv_depth_map and
 // final_T ([H, W] each, any NULL but not all) beside a.dL_dcolor, which may then be NULL.  z_bits:
 // per Gaussian, the bits of its view-space z (the rebuild's depth keys, as GsrDepthArgs).  The
@@ -667,8 +665,6 @@ struct GsrPlaneBwdArgs {
     const uint32_t *z_bits;
     const float *dL_ddepth_map, *dL_dinv_depth_map, *dL_dfinal_T;
 };
-hipError_t gsr_launch_blend_bwd_planes(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
-                                       hipStream_t s, const GsrStripBwdArgs *strip = nullptr);
 // gsr_backward_features (k_blend_bwd_features_q): launches of their own beside the colour / planes
 // blend-backward, per chunk of 16, 8 or 4 channels (the forward's rule), over the same lists.
 // A launch carries the recursion for its own channels (the start value is 0: no background), adds
@@ -696,9 +692,15 @@ struct GsrDetBwdArgs {
     uint8_t *marks;
     uint32_t K;
 };
-hipError_t gsr_launch_blend_bwd_det(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
-                                    const GsrDetBwdArgs &d, hipStream_t s,
-                                    const GsrStripBwdArgs *strip = nullptr);
+// The blend's backward, one of the eight k_blend_bwd*_q: with the planes (p), the deterministic
+// slots (d) and a strip, each NULL for without.  hipErrorInvalidValue without a gradient to read
+// (a.dL_dcolor NULL and no p), for a p without z_bits or without any of its three gradients, a d
+// with a NULL buffer or K >= 2^30, or a strip that does not describe rows of the frame.  An empty
+// grid (a.n_tiles == 0) launches nothing and is hipSuccess, whatever the strip; without d it also
+// comes before the missing a.dL_dcolor.
+hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
+                                const GsrDetBwdArgs *d, const GsrStripBwdArgs *strip,
+                                hipStream_t s);
 // slab[i] = sum over j < i of w_j * rows_j (strip_rect, 0 for a Gaussian without a rect), 64-bit;
 // partials: workspace of gsr_slab_blocks(P) uint64.  P == 0 launches nothing.
 int64_t gsr_slab_blocks(int64_t P);

@@ -26,8 +26,8 @@
 //                              tile_row_begin = 0, tile_row_end = 0)
 //       -> (num_rendered, color, radii, depth_map [H,W], inv_depth_map [H,W], final_T [H,W])
 //     this package's own, every forward in one entry (GaussianRasterizationSettings.shading,
-//     .depth_maps, .antialiasing).  A shading, or the plain splat frame: gsr_forward_shaded.
-//     Anything else: gsr_forward_filtered, with the depth planes and final_T only if `planes`
+//     .depth_maps, .antialiasing).  A shading: gsr_forward_shaded.  The splat composite:
+//     gsr_forward_features without features, with the depth planes and final_T only if `planes`
 //     (without, the three tensors are empty and nothing of them is rendered) and a filter only if
 //     `antialiasing` (the effective opacity of the 0.3-pixel dilation's compensation).  With a
 //     strip of tile rows (the two trailing arguments, not both 0; they may be left out) the image
@@ -40,17 +40,17 @@
 //                                       deterministic = False)
 //       -> rasterize_gaussians_backward's 8-tuple, then dL_dviewmatrix [4,4], dL_dprojmatrix
 //          [4,4], dL_dcampos [3] (empty without `camera`)
-//     this package's own, every backward in one entry: gsr_backward_filtered, with the plane
-//     gradients only if one of the three is not empty (an empty gradient tensor is an unused
-//     one), the camera's only if `camera`, a filter only if `antialiasing`; with
-//     `deterministic` gsr_backward_ordered, whose gradients have the same bits on every call
+//     this package's own, every backward in one entry: gsr_backward_features without features
+//     (which is every entry below it), with the plane gradients only if one of the three is not
+//     empty (an empty gradient tensor is an unused one), the camera's only if `camera`, a filter
+//     only if `antialiasing`; with `deterministic` the gradients have the same bits on every call
 //     (the trailing argument may be left out: the 22-argument call is unchanged).  The two matrices'
 //     gradients are in the inputs' layout (the 16 floats of the input, viewed (4, 4)).
 //   _C.rasterize_gaussians_backward_strip_ext(<rasterize_gaussians_backward_ext's 23 arguments>,
 //                                             tile_row_begin, tile_row_end, image_height)
 //       -> the same 11-tuple
-//     this package's own: gsr_backward_strip, the backward on a strip of tile rows (not both 0) in
-//     either mode.  The image and plane gradients are strip-local, [3, rows, W] and [rows, W], and
+//     this package's own: the same call on a strip of tile rows (not both 0; gsr_backward_strip's
+//     request) in either mode.  The image and plane gradients are strip-local, [3, rows, W] and [rows, W], and
 //     image_height gives the frame's height, which they no longer tell; the gradients stay
 //     whole-scene.  (An entry of its own: rasterize_gaussians_backward_ext keeps its signature.)
 //   _C.rasterize_gaussians_features(<rasterize_gaussians' 19 arguments>, planes, antialiasing,
@@ -282,13 +282,12 @@ Forward6 forward_impl(const Inputs &in, int64_t frame_H, int64_t W, int64_t shad
         int rc;
         {  // the forward waits for K (pinned memory): other Python threads may run meanwhile
             pybind11::gil_scoped_release no_gil;
-            rc = features
-                     ? gsr_forward_features(ctx, &sc.g, &sc.st, &out, planes ? &d : nullptr,
-                                            nullptr, antialiasing ? &fs : nullptr, &fo, s)
-                 : planes || antialiasing
-                     ? gsr_forward_filtered(ctx, &sc.g, &sc.st, &out, planes ? &d : nullptr,
-                                            nullptr, antialiasing ? &fs : nullptr, s)
-                     : gsr_forward_shaded(ctx, &sc.g, &sc.st, &out, (int32_t)shading, s);
+            // (gsr_forward_features with NULLs is every splat forward below it)
+            rc = shading != GSR_SHADE_SPLAT
+                     ? gsr_forward_shaded(ctx, &sc.g, &sc.st, &out, (int32_t)shading, s)
+                     : gsr_forward_features(ctx, &sc.g, &sc.st, &out, planes ? &d : nullptr,
+                                            nullptr, antialiasing ? &fs : nullptr,
+                                            features ? &fo : nullptr, s);
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_forward failed (", rc, "): ", gsr_last_error());
         num_rendered = out.num_rendered;
@@ -461,24 +460,12 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         int rc;
         {  // the rebuild waits for K (pinned memory), as the forward does
             pybind11::gil_scoped_release no_gil;
-            if (features)  // gsr_backward_features: a strip or a frame; refuses deterministic
+            if (upstream && !features)
+                rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
+            else  // with NULLs and a 0 every entry below it; refuses deterministic with features
                 rc = gsr_backward_features(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
                                            camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
-                                           &order, &fg, &gr, s);
-            else if (upstream)
-                rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
-            else if (strip)  // gsr_backward_strip: the strip's loss, in either mode
-                rc = gsr_backward_strip(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
-                                        camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
-                                        &order, &gr, s);
-            else if (deterministic)  // gsr_backward_ordered: bit-reproducible sums
-                rc = gsr_backward_ordered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
-                                          camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
-                                          &order, &gr, s);
-            else
-                rc = gsr_backward_filtered(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
-                                           camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
-                                           &gr, s);
+                                           &order, features ? &fg : nullptr, &gr, s);
         }
         TORCH_CHECK(rc == GSR_OK, "gsr_backward failed (", rc, "): ", gsr_last_error());
     }

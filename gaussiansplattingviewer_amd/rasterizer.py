@@ -334,33 +334,52 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     lib = _lib.load_library()
     ctx = _lib.context(dev_index, slot)
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(out))
+    # the optional structs, NULL for each the call does without
+    structs = _refs(
+        depth_planes and _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes}),
+        surface_planes and _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr()
+                                                     for n in surface_planes}),
+        antialiasing and _lib.GsrFilterSettings(antialiasing=int(antialiasing)),
+        features is not None and _lib.GsrFeatureOutputs(
+            C=int(features.size(1)), features=_lib.ptr(features),
+            feature_map=feature_map.data_ptr()))
     with torch.cuda.device(dev_index):
         if shading != _lib.GSR_SHADE_SPLAT:
             _lib.check(lib.gsr_forward_shaded(*head, int(shading), ctypes.c_void_p(stream)),
                        "gsr_forward_shaded")
-        elif features is not None:  # NULL for each struct the call does without
-            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
-            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
-            feat = _lib.GsrFeatureOutputs(C=int(features.size(1)), features=_lib.ptr(features),
-                                          feature_map=feature_map.data_ptr())
-            _lib.check(_lib.features_fns(lib)[0](
-                *head, ctypes.byref(planes) if depth_planes else None,
-                ctypes.byref(surface) if surface_planes else None,
-                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
-                if antialiasing else None,
-                ctypes.byref(feat), ctypes.c_void_p(stream)), "gsr_forward_features")
-        elif not (depth_planes or surface_planes or antialiasing):
-            _lib.check(lib.gsr_forward(*head, ctypes.c_void_p(stream)), "gsr_forward")
-        else:  # NULL for each struct the call does without
-            planes = _lib.GsrDepthOutputs(**{n: ext[n].data_ptr() for n in depth_planes})
-            surface = _lib.GsrSurfaceOutputs(**{n: ext[n].data_ptr() for n in surface_planes})
-            _lib.check(_lib.filtered_fns(lib)[0](
-                *head, ctypes.byref(planes) if depth_planes else None,
-                ctypes.byref(surface) if surface_planes else None,
-                ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
-                if antialiasing else None,
-                ctypes.c_void_p(stream)), "gsr_forward_filtered")
+        else:
+            name, fn, n = _lowest_entry(_FORWARD_ENTRIES, lib, structs)
+            _lib.check(fn(*head, *structs[:n], ctypes.c_void_p(stream)), name)
     return ForwardResult(int(out.num_rendered), color, radii, ext, feature_map)
+
+
+def _refs(*structs):
+    """ctypes.byref of each struct; None for anything else (a struct the call does without)."""
+    return tuple(ctypes.byref(s) if isinstance(s, ctypes.Structure) else None for s in structs)
+
+
+# The entries the ctypes path calls, lowest first: (name, its accessor, how many of the top entry's
+# optional structs it takes, whether a backward honours a tile row strip).  The lowest entry that
+# can express a request is called, so an older build of ABI 4 loaded through GSR_LIB serves every
+# request it has an entry for.
+_FORWARD_ENTRIES = (
+    ("gsr_forward", lambda lib: lib.gsr_forward, 0, True),
+    ("gsr_forward_filtered", lambda lib: _lib.filtered_fns(lib)[0], 3, True),
+    ("gsr_forward_features", lambda lib: _lib.features_fns(lib)[0], 4, True))
+_BACKWARD_ENTRIES = (
+    ("gsr_backward", _lib.backward_fn, 0, False),
+    ("gsr_backward_filtered", lambda lib: _lib.filtered_fns(lib)[1], 3, False),
+    ("gsr_backward_ordered", _lib.backward_ordered_fn, 4, False),
+    ("gsr_backward_strip", _lib.backward_strip_fn, 4, True),
+    ("gsr_backward_features", lambda lib: _lib.features_fns(lib)[1], 5, True))
+
+
+def _lowest_entry(entries, lib, structs, strip=False):
+    """(name, function, number of optional structs it takes) of the lowest of `entries` that takes
+    the last struct of `structs` that is not None, and a strip if there is one."""
+    used = max((i + 1 for i, s in enumerate(structs) if s is not None), default=0)
+    return next((name, accessor(lib), n) for name, accessor, n, strips in entries
+                if n >= used and (strips or not strip))
 
 
 def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, scales, rotations,
@@ -476,47 +495,24 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
-    d_feat = None
     if features is not None:
-        d_feat = torch.zeros((P, features.size(1)), **f32)
+        d_feat = grads["dL_dfeatures"] = torch.zeros((P, features.size(1)), **f32)
         d_map = _as_dev(dL_dfeature_map, device, "C,H,W")
+    # the optional structs, NULL for each the call does without
+    structs = _refs(
+        (plane_grads or depths) and _lib.GsrPlaneGradients(
+            **{n: _lib.ptr(t) for n, t in plane_grads.items()},
+            dL_ddepths=_lib.ptr(grads.get("dL_ddepths"))),
+        camera and _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()}),
+        antialiasing and _lib.GsrFilterSettings(antialiasing=int(antialiasing)),
+        deterministic and _lib.GsrBackwardOrder(deterministic=int(deterministic)),
+        features is not None and _lib.GsrFeatureGradients(
+            C=int(features.size(1)), features=_lib.ptr(features),
+            dL_dfeature_map=_lib.ptr(d_map), dL_dfeatures=_lib.ptr(d_feat)))
     with torch.cuda.device(dev_index):
-        if not (plane_grads or depths or camera or antialiasing or deterministic or re or
-                features is not None):
-            _lib.check(_lib.backward_fn(lib)(*head, ctypes.byref(out), ctypes.c_void_p(stream)),
-                       "gsr_backward")
-        else:  # NULL for each struct the call does without
-            planes = _lib.GsrPlaneGradients(**{n: _lib.ptr(t) for n, t in plane_grads.items()},
-                                            dL_ddepths=_lib.ptr(grads.get("dL_ddepths")))
-            cg = _lib.GsrCameraGradients(**{n: _lib.ptr(t) for n, t in cam.items()})
-            structs = (ctypes.byref(planes) if plane_grads or depths else None,
-                       ctypes.byref(cg) if camera else None,
-                       ctypes.byref(_lib.GsrFilterSettings(antialiasing=int(antialiasing)))
-                       if antialiasing else None)
-            if features is not None:
-                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
-                feat = _lib.GsrFeatureGradients(
-                    C=int(features.size(1)), features=_lib.ptr(features),
-                    dL_dfeature_map=_lib.ptr(d_map), dL_dfeatures=_lib.ptr(d_feat))
-                _lib.check(_lib.features_fns(lib)[1](
-                    *head, *structs, ctypes.byref(order), ctypes.byref(feat), ctypes.byref(out),
-                    ctypes.c_void_p(stream)), "gsr_backward_features")
-                grads["dL_dfeatures"] = d_feat
-            elif re:
-                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
-                _lib.check(_lib.backward_strip_fn(lib)(
-                    *head, *structs, ctypes.byref(order), ctypes.byref(out),
-                    ctypes.c_void_p(stream)), "gsr_backward_strip")
-            elif deterministic:
-                order = _lib.GsrBackwardOrder(deterministic=int(deterministic))
-                _lib.check(_lib.backward_ordered_fn(lib)(
-                    *head, *structs, ctypes.byref(order), ctypes.byref(out),
-                    ctypes.c_void_p(stream)), "gsr_backward_ordered")
-            else:
-                _lib.check(_lib.filtered_fns(lib)[1](
-                    *head, *structs, ctypes.byref(out), ctypes.c_void_p(stream)),
-                    "gsr_backward_filtered")
-            grads.update(cam)
+        name, fn, n = _lowest_entry(_BACKWARD_ENTRIES, lib, structs, strip=bool(re))
+        _lib.check(fn(*head, *structs[:n], ctypes.byref(out), ctypes.c_void_p(stream)), name)
+    grads.update(cam)
     return grads
 
 
@@ -587,30 +583,34 @@ def _saved(args):
     return args[1], args[14], args[2], args[3], args[4], args[5], args[7]
 
 
-def _forward(args, rs, planes: bool):
-    """One frame of `_pack`'s arguments -> (num_rendered, color, radii, planes): PLANE_NAMES'
-    tensors, or () without `planes`.  Through `_C`: upstream's entry for the plain frame, its
-    shaded twin, the general entry for the rest; under GSR_LIB (an A/B build: `_C` links the
+def _forward(args, rs, planes: bool, features=None):
+    """One frame of `_pack`'s arguments -> (num_rendered, color, radii, planes, feature_map):
+    PLANE_NAMES' tensors, or () without `planes`; feature_map (C, rows, W) of `features` (P, C),
+    or None without.  Through `_C`: upstream's entry for the plain frame, its shaded twin, the
+    features' entry, the general entry for the rest; under GSR_LIB (an A/B build: `_C` links the
     in-tree library) by ctypes."""
     strip = getattr(rs, "tile_rows", None)
     if not _lib._native_shares_library():
         res = rasterize_gaussians_native(*args, extras=PLANE_NAMES if planes else (),
                                          shading=rs.shading, antialiasing=rs.antialiasing,
-                                         tile_rows=strip)
+                                         tile_rows=strip, features=features)
         return (res.num_rendered, res.color, res.radii,
-                tuple(res.extras[n] for n in PLANE_NAMES) if planes else ())
+                tuple(res.extras[n] for n in PLANE_NAMES) if planes else (), res.feature_map)
     from . import _C
-    if planes or rs.antialiasing or strip:
-        if strip:  # (checked here for the message; the entry checks it again)
-            _strip_rows(strip, int(rs.image_height))
+    if strip:  # (checked here for the message; the entry checks it again)
+        _strip_rows(strip, int(rs.image_height))
+    feature_map = None
+    if features is not None:
+        num_rendered, color, radii, *maps, feature_map = _C.rasterize_gaussians_features(
+            *args, planes, bool(rs.antialiasing), *(strip or (0, 0)), features)
+    elif planes or rs.antialiasing or strip:
         num_rendered, color, radii, *maps = _C.rasterize_gaussians_ext(
             *args, int(rs.shading), planes, bool(rs.antialiasing), *(strip or ()))
-        return num_rendered, color, radii, tuple(maps) if planes else ()
-    if rs.shading:  # upstream's 19 arguments and the shading
-        num_rendered, color, radii, *_ = _C.rasterize_gaussians_shaded(*args, int(rs.shading))
+    elif rs.shading:  # upstream's 19 arguments and the shading
+        num_rendered, color, radii, *maps = _C.rasterize_gaussians_shaded(*args, int(rs.shading))
     else:
-        num_rendered, color, radii, *_ = _C.rasterize_gaussians(*args)
-    return num_rendered, color, radii, ()
+        num_rendered, color, radii, *maps = _C.rasterize_gaussians(*args)
+    return num_rendered, color, radii, tuple(maps) if planes else (), feature_map
 
 
 _GRADIENT_ORDER = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D",
@@ -624,7 +624,23 @@ def _deterministic(rs) -> bool:
     return torch.are_deterministic_algorithms_enabled() if det is None else bool(det)
 
 
-def _backward(rs, saved, grads, camera=None):
+def _refuse_deterministic_features(rs):
+    """The deterministic mode has no feature sums (gsr_backward_features refuses it): the setting
+    raises; torch's global switch raises too, or with warn_only warns and runs the atomic sums."""
+    what = ("the deterministic backward has no feature channels: its slots hold 9 or 10 sums per "
+            "(Gaussian, tile, quadrant) and have no room for C more")
+    if getattr(rs, "deterministic", None):
+        raise RuntimeError(f"GaussianRasterizationSettings(deterministic=True) with features: {what}")
+    if getattr(rs, "deterministic", None) is None and torch.are_deterministic_algorithms_enabled():
+        if not torch.is_deterministic_algorithms_warn_only_enabled():
+            raise RuntimeError(f"torch.use_deterministic_algorithms(True) with features: {what} "
+                               "(deterministic=False in the settings runs the atomic sums)")
+        import warnings
+        warnings.warn(f"gaussiansplattingviewer_amd: {what}; the sums over pixels are float "
+                      "atomics in this backward", UserWarning, stacklevel=3)
+
+
+def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=None):
     """The gradients of one frame.  saved: `_saved`'s seven; grads: those of (color, depth_map,
     inv_depth_map, final_T), None = unused; camera: None, or the (viewmatrix, projmatrix, campos)
     to differentiate by, which the frame was rendered with.  Returns `_GRADIENT_ORDER`'s eleven,
@@ -632,9 +648,17 @@ def _backward(rs, saved, grads, camera=None):
     image's gradient is asked for, else the general one; under GSR_LIB by ctypes.  In the
     deterministic mode (`_deterministic`) the general entry with a 23rd argument, True; on a
     strip (rs.tile_rows) the strip's entry, whose three more are the strip's rows and the frame's
-    height."""
+    height.  With `features` (the frame's feature rows) and grad_feature_map, its planes' gradient
+    or None, a twelfth follows: dL_dfeatures, through the features' entry, which has no
+    deterministic mode (`_refuse_deterministic_features`)."""
     means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
     det = _deterministic(rs)
+    if features is not None:
+        _refuse_deterministic_features(rs)
+        if grad_feature_map is None:  # the loss does not read the feature planes
+            g = _backward(rs._replace(deterministic=False), saved, grads, camera)
+            return (*g, torch.zeros_like(features))
+        det = False
     strip = getattr(rs, "tile_rows", None)
     viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not _lib._native_shares_library():
@@ -644,12 +668,14 @@ def _backward(rs, saved, grads, camera=None):
             campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
             dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
             deterministic=det, tile_rows=strip,
-            image_height=None if strip is None else rs.image_height)
-        return tuple(g.get(n) for n in _GRADIENT_ORDER)
+            image_height=None if strip is None else rs.image_height,
+            features=features, dL_dfeature_map=grad_feature_map)
+        return tuple(g.get(n) for n in _GRADIENT_ORDER) + \
+            (() if features is None else (g["dL_dfeatures"],))
     from . import _C
     e = torch.empty(0)
     if (camera is None and not rs.antialiasing and not det and strip is None and
-            all(t is None for t in grads[1:])):
+            features is None and all(t is None for t in grads[1:])):
         # (radii, num_rendered and the three buffers: accepted and ignored)
         return _C.rasterize_gaussians_backward(
             rs.bg, means3D, e, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds,
@@ -658,14 +684,20 @@ def _backward(rs, saved, grads, camera=None):
     if camera is not None:
         viewmatrix, projmatrix, campos = (_as_dev(t.detach(), means3D.device, "")
                                           for t in camera)
-    entry = _C.rasterize_gaussians_backward_strip_ext if strip else \
-        _C.rasterize_gaussians_backward_ext
+    if features is not None:
+        entry = _C.rasterize_gaussians_backward_features
+        tail = (False, *(strip or (0, 0)), int(rs.image_height), features, grad_feature_map)
+    elif strip:
+        entry = _C.rasterize_gaussians_backward_strip_ext
+        tail = (det, *strip, int(rs.image_height))
+    else:
+        entry = _C.rasterize_gaussians_backward_ext
+        tail = (True,) if det else ()
     g = entry(
         rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
         viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
-        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing),
-        *((det, *strip, int(rs.image_height)) if strip else (True,) if det else ()))
-    return g if camera is not None else g[:8] + (None,) * 3
+        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing), *tail)
+    return g if camera is not None else g[:8] + (None,) * 3 + g[11:]
 
 
 def _input_grads(has_means2D, saved, g):
@@ -708,7 +740,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise RuntimeError("antialiasing belongs to the splat composite: not available with "
                                f"shading {rs.shading}")
         try:
-            num_rendered, color, radii, _ = _forward(args, rs, False)
+            num_rendered, color, radii, _, _ = _forward(args, rs, False)
         except Exception:
             if cpu_args is not None:
                 torch.save(cpu_args, SNAPSHOT_FILE)
@@ -751,7 +783,7 @@ class _RasterizeGaussiansPlanes(torch.autograd.Function):
         ctx.has_means2D = isinstance(means2D, torch.Tensor)
         args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
                      cov3Ds_precomp)
-        _, color, radii, planes = _forward(args, rs, True)
+        _, color, radii, planes, _ = _forward(args, rs, True)
         ctx.raster_settings = rs
         ctx.save_for_backward(*_saved(args))
         ctx.mark_non_differentiable(radii)
@@ -815,67 +847,6 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 like(g[10], campos) if need[11] else None)
 
 
-def _forward_features(args, rs, planes: bool, features):
-    """`_forward` with feature channels -> (num_rendered, color, radii, planes, feature_map);
-    through `_C.rasterize_gaussians_features`, under GSR_LIB by ctypes."""
-    strip = getattr(rs, "tile_rows", None)
-    if not _lib._native_shares_library():
-        res = rasterize_gaussians_native(*args, extras=PLANE_NAMES if planes else (),
-                                         antialiasing=rs.antialiasing, tile_rows=strip,
-                                         features=features)
-        return (res.num_rendered, res.color, res.radii,
-                tuple(res.extras[n] for n in PLANE_NAMES) if planes else (), res.feature_map)
-    from . import _C
-    if strip:
-        _strip_rows(strip, int(rs.image_height))
-    num_rendered, color, radii, *maps, feature_map = _C.rasterize_gaussians_features(
-        *args, planes, bool(rs.antialiasing), *(strip or (0, 0)), features)
-    return num_rendered, color, radii, tuple(maps) if planes else (), feature_map
-
-
-def _backward_features(rs, saved, grads, features, grad_feature_map, camera):
-    """`_backward` with feature channels: `_GRADIENT_ORDER`'s eleven, then dL_dfeatures.  The
-    deterministic mode has no feature sums (gsr_backward_features refuses it): the setting raises;
-    torch's global switch raises too, or with warn_only warns and runs the atomic sums."""
-    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
-    what = ("the deterministic backward has no feature channels: its slots hold 9 or 10 sums per "
-            "(Gaussian, tile, quadrant) and have no room for C more")
-    if getattr(rs, "deterministic", None):
-        raise RuntimeError(f"GaussianRasterizationSettings(deterministic=True) with features: {what}")
-    if getattr(rs, "deterministic", None) is None and torch.are_deterministic_algorithms_enabled():
-        if not torch.is_deterministic_algorithms_warn_only_enabled():
-            raise RuntimeError(f"torch.use_deterministic_algorithms(True) with features: {what} "
-                               "(deterministic=False in the settings runs the atomic sums)")
-        import warnings
-        warnings.warn(f"gaussiansplattingviewer_amd: {what}; the sums over pixels are float "
-                      "atomics in this backward", UserWarning, stacklevel=2)
-    strip = getattr(rs, "tile_rows", None)
-    viewmatrix, projmatrix, campos = camera or (rs.viewmatrix, rs.projmatrix, rs.campos)
-    if grad_feature_map is None:  # the loss does not read the feature planes
-        g = _backward(rs._replace(deterministic=False), saved, grads, camera)
-        return (*g, torch.zeros_like(features))
-    if not _lib._native_shares_library():
-        g = rasterize_gaussians_backward_native(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
-            cov3Ds, viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, grads[0], sh, rs.sh_degree,
-            campos, rs.debug, dL_ddepth_map=grads[1], dL_dinv_depth_map=grads[2],
-            dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
-            tile_rows=strip, image_height=None if strip is None else rs.image_height,
-            features=features, dL_dfeature_map=grad_feature_map)
-        return tuple(g.get(n) for n in _GRADIENT_ORDER) + (g["dL_dfeatures"],)
-    from . import _C
-    e = torch.empty(0)
-    if camera is not None:
-        viewmatrix, projmatrix, campos = (_as_dev(t.detach(), means3D.device, "")
-                                          for t in camera)
-    g = _C.rasterize_gaussians_backward_features(
-        rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds,
-        viewmatrix, projmatrix, rs.tanfovx, rs.tanfovy, sh, rs.sh_degree, campos, rs.debug,
-        *(e if t is None else t for t in grads), camera is not None, bool(rs.antialiasing), False,
-        *(strip or (0, 0)), int(rs.image_height), features, grad_feature_map)
-    return g if camera is not None else g[:8] + (None,) * 3 + g[11:]
-
-
 class _RasterizeGaussiansFeatures(torch.autograd.Function):
     """The three Functions above in one, with `features` (P, C) composited beside the colour
     (`gsr_forward_features`): returns the outputs of the call without features -- (color, radii),
@@ -898,8 +869,7 @@ class _RasterizeGaussiansFeatures(torch.autograd.Function):
         args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
                      cov3Ds_precomp)
         rows = _feature_rows(features, int(means3D.size(0)), means3D.device)
-        _, color, radii, planes, feature_map = _forward_features(args, rs, bool(rs.depth_maps),
-                                                                 rows)
+        _, color, radii, planes, feature_map = _forward(args, rs, bool(rs.depth_maps), rows)
         # (a camera given as plain numbers has no gradient and is read from the settings)
         ctx.save_for_backward(*_saved(args), rows, *(
             t if isinstance(t, torch.Tensor) else None for t in (viewmatrix, projmatrix, campos)))
@@ -923,8 +893,8 @@ class _RasterizeGaussiansFeatures(torch.autograd.Function):
         with_camera = any(need[10:13])
         if viewmatrix is None or projmatrix is None or campos is None:
             viewmatrix, projmatrix, campos = rs.viewmatrix, rs.projmatrix, rs.campos
-        g = _backward_features(rs, saved, grads, rows, grad_map,
-                               (viewmatrix, projmatrix, campos) if with_camera else None)
+        g = _backward(rs, saved, grads, (viewmatrix, projmatrix, campos) if with_camera else None,
+                      features=rows, grad_feature_map=grad_map)
         like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731
         features = ctx.features_like
         return (*_input_grads(ctx.has_means2D, saved, g)[:8], None,
