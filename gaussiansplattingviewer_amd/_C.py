@@ -66,6 +66,12 @@ lambda_dssim, need_saved)` is `gsr_image_loss` -> (values (3,) = loss, l1, ssim;
 (3, C, H, W), empty without `need_saved`), and `_C.fused_image_loss_backward(image, target,
 lambda_dssim, saved, dL_dloss)` is `gsr_image_loss_backward` -> dL_dimage; the images are contiguous
 float32 (C, H, W) device tensors and dL_dloss one device value (empty = 1.0).  No context is used.
+The frame's loss on a strip (`losses.frame_loss_on_strip`): `_C.fused_image_loss_window(image,
+target, frame_H, row0, own_begin, own_end, lambda_dssim, need_saved)` is `gsr_image_loss_window`
+on band buffers (C, rows, W) whose row 0 is frame row row0 -> (the window's three shares; saved
+(3, C, A, W) over the apron), and `_C.fused_image_loss_window_backward(image, target, frame_H,
+row0, own_begin, own_end, lambda_dssim, saved, dL_dloss)` is `gsr_image_loss_window_backward` ->
+dL_dimage (C, own_end - own_begin, W).
 The optimizer (`optim.SparseGaussianAdam`, `optim.densification_stats`): `_C.adamUpdate(param,
 grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)` has upstream's signature (one group,
 in place, no bias correction); `_C.fused_adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs,
@@ -90,6 +96,7 @@ from __future__ import annotations
 try:
     from ._native import (abi_version, adamUpdate, densification_stats,  # noqa: F401
                           densify_apply, densify_plan, distCUDA2, fused_adam_step, fused_image_loss, fused_image_loss_backward,
+                          fused_image_loss_window, fused_image_loss_window_backward,
                           mark_visible, rasterize_gaussians,
                           rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,

@@ -15,8 +15,8 @@ from .renderer import (GaussianDataHIP, GaussianRenderBase, HIPRenderer, _sort_g
                        depth_argsort, gaus_hip_from_cpu)
 from .gaussian_data import GaussianData, naive_gaussian, synthetic_gaussians
 from .camera import Camera, cuda_camera_inputs, look_at, orbit_eye, static_camera
-from .strips import strip_rows, render_strips
-from .losses import photometric_loss, ssim
+from .strips import exchange_halo, strip_rows, render_strips
+from .losses import HALO_ROWS, frame_loss_on_strip, photometric_loss, ssim
 from .optim import SparseGaussianAdam, densification_stats
 from .densify import DensifyCounts, DensifyResult, densify_and_prune
 from .pointcloud import knn_mean_dist2, scene_from_point_cloud
@@ -28,7 +28,8 @@ __all__ = [
     "GaussianRenderBase", "GaussianDataHIP", "gaus_hip_from_cpu", "_sort_gaussian_hip",
     "depth_argsort", "GaussianData", "naive_gaussian", "synthetic_gaussians", "Camera",
     "cuda_camera_inputs", "look_at", "orbit_eye", "static_camera", "strip_rows",
-    "render_strips", "photometric_loss", "ssim", "SparseGaussianAdam",
+    "render_strips", "photometric_loss", "ssim", "frame_loss_on_strip", "exchange_halo",
+    "HALO_ROWS", "SparseGaussianAdam",
     "densification_stats", "densify_and_prune", "DensifyResult", "DensifyCounts",
     "knn_mean_dist2", "scene_from_point_cloud", "load_ply", "load_scene_ply", "save_ply",
 ]

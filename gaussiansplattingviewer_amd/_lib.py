@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
     "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
     "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
+    "gsr_image_loss_window_workspace", "gsr_image_loss_window", "gsr_image_loss_window_backward",
     "gsr_adam_step", "gsr_densify_stats",
     "gsr_densify_workspace", "gsr_densify_plan", "gsr_densify_apply",
     "gsr_knn_workspace", "gsr_knn_stages",
@@ -156,6 +157,13 @@ class GsrImageLossInputs(ctypes.Structure):
     _fields_ = [("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("lambda_", ctypes.c_float), ("image", ctypes.c_void_p),
                 ("target", ctypes.c_void_p)]
+
+
+class GsrLossWindow(ctypes.Structure):
+    """gsr_loss_window: the rows of a frame that gsr_image_loss_window's band buffers hold and
+    the own rows it sums and differentiates."""
+    _fields_ = [("frame_H", ctypes.c_int32), ("row0", ctypes.c_int32),
+                ("own_begin", ctypes.c_int32), ("own_end", ctypes.c_int32)]
 
 
 MAX_PARAM_GROUPS = 8  # GSR_MAX_PARAM_GROUPS
@@ -283,6 +291,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         lib.gsr_image_loss.restype = i32
         lib.gsr_image_loss_backward.argtypes = [loss_in, vp, vp, vp, vp]
         lib.gsr_image_loss_backward.restype = i32
+    if hasattr(lib, "gsr_image_loss_window"):
+        loss_in, win = ctypes.POINTER(GsrImageLossInputs), ctypes.POINTER(GsrLossWindow)
+        lib.gsr_image_loss_window_workspace.argtypes = [loss_in, win]
+        lib.gsr_image_loss_window_workspace.restype = i64
+        lib.gsr_image_loss_window.argtypes = [loss_in, win, vp, vp, vp, vp]
+        lib.gsr_image_loss_window.restype = i32
+        lib.gsr_image_loss_window_backward.argtypes = [loss_in, win, vp, vp, vp, vp]
+        lib.gsr_image_loss_window_backward.restype = i32
     if hasattr(lib, "gsr_adam_step"):
         lib.gsr_adam_step.argtypes = [ctypes.POINTER(GsrAdamSettings),
                                       ctypes.POINTER(GsrParamGroup), vp]
@@ -429,6 +445,13 @@ def image_loss_fns(lib: ctypes.CDLL):
     RuntimeError if that build does not have them."""
     return _optional_fn(lib, "gsr_image_loss_workspace / gsr_image_loss / "
                         "gsr_image_loss_backward", "the fused image loss needs")
+
+
+def image_loss_window_fns(lib: ctypes.CDLL):
+    """(gsr_image_loss_window_workspace, gsr_image_loss_window, gsr_image_loss_window_backward) of
+    a loaded library; RuntimeError if that build does not have them."""
+    return _optional_fn(lib, "gsr_image_loss_window_workspace / gsr_image_loss_window / "
+                        "gsr_image_loss_window_backward", "the frame's loss on a strip needs")
 
 
 def optimizer_fns(lib: ctypes.CDLL):

@@ -13,6 +13,12 @@
 // rows and in pass 3 along the columns, and either way 32 consecutive lanes then touch 32 banks.
 // The forward's two sums leave a block as one float pair (a fixed shuffle tree, then the four
 // waves in order); k_loss_finish adds the pairs in a fixed order in double and rounds once.
+//
+// A window of a frame (gsr_image_loss_window and its backward) runs the same
+// bodies: loss_forward, loss_backward and loss_finish below are the kernels' code, and the
+// template argument kWin only moves the tile grid to the window's first row, addresses the band
+// buffers from their first frame row and keeps rows outside the window out of the sums.  A frame
+// kernel passes kWin = false and an unused Rows: what it compiles to does not change.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,13 +60,23 @@ __device__ __forceinline__ Tile tile_of(uint32_t block, int tiles_x, int tiles_y
     return k;
 }
 
-// kP planes' 26 x 74 halo tiles -> LDS, out-of-image elements 0.0.  Every load of a thread (8 per
+// What a window adds to a frame call (frame rows throughout; a frame call reads none of it).
+struct Rows {
+    int row0, Hb;   // the band buffers: their first frame row and their rows
+    int lo, hi;     // the rows the call may read: inside the frame AND inside the buffer it stages
+    int g0, g1;     // the rows computed; the tile grid starts at g0
+    int own0, own1; // the rows summed (forward) / differentiated (backward)
+    int64_t NS;     // the plane stride of `saved`: C * (apron rows) * W
+};
+
+// kP planes' 26 x 74 halo tiles -> LDS, out-of-image elements 0.0 (rows outside [lo, hi), columns
+// outside [0, W); row `row0` is the planes' first).  Every load of a thread (8 per
 // plane) is issued before the first LDS store, from an address that is always valid (an
 // out-of-image element reads the plane's first word and is replaced by 0.0), so the loads are
 // straight-line code and their latencies overlap instead of adding up.
 template <int kP>
-__device__ __forceinline__ void stage(const float *const (&src)[kP], int H, int W, Tile k,
-                                      float *const (&dst)[kP]) {
+__device__ __forceinline__ void stage(const float *const (&src)[kP], int lo, int hi, int W, Tile k,
+                                      float *const (&dst)[kP], int row0) {
     constexpr int kIter = (kHh * kHw + kThreads - 1) / kThreads;
     float v[kP][kIter];
 #pragma unroll
@@ -68,8 +84,8 @@ __device__ __forceinline__ void stage(const float *const (&src)[kP], int H, int 
         const int i = threadIdx.x + it * kThreads;
         const int r = i / kHw, cc = i - r * kHw;
         const int gr = k.r0 - kR + r, gc = k.c0 - kR + cc;
-        const bool in = i < kHh * kHw && gr >= 0 && gr < H && gc >= 0 && gc < W;
-        const int64_t off = in ? (int64_t)gr * W + gc : 0;
+        const bool in = i < kHh * kHw && gr >= lo && gr < hi && gc >= 0 && gc < W;
+        const int64_t off = in ? (int64_t)(gr - row0) * W + gc : 0;
 #pragma unroll
         for (int p = 0; p < kP; ++p) {
             const float t = src[p][off];
@@ -107,19 +123,24 @@ __device__ __forceinline__ void vertical4(const float *__restrict__ h, int rg, i
     window4(v, o);
 }
 
-template <bool kSave>
-__global__ void __launch_bounds__(kThreads)
-k_loss_forward(const float *__restrict__ image, const float *__restrict__ target, int H, int W,
-               int tiles_x, int tiles_y, int64_t N, float *__restrict__ saved,
-               float *__restrict__ partial) {
+// The forward's block.  H: the frame's rows; N = C H W of the frame.  kWin: `image` and `target`
+// are band buffers [C, w.Hb, W], the tiles cover rows [w.g0, w.g1), `saved` is [3, C, g1 - g0, W]
+// and only rows [w.own0, w.own1) enter the two sums.
+template <bool kSave, bool kWin>
+__device__ __forceinline__ void loss_forward(const float *__restrict__ image,
+                                             const float *__restrict__ target, int H, int W,
+                                             int tiles_x, int tiles_y, int64_t N,
+                                             float *__restrict__ saved,
+                                             float *__restrict__ partial, const Rows &w) {
     __shared__ float sx[kHh * kSin], sy[kHh * kSin];
     __shared__ float sh[5][kHh * kSh];
     __shared__ float red[2][kThreads / 64];
-    const Tile k = tile_of(blockIdx.x, tiles_x, tiles_y);
-    const int64_t plane = (int64_t)k.c * H * W;
+    Tile k = tile_of(blockIdx.x, tiles_x, tiles_y);
+    if (kWin) k.r0 += w.g0;
+    const int64_t plane = (int64_t)k.c * (kWin ? w.Hb : H) * W;
     const float *const src[2] = {image + plane, target + plane};
     float *const dst[2] = {sx, sy};
-    stage<2>(src, H, W, k, dst);
+    stage<2>(src, kWin ? w.lo : 0, kWin ? w.hi : H, W, k, dst, kWin ? w.row0 : 0);
     __syncthreads();
 
     for (int item = threadIdx.x; item < kHh * kGroups; item += kThreads) {
@@ -167,7 +188,7 @@ k_loss_forward(const float *__restrict__ image, const float *__restrict__ target
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int gr = k.r0 + 4 * rg + j;
-        if (gr >= H || gc >= W) continue;
+        if (gr >= (kWin ? w.g1 : H) || gc >= W) continue;
         const float x = sx[(4 * rg + j + kR) * kSin + col + kR];
         const float y = sy[(4 * rg + j + kR) * kSin + col + kR];
         const float m1 = mu1[j], m2 = mu2[j];
@@ -178,14 +199,18 @@ k_loss_forward(const float *__restrict__ image, const float *__restrict__ target
         const float iA = 1.0f / A, iB = 1.0f / B;
         const float iAB = iA * iB;
         const float map = Cc * D * iAB;
-        sum_l1 += fabsf(x - y);
-        sum_map += map;
+        if (!kWin || (gr >= w.own0 && gr < w.own1)) {
+            sum_l1 += fabsf(x - y);
+            sum_map += map;
+        }
         if (kSave) {
-            const int64_t at = plane + (int64_t)gr * W + gc;
+            const int64_t NS = kWin ? w.NS : N;
+            const int64_t at = kWin ? ((int64_t)k.c * (w.g1 - w.g0) + (gr - w.g0)) * W + gc
+                                    : plane + (int64_t)gr * W + gc;
             // 2 mu2 (D - Cc)/(A B) + 2 mu1 map (1/B - 1/A)
             saved[at] = 2.0f * m2 * (D - Cc) * iAB + 2.0f * m1 * map * (iB - iA);
-            saved[N + at] = -(map * iB);
-            saved[2 * N + at] = 2.0f * Cc * iAB;
+            saved[NS + at] = -(map * iB);
+            saved[2 * NS + at] = 2.0f * Cc * iAB;
         }
     }
 #pragma unroll
@@ -204,11 +229,28 @@ k_loss_forward(const float *__restrict__ image, const float *__restrict__ target
     }
 }
 
-// The blocks' pairs, added in a fixed order in double: thread t takes pairs t, t + 256, ..., then
-// a tree over the 256 threads.  values = (loss, l1, ssim), each rounded once.
+template <bool kSave>
 __global__ void __launch_bounds__(kThreads)
-k_loss_finish(const float *__restrict__ partial, int blocks, double N, float lambda,
-              float *__restrict__ values) {
+k_loss_forward(const float *__restrict__ image, const float *__restrict__ target, int H, int W,
+               int tiles_x, int tiles_y, int64_t N, float *__restrict__ saved,
+               float *__restrict__ partial) {
+    loss_forward<kSave, false>(image, target, H, W, tiles_x, tiles_y, N, saved, partial, Rows{});
+}
+
+template <bool kSave>
+__global__ void __launch_bounds__(kThreads)
+k_loss_window_forward(const float *__restrict__ image, const float *__restrict__ target, int H,
+                      int W, int tiles_x, int tiles_y, int64_t N, float *__restrict__ saved,
+                      float *__restrict__ partial, Rows w) {
+    loss_forward<kSave, true>(image, target, H, W, tiles_x, tiles_y, N, saved, partial, w);
+}
+
+// The blocks' pairs, added in a fixed order in double: thread t takes pairs t, t + 256, ..., then
+// a tree over the 256 threads.  values = (loss, l1, ssim), each rounded once.  `whole` is the
+// share of the frame's elements the pairs were summed over, n_own / N: 1.0 for a frame.
+__device__ __forceinline__ void loss_finish(const float *__restrict__ partial, int blocks, double N,
+                                            float lambda, double whole,
+                                            float *__restrict__ values) {
     __shared__ double s[2][kThreads];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < blocks; i += kThreads) {
@@ -227,24 +269,45 @@ k_loss_finish(const float *__restrict__ partial, int blocks, double N, float lam
     }
     if (threadIdx.x == 0) {
         const double l1 = s[0][0] / N, ssim = s[1][0] / N, w = (double)lambda;
-        values[0] = (float)((1.0 - w) * l1 + w * (1.0 - ssim));
+        values[0] = (float)((1.0 - w) * l1 + w * (whole - ssim));
         values[1] = (float)l1;
         values[2] = (float)ssim;
     }
 }
 
 __global__ void __launch_bounds__(kThreads)
-k_loss_backward(const float *__restrict__ image, const float *__restrict__ target, int H, int W,
-                int tiles_x, int tiles_y, int64_t N, float lambda,
-                const float *__restrict__ saved, const float *__restrict__ dL_dloss,
-                float *__restrict__ dL_dimage) {
+k_loss_finish(const float *__restrict__ partial, int blocks, double N, float lambda,
+              float *__restrict__ values) {
+    loss_finish(partial, blocks, N, lambda, 1.0, values);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_loss_window_finish(const float *__restrict__ partial, int blocks, double N, float lambda,
+                     double whole, float *__restrict__ values) {
+    loss_finish(partial, blocks, N, lambda, whole, values);
+}
+
+// The backward's block.  kWin: the tiles cover the own rows [w.own0, w.own1); `saved` is the
+// window forward's [3, C, w.hi - w.lo, W] over the apron rows [w.lo, w.hi) and is staged from
+// there (rows outside it are outside the frame: 0.0); `image` and `target` are the band buffers;
+// dL_dimage is [C, own1 - own0, W].  gm and cl are the frame's.
+template <bool kWin>
+__device__ __forceinline__ void loss_backward(const float *__restrict__ image,
+                                              const float *__restrict__ target, int H, int W,
+                                              int tiles_x, int tiles_y, int64_t N, float lambda,
+                                              const float *__restrict__ saved,
+                                              const float *__restrict__ dL_dloss,
+                                              float *__restrict__ dL_dimage, const Rows &w) {
     __shared__ float sa[3][kHh * kSin];
     __shared__ float sh[3][kHh * kSh];
-    const Tile k = tile_of(blockIdx.x, tiles_x, tiles_y);
-    const int64_t plane = (int64_t)k.c * H * W;
-    const float *const src[3] = {saved + plane, saved + N + plane, saved + 2 * N + plane};
+    Tile k = tile_of(blockIdx.x, tiles_x, tiles_y);
+    if (kWin) k.r0 += w.own0;
+    const int64_t plane = (int64_t)k.c * (kWin ? w.Hb : H) * W;
+    const int64_t NS = kWin ? w.NS : N;
+    const int64_t splane = kWin ? (int64_t)k.c * (w.hi - w.lo) * W : plane;
+    const float *const src[3] = {saved + splane, saved + NS + splane, saved + 2 * NS + splane};
     float *const dst[3] = {sa[0], sa[1], sa[2]};
-    stage<3>(src, H, W, k, dst);
+    stage<3>(src, kWin ? w.lo : 0, kWin ? w.hi : H, W, k, dst, kWin ? w.lo : 0);
     // this thread's 4 pixels of image and target, asked for before the passes that hide them
     const int col = threadIdx.x & (kTw - 1), rg = threadIdx.x / kTw;
     const int gc = k.c0 + col;
@@ -252,7 +315,9 @@ k_loss_backward(const float *__restrict__ image, const float *__restrict__ targe
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int gr = k.r0 + 4 * rg + j;
-        const int64_t at = gr < H && gc < W ? plane + (int64_t)gr * W + gc : plane;
+        const int64_t at = gr < (kWin ? w.own1 : H) && gc < W
+                               ? plane + (int64_t)(kWin ? gr - w.row0 : gr) * W + gc
+                               : plane;
         px[j] = image[at];
         py[j] = target[at];
     }
@@ -283,13 +348,32 @@ k_loss_backward(const float *__restrict__ image, const float *__restrict__ targe
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int gr = k.r0 + 4 * rg + j;
-        if (gr >= H || gc >= W) continue;
-        const int64_t at = plane + (int64_t)gr * W + gc;
+        if (gr >= (kWin ? w.own1 : H) || gc >= W) continue;
+        const int64_t at = kWin ? ((int64_t)k.c * (w.own1 - w.own0) + (gr - w.own0)) * W + gc
+                                : plane + (int64_t)gr * W + gc;
         const float x = px[j], y = py[j];
         const float d = x - y;
         const float sg = d > 0.0f ? 1.0f : d < 0.0f ? -1.0f : d == 0.0f ? 0.0f : d;  // NaN stays
         dL_dimage[at] = (gm * ca[j] + 2.0f * x * (gm * cb[j]) + y * (gm * cc[j])) + cl * sg;
     }
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_loss_backward(const float *__restrict__ image, const float *__restrict__ target, int H, int W,
+                int tiles_x, int tiles_y, int64_t N, float lambda,
+                const float *__restrict__ saved, const float *__restrict__ dL_dloss,
+                float *__restrict__ dL_dimage) {
+    loss_backward<false>(image, target, H, W, tiles_x, tiles_y, N, lambda, saved, dL_dloss,
+                         dL_dimage, Rows{});
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_loss_window_backward(const float *__restrict__ image, const float *__restrict__ target, int H,
+                       int W, int tiles_x, int tiles_y, int64_t N, float lambda,
+                       const float *__restrict__ saved, const float *__restrict__ dL_dloss,
+                       float *__restrict__ dL_dimage, Rows w) {
+    loss_backward<true>(image, target, H, W, tiles_x, tiles_y, N, lambda, saved, dL_dloss,
+                        dL_dimage, w);
 }
 
 struct Shape {
@@ -312,6 +396,52 @@ bool shape_of(int32_t C, int32_t H, int32_t W, Shape *s) {
 bool check_inputs(const gsr_image_loss_inputs *in, Shape *s) {
     return in && in->image && in->target && shape_of(in->C, in->H, in->W, s) &&
            in->lambda >= 0.0f && in->lambda <= 1.0f;  // false for NaN
+}
+
+constexpr int kHalo = 2 * kR;  // rows of a neighbour a window with `saved` reads: 5 + 5
+
+// A checked window: the forward's and the backward's Rows and grids.
+struct Window {
+    Rows fwd, bwd;
+    int tiles_x, fwd_tiles_y, bwd_tiles_y;
+    int64_t N, n_own, fwd_blocks, bwd_blocks, apron_blocks;
+};
+
+int tile_rows_of(int rows) { return (rows + kTh - 1) / kTh; }
+
+// False for what the window entries refuse.  `halo`: the rows beyond the own rows the band must
+// hold, inside the frame (10 with `saved`, 5 without, 0 for the backward); -1 skips the band's
+// pointers and coverage (the workspace size depends on neither).
+bool window_of(const gsr_image_loss_inputs *in, const gsr_loss_window *w, int halo, bool save,
+               Window *o) {
+    if (!in || !w) return false;
+    Shape frame;
+    if (in->H < 1 || !shape_of(in->C, w->frame_H, in->W, &frame)) return false;
+    if (!(in->lambda >= 0.0f && in->lambda <= 1.0f)) return false;
+    const int64_t H = w->frame_H;
+    if (w->own_begin < 0 || w->own_begin >= w->own_end || w->own_end > H) return false;
+    if (w->row0 < 0 || (int64_t)w->row0 + in->H > H) return false;  // the band lies in the frame
+    const int own0 = w->own_begin, own1 = w->own_end;
+    const auto below = [](int r, int d) { return r > d ? r - d : 0; };
+    const auto above = [H](int r, int d) { return (int)(r + (int64_t)d < H ? r + d : H); };
+    if (halo >= 0) {
+        if (!in->image || !in->target) return false;
+        if (w->row0 > below(own0, halo) || w->row0 + in->H < above(own1, halo)) return false;
+    }
+    const int a0 = below(own0, kR), a1 = above(own1, kR);  // the apron
+    o->tiles_x = frame.tiles_x;
+    o->N = frame.N;
+    o->n_own = (int64_t)in->C * (own1 - own0) * in->W;
+    const int64_t NS = (int64_t)in->C * (a1 - a0) * in->W;
+    const int g0 = save ? a0 : own0, g1 = save ? a1 : own1;
+    o->fwd = Rows{w->row0, in->H, below(g0, kR), above(g1, kR), g0, g1, own0, own1, NS};
+    o->bwd = Rows{w->row0, in->H, a0, a1, own0, own1, own0, own1, NS};
+    o->fwd_tiles_y = tile_rows_of(g1 - g0);
+    o->bwd_tiles_y = tile_rows_of(own1 - own0);
+    o->fwd_blocks = (int64_t)in->C * o->tiles_x * o->fwd_tiles_y;
+    o->bwd_blocks = (int64_t)in->C * o->tiles_x * o->bwd_tiles_y;
+    o->apron_blocks = (int64_t)in->C * o->tiles_x * tile_rows_of(a1 - a0);
+    return true;
 }
 
 int launched(const char *what) {
@@ -363,6 +493,50 @@ int gsr_image_loss_backward(const gsr_image_loss_inputs *in, const float *saved,
                        static_cast<hipStream_t>(stream), in->image, in->target, in->H, in->W,
                        s.tiles_x, s.tiles_y, s.N, in->lambda, saved, dL_dloss, dL_dimage);
     return launched("image loss backward");
+}
+
+int64_t gsr_image_loss_window_workspace(const gsr_image_loss_inputs *in,
+                                        const gsr_loss_window *w) {
+    Window win;
+    if (!window_of(in, w, -1, true, &win))
+        return gsr_set_error(GSR_E_INVALID, "gsr_image_loss_window_workspace: bad arguments");
+    return win.apron_blocks * 2 * (int64_t)sizeof(float);  // the grid with `saved`, the larger
+}
+
+int gsr_image_loss_window(const gsr_image_loss_inputs *in, const gsr_loss_window *w,
+                          float *values, float *saved, void *workspace, void *stream) {
+    Window win;
+    if (!values || !workspace || !window_of(in, w, saved ? kHalo : kR, saved != nullptr, &win))
+        return gsr_set_error(GSR_E_INVALID, "gsr_image_loss_window: bad arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *partial = static_cast<float *>(workspace);
+    if (saved)
+        hipLaunchKernelGGL(k_loss_window_forward<true>, dim3((uint32_t)win.fwd_blocks),
+                           dim3(kThreads), 0, st, in->image, in->target, w->frame_H, in->W,
+                           win.tiles_x, win.fwd_tiles_y, win.N, saved, partial, win.fwd);
+    else
+        hipLaunchKernelGGL(k_loss_window_forward<false>, dim3((uint32_t)win.fwd_blocks),
+                           dim3(kThreads), 0, st, in->image, in->target, w->frame_H, in->W,
+                           win.tiles_x, win.fwd_tiles_y, win.N, saved, partial, win.fwd);
+    int rc = launched("image loss window forward");
+    if (rc != GSR_OK) return rc;
+    hipLaunchKernelGGL(k_loss_window_finish, dim3(1), dim3(kThreads), 0, st, partial,
+                       (int)win.fwd_blocks, (double)win.N, in->lambda,
+                       (double)win.n_own / (double)win.N, values);
+    return launched("image loss window finish");
+}
+
+int gsr_image_loss_window_backward(const gsr_image_loss_inputs *in, const gsr_loss_window *w,
+                                   const float *saved, const float *dL_dloss, float *dL_dimage,
+                                   void *stream) {
+    Window win;
+    if (!saved || !dL_dimage || !window_of(in, w, 0, true, &win))
+        return gsr_set_error(GSR_E_INVALID, "gsr_image_loss_window_backward: bad arguments");
+    hipLaunchKernelGGL(k_loss_window_backward, dim3((uint32_t)win.bwd_blocks), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), in->image, in->target, w->frame_H, in->W,
+                       win.tiles_x, win.bwd_tiles_y, win.N, in->lambda, saved, dL_dloss,
+                       dL_dimage, win.bwd);
+    return launched("image loss window backward");
 }
 
 }  // extern "C"

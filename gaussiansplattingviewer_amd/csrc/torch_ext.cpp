@@ -74,6 +74,16 @@
 //   _C.fused_image_loss_backward(image, target, lambda_dssim, saved, dL_dloss) -> dL_dimage
 //     gsr_image_loss_backward; dL_dloss is a one-element device tensor (read on the device, no
 //     host wait) or empty for 1.0.
+//   _C.fused_image_loss_window(image, target, frame_H, row0, own_begin, own_end, lambda_dssim,
+//                              need_saved) -> (values [3], saved)
+//     gsr_image_loss_window: the frame's loss on the rows [own_begin, own_end) of a frame of
+//     frame_H rows, from the band buffers image / target [C, rows, W] whose row 0 is frame row
+//     row0; values = the window's shares, saved = [3, C, A, W] over the apron (own rows +- 5,
+//     clipped to the frame), empty without `need_saved`.
+//   _C.fused_image_loss_window_backward(image, target, frame_H, row0, own_begin, own_end,
+//                                       lambda_dssim, saved, dL_dloss) -> dL_dimage
+//     gsr_image_loss_window_backward: the frame loss's gradient on the own rows,
+//     [C, own_end - own_begin, W].
 //   _C.adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)
 //     upstream's fused sparse Adam (SparseGaussianAdam): gsr_adam_step on one [N, M] group, in
 //     place, for the rows whose `visible` (bool or uint8 [N]) is set; no bias correction.
@@ -639,6 +649,77 @@ torch::Tensor fused_image_loss_backward(const torch::Tensor &image, const torch:
     return grad;
 }
 
+// A window of a frame for the two entries below: the band's struct is loss_inputs' (the frame's
+// size limit is the C ABI's to check).
+gsr_loss_window loss_window(int64_t frame_H, int64_t row0, int64_t own_begin, int64_t own_end) {
+    const int64_t lim = (int64_t)1 << 31;
+    TORCH_CHECK(frame_H >= 0 && frame_H < lim && row0 >= 0 && row0 < lim && own_begin >= 0 &&
+                    own_begin < lim && own_end >= 0 && own_end < lim,
+                "frame_H, row0, own_begin and own_end must be in [0, 2^31)");
+    gsr_loss_window w{};
+    w.frame_H = (int32_t)frame_H;
+    w.row0 = (int32_t)row0;
+    w.own_begin = (int32_t)own_begin;
+    w.own_end = (int32_t)own_end;
+    return w;
+}
+
+int64_t apron_rows(const gsr_loss_window &w) {
+    const int64_t a0 = std::max<int64_t>(0, (int64_t)w.own_begin - 5);
+    const int64_t a1 = std::min<int64_t>(w.frame_H, (int64_t)w.own_end + 5);
+    return std::max<int64_t>(0, a1 - a0);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> fused_image_loss_window(
+    const torch::Tensor &image, const torch::Tensor &target, int64_t frame_H, int64_t row0,
+    int64_t own_begin, int64_t own_end, double lambda, bool need_saved) {
+    const gsr_image_loss_inputs in = loss_inputs(image, target, lambda);
+    const gsr_loss_window w = loss_window(frame_H, row0, own_begin, own_end);
+    const int64_t bytes = gsr_image_loss_window_workspace(&in, &w);
+    TORCH_CHECK(bytes >= 0, "gsr_image_loss_window_workspace failed (", bytes, "): ",
+                gsr_last_error());
+    c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor values = torch::empty({3}, image.options());
+    torch::Tensor saved = need_saved ? torch::empty({3, in.C, apron_rows(w), in.W}, image.options())
+                                     : torch::empty({0}, image.options());
+    torch::Tensor ws = torch::empty({bytes}, image.options().dtype(torch::kUInt8));
+    hipStream_t s = c10::hip::getCurrentHIPStream(image.device().index()).stream();
+    const int rc = gsr_image_loss_window(&in, &w, values.data_ptr<float>(),
+                                         need_saved ? saved.data_ptr<float>() : nullptr,
+                                         ws.data_ptr(), s);
+    TORCH_CHECK(rc == GSR_OK, "gsr_image_loss_window failed (", rc, "): ", gsr_last_error());
+    return std::make_tuple(values, saved);
+}
+
+torch::Tensor fused_image_loss_window_backward(const torch::Tensor &image,
+                                               const torch::Tensor &target, int64_t frame_H,
+                                               int64_t row0, int64_t own_begin, int64_t own_end,
+                                               double lambda, const torch::Tensor &saved,
+                                               const torch::Tensor &dL_dloss) {
+    const gsr_image_loss_inputs in = loss_inputs(image, target, lambda);
+    const gsr_loss_window w = loss_window(frame_H, row0, own_begin, own_end);
+    TORCH_CHECK(own_begin < own_end && own_end <= frame_H, "own rows must lie in the frame");
+    TORCH_CHECK(saved.is_cuda() && saved.device() == image.device() &&
+                    saved.scalar_type() == torch::kFloat32 && saved.is_contiguous() &&
+                    saved.numel() == 3 * (int64_t)in.C * apron_rows(w) * in.W,
+                "saved must be the window forward's contiguous float32 (3, C, A, W) tensor");
+    const float *gl = nullptr;
+    torch::Tensor g;
+    if (dL_dloss.defined() && dL_dloss.numel() != 0) {
+        TORCH_CHECK(dL_dloss.numel() == 1, "dL_dloss must hold one value");
+        g = dL_dloss.to(image.device(), torch::kFloat32).contiguous();
+        gl = g.data_ptr<float>();
+    }
+    c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor grad = torch::empty({in.C, own_end - own_begin, in.W}, image.options());
+    hipStream_t s = c10::hip::getCurrentHIPStream(image.device().index()).stream();
+    const int rc = gsr_image_loss_window_backward(&in, &w, saved.data_ptr<float>(), gl,
+                                                  grad.data_ptr<float>(), s);
+    TORCH_CHECK(rc == GSR_OK, "gsr_image_loss_window_backward failed (", rc, "): ",
+                gsr_last_error());
+    return grad;
+}
+
 // A float32 [P, M] tensor of the optimizer entries: on `dev`, contiguous, `numel` elements.
 float *adam_buffer(const torch::Tensor &t, const torch::Device &dev, int64_t numel,
                    const char *name) {
@@ -984,6 +1065,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_image_loss_backward", &fused_image_loss_backward,
           "image, target, lambda_dssim, saved, dL_dloss (one device value, or empty for 1.0): "
           "gsr_image_loss_backward -> dL_dimage (C, H, W)");
+    m.def("fused_image_loss_window", &fused_image_loss_window,
+          "band image, band target (contiguous float32 (C, rows, W)), frame_H, row0, own_begin, "
+          "own_end, lambda_dssim, need_saved: gsr_image_loss_window -> (values (3,), saved "
+          "(3, C, A, W) or empty)");
+    m.def("fused_image_loss_window_backward", &fused_image_loss_window_backward,
+          "band image, band target, frame_H, row0, own_begin, own_end, lambda_dssim, saved, "
+          "dL_dloss: gsr_image_loss_window_backward -> dL_dimage (C, own_end - own_begin, W)");
     m.def("adamUpdate", &adam_update,
           "upstream's adamUpdate: param, grad, exp_avg, exp_avg_sq (N, M), visible (bool or uint8 "
           "N), lr, b1, b2, eps, N, M: gsr_adam_step on one group, in place, no bias correction");

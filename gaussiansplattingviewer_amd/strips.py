@@ -17,12 +17,17 @@ bit-identical to the same rows of a single-GPU frame, wherever the boundaries fa
 * Gradients: a rank differentiates its own strip (`GaussianRasterizationSettings(tile_rows=)`,
   `gsr_backward_strip`); the strips' whole-scene gradients add up to the frame's, and
   `reduce_gradients` sums them over the ranks.
+* The loss: `exchange_halo` hands every rank the ten rendered rows on either side of its strip,
+  with which `losses.frame_loss_on_strip` computes the strip's share of the frame's loss and the
+  frame loss's gradient on the strip's rows (`halo_plan` is the index arithmetic).
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from .losses import HALO_ROWS
 
 TILE = 16
 
@@ -257,6 +262,111 @@ def reduce_gradients(tensors, group=None) -> None:
             torch.cuda.current_stream(dev).synchronize()
     for t in tensors:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
+def halo_plan(layout: list[tuple[int, int]], H: int, rank: int, rows: int = HALO_ROWS) -> dict:
+    """What `exchange_halo` moves for `rank`, as index arithmetic alone (no process group):
+
+        {"rows": (y0, y1),                  # the rank's strip in frame rows
+         "above": (peer, n) or None,        # n frame rows [y0 - n, y0) come from rank peer
+         "below": (peer, n) or None,        # n frame rows [y1, y1 + n) come from rank peer
+         "sends": [(peer, s0, s1), ...]}    # the strip's own rows [s0, s1) (strip-local) go to peer
+
+    with n = min(rows, y0) above and min(rows, H - y1) below.  The two neighbours suffice by the
+    layout's construction: tile rows are 16 pixel rows, so every non-empty strip but the last has
+    >= 16 >= `rows` rows and covers a neighbour's halo alone; only the last can be shorter (a
+    ragged last tile row), and what the strip before it needs below, min(rows, H - y1), is then
+    that whole strip.  Empty strips come last (`strip_layout` and `balanced_layout` give every
+    rank a row while rows remain): such a rank sends and receives nothing, and the last non-empty
+    strip has no neighbour below.  ValueError for a layout that is not such a partition of the
+    frame's tile rows, or `rows` larger than a strip that would have to supply them."""
+    world = len(layout)
+    if not 0 <= rank < world:
+        raise ValueError("bad rank / world")
+    if rows < 0 or H < 1:
+        raise ValueError("rows must be >= 0 and H >= 1")
+    px, edge, ended = [], 0, False
+    for tb, te in layout:
+        y0, r = strip_pixel_rows((tb, te), H)
+        if r:
+            if ended or y0 != edge:
+                raise ValueError(f"layout {layout} is not a partition of the frame's rows with "
+                                 "its empty strips last")
+            edge = y0 + r
+        else:
+            ended = True
+        px.append((y0, y0 + r))
+    if edge != H:
+        raise ValueError(f"layout {layout} covers {edge} of the frame's {H} rows")
+    y0, y1 = px[rank]
+    plan = {"rows": (y0, y1), "above": None, "below": None, "sends": []}
+    if y0 == y1:
+        return plan
+
+    def supplies(peer, n):  # rank `peer` must hold the n rows on its own
+        if px[peer][1] - px[peer][0] < n:
+            raise ValueError(f"strip {px[peer]} of rank {peer} is shorter than the {n} halo rows "
+                             "its neighbour needs")
+
+    a, b = min(rows, y0), min(rows, H - y1)
+    if a:
+        supplies(rank - 1, a)
+        plan["above"] = (rank - 1, a)
+    if b:
+        supplies(rank + 1, b)
+        plan["below"] = (rank + 1, b)
+    r = y1 - y0
+    if rank > 0:  # the strip above reads its `below` from this strip's first rows
+        n = min(rows, H - y0)
+        supplies(rank, n)
+        if n:
+            plan["sends"].append((rank - 1, 0, n))
+    if rank + 1 < world and px[rank + 1][0] != px[rank + 1][1]:  # the strip below: its `above`
+        n = min(rows, y1)
+        supplies(rank, n)
+        if n:
+            plan["sends"].append((rank + 1, r - n, r))
+    return plan
+
+
+def exchange_halo(strip: torch.Tensor, layout: list[tuple[int, int]], H: int, rank: int,
+                  group=None, rows: int = HALO_ROWS):
+    """The rendered rows next to this rank's strip that `losses.frame_loss_on_strip` needs:
+    -> (above, below), the frame rows [y0 - a, y0) and [y1, y1 + b) as [C, a, W] and [C, b, W]
+    (None where the count is 0), a = min(rows, y0), b = min(rows, H - y1), received from the two
+    neighbouring ranks while this strip's own edge rows go to them.  `strip` is this rank's
+    [C, y1 - y0, W] render of `layout[rank]`, detached (the halos are constants of the loss: a
+    rank differentiates its own rows only).  One `batch_isend_irecv` with one message per colour
+    plane and direction, as StripGather's; with a backend that moves device tensors from host
+    threads (gloo; not RCCL) the current stream is synchronised first, as `reduce_gradients`
+    does, so the render that wrote the strip is done.  The call returns when the halos have
+    arrived.  A no-op at world 1 and for a rank with an empty strip: (None, None).  `halo_plan`
+    states which rows move and why the neighbours suffice."""
+    if strip.requires_grad:
+        raise ValueError("exchange_halo moves constants: pass the strip detached")
+    plan = halo_plan(layout, H, rank, rows)
+    y0, y1 = plan["rows"]
+    if strip.dim() != 3 or strip.shape[1] != y1 - y0:
+        raise ValueError(f"strip shape {tuple(strip.shape)} != (C, {y1 - y0}, W)")
+    if len(layout) == 1 or y0 == y1:
+        return None, None
+    C, _, W = strip.shape
+    strip = strip.contiguous()
+    halos = {side: (strip.new_empty((C, plan[side][1], W)) if plan[side] else None)
+             for side in ("above", "below")}
+    ops = []
+    for peer, s0, s1 in plan["sends"]:
+        ops += [dist.P2POp(dist.isend, strip[c, s0:s1], peer, group=group) for c in range(C)]
+    for side in ("above", "below"):
+        if plan[side]:
+            ops += [dist.P2POp(dist.irecv, halos[side][c], plan[side][0], group=group)
+                    for c in range(C)]
+    if ops:
+        if strip.is_cuda and dist.get_backend(group) != "nccl":
+            torch.cuda.current_stream(strip.device).synchronize()
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+    return halos["above"], halos["below"]
 
 
 def render_strips(render_fn, H: int, W: int, world: int, rank: int, group=None,

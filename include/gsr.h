@@ -724,7 +724,8 @@ int gsr_pack_image(const float *chw, int32_t H, int32_t W, int32_t format, int32
  *   A = mu1^2 + mu2^2 + C1, B = s1 + s2 + C2, Cc = 2 mu1 mu2 + C1, D = 2 s12 + C2,
  *   map = Cc D / (A B).
  * NaN and infinities propagate; nothing is clamped.  A strip image is an image like any other:
- * its loss is that of the strip alone, zero padded at the strip's edges.
+ * its loss is that of the strip alone, zero padded at the strip's edges.  The frame's loss on a
+ * strip, seams unpadded, is gsr_image_loss_window's (below).
  *
  * Neither call takes a context (no mutex, no ordering against frames in flight), allocates or
  * synchronises: all memory is the caller's and all work is enqueued on `stream`.  No atomics:
@@ -760,6 +761,65 @@ int gsr_image_loss(const gsr_image_loss_inputs *in, float *values, float *saved,
                    void *stream);
 int gsr_image_loss_backward(const gsr_image_loss_inputs *in, const float *saved,
                             const float *dL_dloss, float *dL_dimage, void *stream);
+
+/* ---- The frame's loss on a window of its rows: a strip's share, with halo rows ----
+ * (additive to ABI 4; no existing struct, entry point or kernel changes)
+ *
+ * The loss above, of a frame [C, frame_H, W], computed from a band of its rows: what a rank that
+ * rendered a strip, or a fit that walks a large frame band by band, needs to minimise the
+ * frame's loss and not the strip's.  The map at a pixel reads the images within 5 rows of it and
+ * the gradient at a pixel reads the map's partial derivatives within 5 rows of it, so the own
+ * rows and 10 rows of each neighbour are all a window needs.
+ *
+ * `in` describes the band: in->image and in->target are contiguous [C, in->H, W] buffers whose
+ * row 0 is frame row w->row0, and the band lies inside the frame (row0 >= 0, row0 + in->H <=
+ * frame_H).  The own rows [own_begin, own_end) are the rows summed and differentiated; the apron
+ * is [max(0, own_begin - 5), min(frame_H, own_end + 5)), A rows.  N = C * frame_H * W, the
+ * frame's, normalises everything, and n_own = C (own_end - own_begin) W.
+ *
+ * Padding: frame rows < 0 or >= frame_H are the zero padding, as are columns outside [0, W).
+ *   Every other row a call needs must lie inside the band.  A seam is never padded.
+ * Rows needed: with `saved`, [max(0, own_begin - 10), min(frame_H, own_end + 10)); without, the
+ *   apron; the backward reads of the band only the own rows.  Band rows beyond these are not read.
+ * values[3] = (loss, l1, ssim), the window's shares:
+ *     l1 = sum_own |image - target| / N,   ssim = sum_own map / N,
+ *     loss = (1 - lambda) l1 + lambda (n_own / N - ssim),
+ *   each formed in double from the blocks' partial sums in a fixed order and rounded once.  Over
+ *   a partition of the frame's rows into own ranges the shares add up to the frame's three
+ *   values (up to the roundings of the shares and of their sum).
+ * saved: device [3, C, A, W] over the apron rows, or NULL when no gradient is wanted.  The
+ *   forward computes the map and its partial derivatives on the apron and sums only the own rows;
+ *   without `saved` it computes the own rows alone, so the partial sums, and with them the last
+ *   bits of `values`, may differ between the two.
+ * dL_dimage: device [C, own_end - own_begin, W], written, not accumulated into.  It is the FRAME
+ *   loss's gradient on the own rows: it includes the terms from map pixels in the apron that a
+ *   neighbour sums into ITS share.  So it is the gradient of the sum of all windows' shares,
+ *   under the same dL_dloss on every window; it is NOT the gradient of this window's share alone.
+ * Per-pixel bits: the arithmetic is gsr_image_loss's own code (the same device functions, tap
+ *   order and constants, gm and cl from the frame's N).  Every element of `saved` on the apron
+ *   and of dL_dimage on the own rows has the bits gsr_image_loss / gsr_image_loss_backward on the
+ *   whole frame give that pixel, wherever the window and its tile grid fall.  The window row0 = 0,
+ *   own = [0, frame_H) has gsr_image_loss's bits in `values` too.
+ * Like the pair above: no context, no allocation, no synchronisation, no atomics; the same bits on
+ *   every call with the same inputs, on any stream.  gsr_image_loss_window_workspace gives the
+ *   bytes of device scratch gsr_image_loss_window needs (it reads the sizes and the own range
+ *   only, not the band's pointers or coverage).
+ * Refused with GSR_E_INVALID before any HIP call, nothing written: a NULL in, w, image, target,
+ *   values or workspace; the backward's NULL saved or dL_dimage; a size < 1;
+ *   C*frame_H*W >= 2^31; own_begin < 0, own_begin >= own_end or own_end > frame_H; a band outside
+ *   the frame or one that does not cover the rows the call needs; lambda outside [0, 1] or NaN. */
+typedef struct gsr_loss_window {
+    int32_t frame_H;   /* rows of the whole frame */
+    int32_t row0;      /* the frame row of row 0 of in->image / in->target */
+    int32_t own_begin; /* frame rows [own_begin, own_end): summed and differentiated */
+    int32_t own_end;
+} gsr_loss_window;
+int64_t gsr_image_loss_window_workspace(const gsr_image_loss_inputs *in, const gsr_loss_window *w);
+int gsr_image_loss_window(const gsr_image_loss_inputs *in, const gsr_loss_window *w, float *values,
+                          float *saved, void *workspace, void *stream);
+int gsr_image_loss_window_backward(const gsr_image_loss_inputs *in, const gsr_loss_window *w,
+                                   const float *saved, const float *dL_dloss, float *dL_dimage,
+                                   void *stream);
 
 /* ---- The parameter update of a fit: a fused, visibility-masked ("sparse") Adam step, and the
  * densification statistics ---- (additive to ABI 4)
