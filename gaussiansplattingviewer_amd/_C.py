@@ -61,6 +61,10 @@ tile_row_end, features)` is `gsr_forward_features` -> the 6-tuple of `rasterize_
 then feature_map (C, rows, W); `_C.rasterize_gaussians_backward_features(<the backward's
 arguments>, deterministic, tile_row_begin, tile_row_end, image_height, features,
 dL_dfeature_map)` is `gsr_backward_features` -> the 11-tuple, then dL_dfeatures (P, C).
+The absolute gradient of the 2D means (`GaussianRasterizer(...)(..., means2D_abs=)`):
+`_C.rasterize_gaussians_backward_abs(<the backward's arguments>, deterministic, tile_row_begin,
+tile_row_end, image_height)`, tile rows (0, 0) for a whole frame, is `gsr_backward_abs` -> the
+11-tuple, then dL_dmeans2D_abs (P, 3).
 The photometric loss (`losses.photometric_loss`): `_C.fused_image_loss(image, target,
 lambda_dssim, need_saved)` is `gsr_image_loss` -> (values (3,) = loss, l1, ssim; saved
 (3, C, H, W), empty without `need_saved`), and `_C.fused_image_loss_backward(image, target,
@@ -98,7 +102,8 @@ try:
                           densify_apply, densify_plan, distCUDA2, fused_adam_step, fused_image_loss, fused_image_loss_backward,
                           fused_image_loss_window, fused_image_loss_window_backward,
                           mark_visible, rasterize_gaussians,
-                          rasterize_gaussians_backward, rasterize_gaussians_backward_ext,
+                          rasterize_gaussians_backward, rasterize_gaussians_backward_abs,
+                          rasterize_gaussians_backward_ext,
                           rasterize_gaussians_backward_features,
                           rasterize_gaussians_backward_strip_ext, rasterize_gaussians_ext,
                           rasterize_gaussians_features, rasterize_gaussians_shaded)

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_shaded", "gsr_forward_depth", "gsr_backward", "gsr_backward_times",
     "gsr_backward_planes", "gsr_forward_surface", "gsr_backward_camera",
     "gsr_forward_filtered", "gsr_backward_filtered", "gsr_backward_ordered",
-    "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features",
+    "gsr_backward_strip", "gsr_forward_features", "gsr_backward_features", "gsr_backward_abs",
     "gsr_image_loss_workspace", "gsr_image_loss", "gsr_image_loss_backward",
     "gsr_image_loss_window_workspace", "gsr_image_loss_window", "gsr_image_loss_window_backward",
     "gsr_adam_step", "gsr_densify_stats",
@@ -152,6 +152,11 @@ class GsrFeatureGradients(ctypes.Structure):
                 ("dL_dfeature_map", ctypes.c_void_p), ("dL_dfeatures", ctypes.c_void_p)]
 
 
+class GsrAbsGradients(ctypes.Structure):
+    """gsr_abs_gradients: gsr_backward_abs' output, [P, 3] floats (None = not wanted)."""
+    _fields_ = [("dL_dmeans2D_abs", ctypes.c_void_p)]
+
+
 class GsrImageLossInputs(ctypes.Structure):
     """gsr_image_loss_inputs: the two [C, H, W] images of gsr_image_loss and its backward."""
     _fields_ = [("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
@@ -255,6 +260,9 @@ _ADDITIVE = {
     "gsr_backward_features": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
                               GsrFilterSettings, GsrBackwardOrder, GsrFeatureGradients,
                               GsrGradients),
+    "gsr_backward_abs": (GsrBackwardInputs, GsrPlaneGradients, GsrCameraGradients,
+                         GsrFilterSettings, GsrBackwardOrder, GsrFeatureGradients,
+                         GsrAbsGradients, GsrGradients),
 }
 
 _lock = threading.Lock()
@@ -438,6 +446,11 @@ def features_fns(lib: ctypes.CDLL):
     build does not have them."""
     return _optional_fn(lib, "gsr_forward_features / gsr_backward_features",
                         "per-Gaussian feature channels need")
+
+
+def backward_abs_fn(lib: ctypes.CDLL):
+    """gsr_backward_abs of a loaded library; RuntimeError if that build does not have it."""
+    return _optional_fn(lib, "gsr_backward_abs", "the absolute means2D gradient needs")
 
 
 def image_loss_fns(lib: ctypes.CDLL):

@@ -183,7 +183,8 @@ struct gsr_context {
     // gsr_backward_camera: the blocks' partial sums of the camera's 27 entries, [27][blocks]
     Buf<float> cam_partials{bufs};
     // gsr_backward_ordered, deterministic (gsr_internal.h GsrDetBwdArgs): the Gaussians' first
-    // pairs (and the scan's block totals), the slots' sums (4 K x 9 or 10 floats, never zeroed) and
+    // pairs (and the scan's block totals), the slots' sums (4 K x 9 or 10 floats, 11 or 12 under
+    // gsr_backward_abs; never zeroed) and
     // their marks (4 K bytes, zeroed by every call); grown on demand, freed with the context
     Buf<uint64_t> det_slab{bufs}, det_partials{bufs};
     Buf<float> det_sums{bufs};
@@ -1584,12 +1585,13 @@ struct BackwardRequest {
     const gsr_backward_order *order = nullptr;
     const gsr_feature_gradients *feat = nullptr;
     bool strips = false;  // gsr_backward_strip on: a strip of the settings is honoured, not refused
+    const gsr_abs_gradients *abs = nullptr;
 };
 
 // What the call does, decided once, before the context is touched.
 struct BackwardPlan {
-    // the entry the messages name: the last of gsr_backward_filtered, _ordered, _strip and
-    // _features whose option is in use (an option at 0 is the entry below), else rq.fn
+    // the entry the messages name: the last of gsr_backward_filtered, _ordered, _strip,
+    // _features and _abs whose option is in use (an option at 0 is the entry below), else rq.fn
     std::string fn;
     hipStream_t s = nullptr;
     bool planes = false;  // a plane gradient is given: the planes instantiations of both kernels
@@ -1602,24 +1604,29 @@ struct BackwardPlan {
     // proper subset of the rows the Gaussians without a tile in it are gated out of the third stage
     bool strip = false;
     const gsr_feature_gradients *ft = nullptr;  // rq.feat when it holds a dL_dfeature_map
+    // gsr_backward_abs: rq.abs's dL_dmeans2D_abs, or NULL -- the kAbs instantiations
+    // of the blend's backward (and of the gather) and k_means2d_abs in the third stage
+    float *abs = nullptr;
 };
 
 static bool backward_null(const gsr_context *ctx, const BackwardRequest &rq) {
     return !ctx || !rq.g || !rq.st || !rq.in || !rq.gr;
 }
 
-// The optional structs -> p.aa, p.det, p.ft and the name the call speaks under.  ctx is compared
+// The optional structs -> p.aa, p.det, p.ft, p.abs and the name the call speaks under.  ctx is compared
 // with NULL only.
 static int backward_parse(const gsr_context *ctx, const BackwardRequest &rq, BackwardPlan &p) {
     const int aa = rq.filter ? rq.filter->antialiasing : 0;
     const int det = rq.order ? rq.order->deterministic : 0;
     if (rq.feat && rq.feat->dL_dfeature_map) p.ft = rq.feat;
+    if (rq.abs) p.abs = rq.abs->dL_dmeans2D_abs;
     p.fn = aa == 0 ? rq.fn : "gsr_backward_filtered";
     if (det != 0) p.fn = "gsr_backward_ordered";
     if (rq.strips) {  // the two entries that read the settings here check their pointers first
         if (backward_null(ctx, rq))
-            return fail(GSR_E_INVALID, std::string(p.ft ? "gsr_backward_features"
-                                                        : "gsr_backward_strip") + ": NULL argument");
+            return fail(GSR_E_INVALID, std::string(p.abs  ? "gsr_backward_abs"
+                                                   : p.ft ? "gsr_backward_features"
+                                                          : "gsr_backward_strip") + ": NULL argument");
         if (rq.st->tile_row_begin != 0 || rq.st->tile_row_end != 0) p.fn = "gsr_backward_strip";
     }
     if (p.ft) {
@@ -1630,6 +1637,14 @@ static int backward_parse(const gsr_context *ctx, const BackwardRequest &rq, Bac
             return fail(GSR_E_INVALID, p.fn + ": deterministic == 1 with a feature gradient: the "
                                               "deterministic slots hold 9 or 10 sums and have no "
                                               "room for C more");
+    }
+    if (p.abs) {
+        p.fn = "gsr_backward_abs";
+        if (p.ft)
+            return fail(GSR_E_INVALID, p.fn + ": dL_dmeans2D_abs with a feature gradient: the "
+                                              "feature channels add their share of dL/dalpha in "
+                                              "passes of their own, and the absolute value of a "
+                                              "pixel's total cannot be split over passes");
     }
     if (det != 0 && det != 1)
         return fail(GSR_E_INVALID, p.fn + ": deterministic must be 0 or 1, got " +
@@ -1753,7 +1768,7 @@ static int backward_blend(gsr_context *ctx, const BackwardRequest &rq, const Bac
         if (K >= (1ull << 30))
             return fail(GSR_E_INVALID, p.fn + ": deterministic needs num_rendered < 2^30, got " +
                                            std::to_string(K));
-        const size_t sums = p.planes ? 10 : 9;
+        const size_t sums = (p.planes ? 10 : 9) + (p.abs ? 2 : 0);
         GSR_TRY(grow(ctx, ctx->det_marks, std::max<size_t>(4 * K, 1), s));
         GSR_TRY(grow(ctx, ctx->det_sums, std::max<size_t>(4 * K * sums * sizeof(float), 1), s));
         da = {ctx->strip_rect.get(), ctx->det_slab.get(), ctx->det_sums.get(),
@@ -1796,7 +1811,7 @@ static int backward_blend(gsr_context *ctx, const BackwardRequest &rq, const Bac
         // (neither: a feature gradient alone, no colour pass)
         if (p.planes || ba.dL_dcolor)
             GSR_HIP(gsr_launch_blend_bwd(ba, p.planes ? &pa : nullptr, p.det ? &da : nullptr, sp,
-                                         s),
+                                         s, p.abs != nullptr),
                     "blend backward launch");
         // gsr_backward_features: beside the pass above, into the same zeroed rows
         if (ft)
@@ -1805,7 +1820,8 @@ static int backward_blend(gsr_context *ctx, const BackwardRequest &rq, const Bac
                     "feature blend backward launch");
     }
     if (p.det)  // every word of every row, zeros where nothing was stored
-        GSR_HIP(gsr_launch_grad_rows_gather(da, P, p.planes, ctx->grad2d.get(), s),
+        GSR_HIP(gsr_launch_grad_rows_gather(da, P, p.planes, ctx->grad2d.get(), s,
+                                            p.abs != nullptr),
                 "gradient rows gather launch");
     GSR_TRY(backward_mark(ctx, p, 2));
     return backward_stage_check(rq, p, "stage blend backward");
@@ -1870,6 +1886,9 @@ static int backward_gaussians(gsr_context *ctx, const BackwardRequest &rq, const
     // gsr_backward_filtered: the antialiased twins, which also read the opacities
     extras.aa_opacities = p.aa ? g->opacities : nullptr;
     GSR_HIP(gsr_launch_preprocess_bwd(pb, extras, s), "per-Gaussian backward launch");
+    if (p.abs)  // gsr_backward_abs: the rows' words 10, 11, behind the gate like the kernel above
+        GSR_HIP(gsr_launch_means2d_abs(pb.radii, pb.grad2d, P, pb.W, pb.H, p.abs, s),
+                "absolute means2D gradient launch");
     if (!p.planes && dL_ddepths)  // no plane gradient: nothing reaches the features
         GSR_HIP(hipMemsetAsync(dL_ddepths, 0, (size_t)P * sizeof(float), s),
                 "hipMemsetAsync(dL_ddepths)");
@@ -1955,6 +1974,15 @@ int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_ra
                           gsr_gradients *gr, void *stream) {
     return backward_entry(ctx, stream, {"gsr_backward_camera", g, st, in, gr, planes, camera,
                                         filter, order, feat, true});
+}
+
+int gsr_backward_abs(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *st,
+                     const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                     const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                     const gsr_backward_order *order, const gsr_feature_gradients *feat,
+                     const gsr_abs_gradients *abs, gsr_gradients *gr, void *stream) {
+    return backward_entry(ctx, stream, {"gsr_backward_camera", g, st, in, gr, planes, camera,
+                                        filter, order, feat, true, abs});
 }
 
 int gsr_backward_times(gsr_context *ctx, float *ms, int n) {

@@ -51,6 +51,12 @@
 //    chunk of channels over the same lists; it adds its share of the six geometry sums to the same
 //    rows and the channels' sums straight to dL_dfeatures.  The kernels above compile as before
 //    (profiles/features_resources.txt).
+//  * k_blend_bwd_abs_q, ..._planes_abs_q, ... (eight), k_means2d_abs -- the absolute gradient of the
+//    2D mean (gsr_backward_abs): the blend's body with kAbs set keeps two more sums
+//    per (splat, quadrant), |v0| and |v1| taken per pixel before any cross-lane sum, through the
+//    same row_sum, flush and atomics (or slots) into words 10 and 11 of the Gaussian's row; the
+//    elementwise kernel scales them to dL_dmeans2D_abs.  The kernels above compile as before
+//    (profiles/backward_absgrad_resources.txt).
 #include "gsr_internal.h"
 
 #include <algorithm>
@@ -101,13 +107,20 @@ struct BwdSplatT<true> {
 // kStrip (gsr_backward_strip): the grid is the strip's tiles; r gives the strip's
 // first tile row (the pixels' coordinates stay the frame's) and the offset and height of the
 // strip-local image and plane gradients; without it r is not read.
-template <bool kPlanes, bool kDet = false, bool kStrip = false>
+// kAbs (gsr_backward_abs): two more sums per (splat, quadrant), the pixels' |v0| and
+// |v1|, for words 10 and 11 of the Gaussian's row (with and without the planes; in a slot they
+// follow the kBase words directly).
+template <bool kPlanes, bool kDet = false, bool kStrip = false, bool kAbs = false>
 __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs &p,
                                           const GsrDetBwdArgs &d = GsrDetBwdArgs{},
                                           const GsrStripBwdArgs &r = GsrStripBwdArgs{}) {
     using BwdSplat = BwdSplatT<kPlanes>;
     // per (splat, quadrant): the words 0..8 of a gradient row, and word 9 (dL/dz) with the planes
-    constexpr int kSums = kPlanes ? 10 : 9;
+    constexpr int kBase = kPlanes ? 10 : 9;
+    // kAbs: the sums kBase and kBase + 1 are sum |v0| and sum |v1|, the row's words kAbsWord, + 1
+    constexpr int kSums = kBase + (kAbs ? 2 : 0);
+    constexpr int kAbsWord = 10;
+    static_assert(kAbsWord >= kBase && kAbsWord + 2 <= kGradRow, "words 10, 11 are free");
     __shared__ BwdSplat s_spl_q[4][64];
     __shared__ uint32_t s_id_q[4][64];
     __shared__ float s_red_q[4][64 * kSums];
@@ -234,7 +247,7 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
             const int k_lo = 16 * kg, k_hi = min(count, k_lo + 16);
             float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f,
                   s8 = 0.f;
-            [[maybe_unused]] float s9 = 0.f;
+            [[maybe_unused]] float s9 = 0.f, sa0 = 0.f, sa1 = 0.f;
             uint32_t touched = 0u;  // slots of the group with a contributing pixel
             for (int k = k_hi; k-- > k_lo;) {
                 const BwdSplat sp = s_spl[k];
@@ -281,6 +294,11 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
                     const float t9 = row_sum(v9);
                     s9 = mine ? t9 : s9;
                 }
+                if constexpr (kAbs) {
+                    // per pixel, before any cross-lane sum: what cancels in s0, s1 adds up here
+                    const float ta0 = row_sum(fabsf(v0)), ta1 = row_sum(fabsf(v1));
+                    sa0 = mine ? ta0 : sa0, sa1 = mine ? ta1 : sa1;
+                }
             }
             if (touched == 0u) continue;
             // slot-major in LDS, the four rows of a slot side by side; then word t of the group's
@@ -290,6 +308,7 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
             mine9[0] = s0, mine9[1] = s1, mine9[2] = s2, mine9[3] = s3, mine9[4] = s4;
             mine9[5] = s5, mine9[6] = s6, mine9[7] = s7, mine9[8] = s8;
             if constexpr (kPlanes) mine9[9] = s9;
+            if constexpr (kAbs) mine9[kBase] = sa0, mine9[kBase + 1] = sa1;
             const int n = (k_hi - k_lo) * kSums;
             for (int t = lane; t < n; t += 64) {
                 const int slot = t / kSums, word = t - slot * kSums;
@@ -304,7 +323,9 @@ __device__ __forceinline__ void blend_bwd(const GsrBlendBwdArgs &a, const GsrPla
                             if (word == 0) d.marks[to] = 1;
                         }
                     } else {
-                        atomicAdd(&a.grad2d[(size_t)s_id[k_lo + slot] * kGradRow + word], sum);
+                        // (kAbs: the last two sums go to the words 10, 11 whatever kBase is)
+                        const int to = kAbs && word >= kBase ? word - kBase + kAbsWord : word;
+                        atomicAdd(&a.grad2d[(size_t)s_id[k_lo + slot] * kGradRow + to], sum);
                     }
                 }
             }
@@ -349,6 +370,43 @@ __global__ __launch_bounds__(256) void k_blend_bwd_planes_det_strip_q(const GsrB
                                                                       const GsrDetBwdArgs d,
                                                                       const GsrStripBwdArgs r) {
     blend_bwd<true, true, true>(a, p, d, r);
+}
+// The same eight with kAbs set (gsr_backward_abs): instantiations of their own again, so the eight
+// above keep their code, registers and LDS (profiles/backward_absgrad_resources.txt).
+__global__ __launch_bounds__(256) void k_blend_bwd_abs_q(const GsrBlendBwdArgs a) {
+    blend_bwd<false, false, false, true>(a, GsrPlaneBwdArgs{});
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_abs_q(const GsrBlendBwdArgs a,
+                                                                const GsrPlaneBwdArgs p) {
+    blend_bwd<true, false, false, true>(a, p);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_det_abs_q(const GsrBlendBwdArgs a,
+                                                             const GsrDetBwdArgs d) {
+    blend_bwd<false, true, false, true>(a, GsrPlaneBwdArgs{}, d);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_det_abs_q(const GsrBlendBwdArgs a,
+                                                                    const GsrPlaneBwdArgs p,
+                                                                    const GsrDetBwdArgs d) {
+    blend_bwd<true, true, false, true>(a, p, d);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_strip_abs_q(const GsrBlendBwdArgs a,
+                                                               const GsrStripBwdArgs r) {
+    blend_bwd<false, false, true, true>(a, GsrPlaneBwdArgs{}, GsrDetBwdArgs{}, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_strip_abs_q(const GsrBlendBwdArgs a,
+                                                                      const GsrPlaneBwdArgs p,
+                                                                      const GsrStripBwdArgs r) {
+    blend_bwd<true, false, true, true>(a, p, GsrDetBwdArgs{}, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_det_strip_abs_q(const GsrBlendBwdArgs a,
+                                                                   const GsrDetBwdArgs d,
+                                                                   const GsrStripBwdArgs r) {
+    blend_bwd<false, true, true, true>(a, GsrPlaneBwdArgs{}, d, r);
+}
+__global__ __launch_bounds__(256) void k_blend_bwd_planes_det_strip_abs_q(
+    const GsrBlendBwdArgs a, const GsrPlaneBwdArgs p, const GsrDetBwdArgs d,
+    const GsrStripBwdArgs r) {
+    blend_bwd<true, true, true, true>(a, p, d, r);
 }
 
 // ---- the feature channels' blend backward (gsr_backward_features) ----------------
@@ -561,6 +619,21 @@ __global__ __launch_bounds__(256) void k_strip_gate(const uint2 *__restrict__ st
     if (i < P && strip_rect[i].x == 0u) radii[i] = 0;
 }
 
+// gsr_launch_means2d_abs: dL_dmeans2D_abs from the rows' words 10 and 11, in dL_dmeans2D's units
+// (k_preprocess_bwd's factors); exact zeros for a culled (or, after the gate, strip-less) Gaussian.
+__global__ __launch_bounds__(256) void k_means2d_abs(const int32_t *__restrict__ radii,
+                                                     const float *__restrict__ grad2d, int64_t P,
+                                                     int W, int H, float *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    float ax = 0.f, ay = 0.f;
+    if (radii[i] > 0) {
+        ax = grad2d[i * kGradRow + 10] * (0.5f * (float)W);
+        ay = grad2d[i * kGradRow + 11] * (0.5f * (float)H);
+    }
+    out[3 * i] = ax, out[3 * i + 1] = ay, out[3 * i + 2] = 0.f;
+}
+
 // ---- the deterministic mode's slab scan and gather ------------------------------
 constexpr int kSlabPer = 4;                    // Gaussians per thread
 constexpr int kSlabBlock = 256 * kSlabPer;     // ... per block
@@ -632,10 +705,11 @@ __device__ __forceinline__ double xor_d(double v) {
     return __hiloint2double(hi, lo);
 }
 
-// One row of 16 lanes per Gaussian (gsr_internal.h, gsr_launch_grad_rows_gather).
-template <int kSums>
-__global__ __launch_bounds__(256) void k_grad_rows_gather(const GsrDetBwdArgs d, int64_t P,
-                                                          float *grad2d) {
+// One row of 16 lanes per Gaussian (gsr_internal.h, gsr_launch_grad_rows_gather).  kAbs: the
+// slot's last two sums are the absolute ones, for the row's words 10 and 11.
+template <int kSums, bool kAbs>
+__device__ __forceinline__ void grad_rows_gather(const GsrDetBwdArgs &d, int64_t P,
+                                                 float *grad2d) {
     const int64_t id = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const uint32_t j = threadIdx.x & 15u;
     uint64_t first = 0, slots = 0;
@@ -663,9 +737,21 @@ __global__ __launch_bounds__(256) void k_grad_rows_gather(const GsrDetBwdArgs d,
         v += xor_d<2>(v);
         v += xor_d<4>(v);
         v += xor_d<8>(v);
-        out = j == (uint32_t)w ? (float)v : out;
+        const int to = kAbs && w >= kSums - 2 ? w - (kSums - 2) + 10 : w;
+        out = j == (uint32_t)to ? (float)v : out;
     }
     if (id < P) grad2d[id * kGradRow + j] = out;
+}
+template <int kSums>
+__global__ __launch_bounds__(256) void k_grad_rows_gather(const GsrDetBwdArgs d, int64_t P,
+                                                          float *grad2d) {
+    grad_rows_gather<kSums, false>(d, P, grad2d);
+}
+// kSums: 11, or 12 with the planes (gsr_backward_abs)
+template <int kSums>
+__global__ __launch_bounds__(256) void k_grad_rows_gather_abs(const GsrDetBwdArgs d, int64_t P,
+                                                              float *grad2d) {
+    grad_rows_gather<kSums, true>(d, P, grad2d);
 }
 
 // ---- per Gaussian ------------------------------------------------------------------------------
@@ -892,7 +978,7 @@ static bool strip_ok(const GsrBlendBwdArgs &a, const GsrStripBwdArgs *r) {
 
 hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
                                 const GsrDetBwdArgs *d, const GsrStripBwdArgs *strip,
-                                hipStream_t s) {
+                                hipStream_t s, bool abs) {
     if (p && (!p->z_bits || (!p->dL_ddepth_map && !p->dL_dinv_depth_map && !p->dL_dfinal_T)))
         return hipErrorInvalidValue;
     const bool no_gradient = !p && !a.dL_dcolor;
@@ -904,7 +990,7 @@ hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs 
     auto launch = [&](auto kernel, auto... more) {
         hipLaunchKernelGGL(kernel, dim3(a.n_tiles), dim3(256), 0, s, a, more...);
     };
-    switch ((p ? 1 : 0) | (d ? 2 : 0) | (strip ? 4 : 0)) {
+    switch ((p ? 1 : 0) | (d ? 2 : 0) | (strip ? 4 : 0) | (abs ? 8 : 0)) {
         case 0: launch(k_blend_bwd_q); break;
         case 1: launch(k_blend_bwd_planes_q, *p); break;
         case 2: launch(k_blend_bwd_det_q, *d); break;
@@ -913,6 +999,14 @@ hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs 
         case 5: launch(k_blend_bwd_planes_strip_q, *p, *strip); break;
         case 6: launch(k_blend_bwd_det_strip_q, *d, *strip); break;
         case 7: launch(k_blend_bwd_planes_det_strip_q, *p, *d, *strip); break;
+        case 8: launch(k_blend_bwd_abs_q); break;
+        case 9: launch(k_blend_bwd_planes_abs_q, *p); break;
+        case 10: launch(k_blend_bwd_det_abs_q, *d); break;
+        case 11: launch(k_blend_bwd_planes_det_abs_q, *p, *d); break;
+        case 12: launch(k_blend_bwd_strip_abs_q, *strip); break;
+        case 13: launch(k_blend_bwd_planes_strip_abs_q, *p, *strip); break;
+        case 14: launch(k_blend_bwd_det_strip_abs_q, *d, *strip); break;
+        case 15: launch(k_blend_bwd_planes_det_strip_abs_q, *p, *d, *strip); break;
     }
     return hipGetLastError();
 }
@@ -973,11 +1067,26 @@ hipError_t gsr_launch_slab_scan(const uint2 *strip_rect, int64_t P, uint64_t *pa
     return hipGetLastError();
 }
 
+hipError_t gsr_launch_means2d_abs(const int32_t *radii, const float *grad2d, int64_t P, int W,
+                                  int H, float *dL_dmeans2D_abs, hipStream_t s) {
+    if (P <= 0) return hipSuccess;
+    if (!radii || !grad2d || !dL_dmeans2D_abs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_means2d_abs, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, radii,
+                       grad2d, P, W, H, dL_dmeans2D_abs);
+    return hipGetLastError();
+}
+
 hipError_t gsr_launch_grad_rows_gather(const GsrDetBwdArgs &d, int64_t P, bool planes,
-                                       float *grad2d, hipStream_t s) {
+                                       float *grad2d, hipStream_t s, bool abs) {
     if (P <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)((P + 15) / 16);
-    if (planes)
+    if (abs && planes)
+        hipLaunchKernelGGL(k_grad_rows_gather_abs<12>, dim3(blocks), dim3(256), 0, s, d, P,
+                           grad2d);
+    else if (abs)
+        hipLaunchKernelGGL(k_grad_rows_gather_abs<11>, dim3(blocks), dim3(256), 0, s, d, P,
+                           grad2d);
+    else if (planes)
         hipLaunchKernelGGL(k_grad_rows_gather<10>, dim3(blocks), dim3(256), 0, s, d, P, grad2d);
     else
         hipLaunchKernelGGL(k_grad_rows_gather<9>, dim3(blocks), dim3(256), 0, s, d, P, grad2d);

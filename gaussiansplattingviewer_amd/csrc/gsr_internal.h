@@ -631,7 +631,9 @@ uint32_t gsr_blend_order_groups(uint32_t n_tiles);
 // The per-Gaussian 2D gradients the blend's backward sums and the per-Gaussian backward reads: one
 // 64-B row per Gaussian, {d/dmean2D x, y (pixels), d/dconic a, b, c, d/dopacity, d/drgb r, g, b,
 // 7 pad}, so one splat's nine sums are one contiguous segment of one 64-B atomic request.  With the
-// planes (gsr_backward_planes) word 9 is d/dz through the features z and 1 / z, 6 pad.
+// planes (gsr_backward_planes) word 9 is d/dz through the features z and 1 / z, 6 pad.  With the
+// absolute gradient (gsr_backward_abs) words 10 and 11 are the sums over pixels of |the pixel's
+// addend to word 0| and |... to word 1|, with and without the planes; 4 pad.
 constexpr int kGradRow = 16;
 struct GsrBlendBwdArgs {
     const uint2 *ranges;  // whole-frame tile ranges
@@ -681,7 +683,8 @@ hipError_t gsr_launch_blend_bwd_features(const GsrBlendBwdArgs &a, const float *
 //   pair = slab[id] + (ty - row0) * w + (tx - x0),   slot = pair * 4 + quad,
 // with {x0 | w << 16, row0 | rows << 16} = strip_rect[id] of the whole frame and slab the exclusive
 // scan of w * rows in id order (its total is K, the list's length).  The wave stores its kSums
-// words (9, or 10 with the planes) to sums[slot * kSums ...] and sets marks[slot] = 1; marks
+// words (9, or 10 with the planes; two more with the absolute sums of gsr_backward_abs, which come
+// last) to sums[slot * kSums ...] and sets marks[slot] = 1; marks
 // ([4 K] bytes) is zeroed by the caller, sums ([4 K * kSums] floats) needs no zeroing: a slot
 // without its mark is never read.  A staged splat whose tile lies outside its rect, or whose pair
 // is not below K, is not stored (it cannot happen with the rebuild's lists).  K < 2^30.
@@ -698,9 +701,12 @@ struct GsrDetBwdArgs {
 // with a NULL buffer or K >= 2^30, or a strip that does not describe rows of the frame.  An empty
 // grid (a.n_tiles == 0) launches nothing and is hipSuccess, whatever the strip; without d it also
 // comes before the missing a.dL_dcolor.
+// abs (gsr_backward_abs): the eight k_blend_bwd*_abs_q instantiations, which also sum
+// the pixels' |v0| and |v1| into words 10 and 11 of the row; a slot of d then holds kSums + 2 words
+// (11, or 12 with the planes), the two absolute sums last.
 hipError_t gsr_launch_blend_bwd(const GsrBlendBwdArgs &a, const GsrPlaneBwdArgs *p,
                                 const GsrDetBwdArgs *d, const GsrStripBwdArgs *strip,
-                                hipStream_t s);
+                                hipStream_t s, bool abs = false);
 // slab[i] = sum over j < i of w_j * rows_j (strip_rect, 0 for a Gaussian without a rect), 64-bit;
 // partials: workspace of gsr_slab_blocks(P) uint64.  P == 0 launches nothing.
 int64_t gsr_slab_blocks(int64_t P);
@@ -711,9 +717,15 @@ hipError_t gsr_launch_slab_scan(const uint2 *strip_rect, int64_t P, uint64_t *pa
 // order (tile row-major within the rect, then quadrant), each sum from +0.0 in double; the 16 lanes
 // are combined by the fixed tree (xor 1, 2, 4, 8) and rounded once.  Words kSums..15 and the rows
 // of Gaussians without a rect or a mark are zeros: no memset of grad2d.  The order is a function
-// of the rect and the marks alone.
+// of the rect and the marks alone.  abs: slots of kSums + 2 words, whose last two go to the words
+// 10 and 11 by the same sums in the same order.
 hipError_t gsr_launch_grad_rows_gather(const GsrDetBwdArgs &d, int64_t P, bool planes,
-                                       float *grad2d, hipStream_t s);
+                                       float *grad2d, hipStream_t s, bool abs = false);
+// gsr_backward_abs's output (k_means2d_abs), after the gate on a strip: dL_dmeans2D_abs[i] =
+// (0.5 W row[10], 0.5 H row[11], 0) where radii[i] > 0, else (0, 0, 0).  [P, 3], any 4-byte
+// alignment.  P == 0 launches nothing.
+hipError_t gsr_launch_means2d_abs(const int32_t *radii, const float *grad2d, int64_t P, int W,
+                                  int H, float *dL_dmeans2D_abs, hipStream_t s);
 // gsr_backward_strip's gate (k_strip_gate): radii[i] = 0 for every Gaussian without a tile in the
 // strip (strip_rect[i].x == 0), in place, so that each of the eight k_preprocess_bwd* kernels
 // leaves it where it leaves a culled Gaussian: before any arithmetic, +0.0 in every gradient, zeros

@@ -381,7 +381,8 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
                          int64_t tile_row_begin = 0, int64_t tile_row_end = 0,
                          int64_t image_height = 0, const torch::Tensor *features = nullptr,
                          const torch::Tensor *dL_dfeature_map = nullptr,
-                         torch::Tensor *dL_dfeatures = nullptr) {
+                         torch::Tensor *dL_dfeatures = nullptr,
+                         torch::Tensor *dL_dmeans2D_abs = nullptr) {
     Scene sc(in);
     const bool strip = tile_row_begin != 0 || tile_row_end != 0;
     const bool has_color = dL_dout_color.defined() && dL_dout_color.numel() != 0;
@@ -431,6 +432,7 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
         d_campos = torch::zeros({3}, f32);
     }
     if (features) *dL_dfeatures = torch::zeros({P, rows_f.size(1)}, f32);
+    if (dL_dmeans2D_abs) *dL_dmeans2D_abs = torch::zeros({P, 3}, f32);
     if (P != 0) {
         sc.fill(frame_H, W);
         sc.st.tile_row_begin = (int32_t)tile_row_begin;
@@ -472,7 +474,12 @@ Backward11 backward_impl(const Inputs &in, const torch::Tensor &dL_dout_color,
             pybind11::gil_scoped_release no_gil;
             if (upstream && !features)
                 rc = gsr_backward(ctx, &sc.g, &sc.st, &bi, &gr, s);
-            else  // with NULLs and a 0 every entry below it; refuses deterministic with features
+            else if (dL_dmeans2D_abs) {  // gsr_backward_abs: the entry below and one more output
+                const gsr_abs_gradients ag{dL_dmeans2D_abs->data_ptr<float>()};
+                rc = gsr_backward_abs(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
+                                      camera ? &cg : nullptr, antialiasing ? &fs : nullptr, &order,
+                                      features ? &fg : nullptr, &ag, &gr, s);
+            } else  // with NULLs and a 0 every entry below it; refuses deterministic with features
                 rc = gsr_backward_features(ctx, &sc.g, &sc.st, &bi, any ? &pg : nullptr,
                                            camera ? &cg : nullptr, antialiasing ? &fs : nullptr,
                                            &order, features ? &fg : nullptr, &gr, s);
@@ -562,6 +569,29 @@ Backward12 rasterize_gaussians_backward_features(
                                  tile_row_begin, tile_row_end, image_height, &features,
                                  &dL_dfeature_map, &dL_dfeatures);
     return std::tuple_cat(g, std::make_tuple(dL_dfeatures));
+}
+
+// The strip-capable general backward with the absolute gradient of the 2D means
+// (gsr_backward_abs): its arguments, tile rows (0, 0) for a whole frame; its tuple with
+// dL_dmeans2D_abs [P, 3] appended.
+Backward12 rasterize_gaussians_backward_abs(
+    const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+    const torch::Tensor &opacities, const torch::Tensor &scales, const torch::Tensor &rotations,
+    double scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+    const torch::Tensor &projmatrix, double tan_fovx, double tan_fovy, const torch::Tensor &sh,
+    int64_t degree, const torch::Tensor &campos, bool debug, const torch::Tensor &dL_dout_color,
+    const torch::Tensor &dL_ddepth_map, const torch::Tensor &dL_dinv_depth_map,
+    const torch::Tensor &dL_dfinal_T, bool camera, bool antialiasing, bool deterministic,
+    int64_t tile_row_begin, int64_t tile_row_end, int64_t image_height) {
+    const torch::Tensor planes[3] = {dL_ddepth_map, dL_dinv_depth_map, dL_dfinal_T};
+    torch::Tensor dL_dmeans2D_abs;
+    Backward11 g = backward_impl({background, means3D, colors, opacities, scales, rotations,
+                                  scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                                  tan_fovy, sh, degree, campos, false, debug},
+                                 dL_dout_color, planes, camera, antialiasing, false, deterministic,
+                                 tile_row_begin, tile_row_end, image_height, nullptr, nullptr,
+                                 nullptr, &dL_dmeans2D_abs);
+    return std::tuple_cat(g, std::make_tuple(dL_dmeans2D_abs));
 }
 
 torch::Tensor mark_visible(const torch::Tensor &means3D, const torch::Tensor &viewmatrix,
@@ -1058,6 +1088,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "rasterize_gaussians_backward_ext's 23 arguments, then tile_row_begin, tile_row_end, "
           "image_height, features (P, C), dL_dfeature_map (C, rows, W): gsr_backward_features -> "
           "the 11-tuple, then dL_dfeatures (P, C)");
+    m.def("rasterize_gaussians_backward_abs", &rasterize_gaussians_backward_abs,
+          "rasterize_gaussians_backward_strip_ext's 26 arguments, tile rows (0, 0) for a whole "
+          "frame: gsr_backward_abs -> the 11-tuple, then dL_dmeans2D_abs (P, 3), the sums over "
+          "pixels of the absolute values of the pixels' terms of dL_dmeans2D");
     m.def("mark_visible", &mark_visible, "upstream markVisible: bool[P]");
     m.def("fused_image_loss", &fused_image_loss,
           "image, target (contiguous float32 (C, H, W)), lambda_dssim, need_saved: gsr_image_loss "

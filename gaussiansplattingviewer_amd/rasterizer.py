@@ -25,6 +25,9 @@ makes every backward bit-reproducible (`gsr_backward_ordered`).
 16-px tile rows (`gsr_backward_strip`): the image-like outputs are strip-local, the gradients
 whole-scene, and over a partition of the rows they add up to the whole frame's
 (`strips.reduce_gradients` sums them over the ranks).
+`GaussianRasterizer(...)(..., means2D_abs=leaf)` also leaves the absolute gradient of the 2D means
+in `leaf.grad` (`_RasterizeGaussiansAbs`, `gsr_backward_abs`): means2D's gradient with every
+pixel's term taken by its absolute value, the number AbsGS-style densification thresholds.
 """
 from __future__ import annotations
 
@@ -371,7 +374,8 @@ _BACKWARD_ENTRIES = (
     ("gsr_backward_filtered", lambda lib: _lib.filtered_fns(lib)[1], 3, False),
     ("gsr_backward_ordered", _lib.backward_ordered_fn, 4, False),
     ("gsr_backward_strip", _lib.backward_strip_fn, 4, True),
-    ("gsr_backward_features", lambda lib: _lib.features_fns(lib)[1], 5, True))
+    ("gsr_backward_features", lambda lib: _lib.features_fns(lib)[1], 5, True),
+    ("gsr_backward_abs", _lib.backward_abs_fn, 6, True))
 
 
 def _lowest_entry(entries, lib, structs, strip=False):
@@ -390,7 +394,7 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
                                         dL_dfinal_T=None, depths=False, camera=False,
                                         antialiasing=False, deterministic=False,
                                         tile_rows=None, image_height=None, features=None,
-                                        dL_dfeature_map=None) -> dict:
+                                        dL_dfeature_map=None, absgrad=False) -> dict:
     """`gsr_backward` over ctypes (the GSR_LIB A/B path and the tests): the forward's inputs in
     `rasterize_gaussians_native`'s order with dL_dout_color (3, H, W) in place of the image size.
     Returns a dict of the gradients by their gsr_gradients names: dL_dmeans3D, dL_dmeans2D (P, 3:
@@ -422,7 +426,11 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
     features (P, C) with dL_dfeature_map (C, rows, W): the call is `gsr_backward_features` -- the
     feature planes' gradient joins the others (dL_dout_color may then be None) and the result also
     holds dL_dfeatures (P, C), exact zeros for culled Gaussians.  With deterministic=True the
-    library refuses the call (RuntimeError): the deterministic slots have no room for C more sums."""
+    library refuses the call (RuntimeError): the deterministic slots have no room for C more sums.
+
+    absgrad=True: the call is `gsr_backward_abs` and the result also holds dL_dmeans2D_abs (P, 3),
+    dL_dmeans2D's sums over pixels with each pixel's term taken by its absolute value (AbsGS; exact
+    zeros for culled Gaussians).  With a feature gradient the library refuses the call."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if (features is None) != (dL_dfeature_map is None):
@@ -495,6 +503,8 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         cam = {"dL_dviewmatrix": torch.zeros((4, 4), **f32),
                "dL_dprojmatrix": torch.zeros((4, 4), **f32), "dL_dcampos": torch.zeros((3,), **f32)}
     head = (ctx, ctypes.byref(g), ctypes.byref(st), ctypes.byref(inp))
+    if absgrad:
+        d_abs = grads["dL_dmeans2D_abs"] = torch.zeros((P, 3), **f32)
     if features is not None:
         d_feat = grads["dL_dfeatures"] = torch.zeros((P, features.size(1)), **f32)
         d_map = _as_dev(dL_dfeature_map, device, "C,H,W")
@@ -508,7 +518,8 @@ def rasterize_gaussians_backward_native(bg, means3D, colors_precomp, opacities, 
         deterministic and _lib.GsrBackwardOrder(deterministic=int(deterministic)),
         features is not None and _lib.GsrFeatureGradients(
             C=int(features.size(1)), features=_lib.ptr(features),
-            dL_dfeature_map=_lib.ptr(d_map), dL_dfeatures=_lib.ptr(d_feat)))
+            dL_dfeature_map=_lib.ptr(d_map), dL_dfeatures=_lib.ptr(d_feat)),
+        absgrad and _lib.GsrAbsGradients(dL_dmeans2D_abs=_lib.ptr(d_abs)))
     with torch.cuda.device(dev_index):
         name, fn, n = _lowest_entry(_BACKWARD_ENTRIES, lib, structs, strip=bool(re))
         _lib.check(fn(*head, *structs[:n], ctypes.byref(out), ctypes.c_void_p(stream)), name)
@@ -640,7 +651,8 @@ def _refuse_deterministic_features(rs):
                       "atomics in this backward", UserWarning, stacklevel=3)
 
 
-def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=None):
+def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=None,
+              absgrad=False):
     """The gradients of one frame.  saved: `_saved`'s seven; grads: those of (color, depth_map,
     inv_depth_map, final_T), None = unused; camera: None, or the (viewmatrix, projmatrix, campos)
     to differentiate by, which the frame was rendered with.  Returns `_GRADIENT_ORDER`'s eleven,
@@ -650,7 +662,9 @@ def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=Non
     strip (rs.tile_rows) the strip's entry, whose three more are the strip's rows and the frame's
     height.  With `features` (the frame's feature rows) and grad_feature_map, its planes' gradient
     or None, a twelfth follows: dL_dfeatures, through the features' entry, which has no
-    deterministic mode (`_refuse_deterministic_features`)."""
+    deterministic mode (`_refuse_deterministic_features`).  With `absgrad` (never with features)
+    a twelfth follows instead: dL_dmeans2D_abs, through the absolute gradient's entry, on whole
+    frames and strips and in both modes."""
     means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds = saved
     det = _deterministic(rs)
     if features is not None:
@@ -669,13 +683,14 @@ def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=Non
             dL_dfinal_T=grads[3], camera=camera is not None, antialiasing=rs.antialiasing,
             deterministic=det, tile_rows=strip,
             image_height=None if strip is None else rs.image_height,
-            features=features, dL_dfeature_map=grad_feature_map)
+            features=features, dL_dfeature_map=grad_feature_map, absgrad=absgrad)
         return tuple(g.get(n) for n in _GRADIENT_ORDER) + \
-            (() if features is None else (g["dL_dfeatures"],))
+            (() if features is None else (g["dL_dfeatures"],)) + \
+            ((g["dL_dmeans2D_abs"],) if absgrad else ())
     from . import _C
     e = torch.empty(0)
     if (camera is None and not rs.antialiasing and not det and strip is None and
-            features is None and all(t is None for t in grads[1:])):
+            features is None and not absgrad and all(t is None for t in grads[1:])):
         # (radii, num_rendered and the three buffers: accepted and ignored)
         return _C.rasterize_gaussians_backward(
             rs.bg, means3D, e, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds,
@@ -687,6 +702,9 @@ def _backward(rs, saved, grads, camera=None, features=None, grad_feature_map=Non
     if features is not None:
         entry = _C.rasterize_gaussians_backward_features
         tail = (False, *(strip or (0, 0)), int(rs.image_height), features, grad_feature_map)
+    elif absgrad:
+        entry = _C.rasterize_gaussians_backward_abs
+        tail = (det, *(strip or (0, 0)), int(rs.image_height))
     elif strip:
         entry = _C.rasterize_gaussians_backward_strip_ext
         tail = (det, *strip, int(rs.image_height))
@@ -904,6 +922,75 @@ class _RasterizeGaussiansFeatures(torch.autograd.Function):
                 like(g[10], campos) if need[12] else None)
 
 
+def _check_means2D_abs(means2D_abs, means3D):
+    """`means2D_abs` as GaussianRasterizer.forward takes it; ValueError otherwise."""
+    P = int(means3D.size(0))
+    t = means2D_abs
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != (P, 3):
+        raise ValueError(f"means2D_abs must be a tensor of shape (num_points, 3) = ({P}, 3)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"means2D_abs must be float32, got {t.dtype}")
+    if t.device != means3D.device:
+        raise ValueError(f"means2D_abs must be on the scene's device {means3D.device}, got "
+                         f"{t.device}")
+    if not t.requires_grad:
+        raise ValueError("means2D_abs must require a gradient: its .grad is the output")
+
+
+class _RasterizeGaussiansAbs(torch.autograd.Function):
+    """The first three Functions in one, with `means2D_abs`, a second (P, 3) leaf beside means2D
+    whose value is never read: returns the outputs of the call without it -- (color, radii), with
+    depth_maps (color, radii, depth_map, inv_depth_map, final_T) -- with those bits, and backward
+    returns dL_dmeans2D_abs (`gsr_backward_abs`, include/gsr.h) as means2D_abs's gradient beside
+    every gradient of the call without it.  viewmatrix, projmatrix and campos travel as tensor
+    arguments and get their gradients when they require them.  An unused output's gradient travels
+    as NULL; a shading raises in backward."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                cov3Ds_precomp, raster_settings, means2D_abs, viewmatrix, projmatrix, campos):
+        rs = raster_settings
+        ctx.has_means2D = isinstance(means2D, torch.Tensor)
+        ctx.raster_settings = rs
+        ctx.set_materialize_grads(False)
+        args = _pack(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
+                     cov3Ds_precomp)
+        ctx.save_for_backward(*_saved(args), *(
+            t if isinstance(t, torch.Tensor) else None for t in (viewmatrix, projmatrix, campos)))
+        # (inside a Function's forward no graph is recorded: the inner Function saves nothing)
+        inner = _RasterizeGaussiansPlanes if rs.depth_maps else _RasterizeGaussians
+        out = inner.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                          cov3Ds_precomp, rs)
+        ctx.mark_non_differentiable(out[1])
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth=None, grad_inv_depth=None,
+                 grad_final_T=None):
+        """Gradients in input order: the nine of `_input_grads`, means2D_abs's, then
+        viewmatrix's, projmatrix's and campos's."""
+        del grad_radii
+        rs = ctx.raster_settings
+        if rs.shading:
+            raise RuntimeError("gaussiansplattingviewer_amd differentiates the splat composite "
+                               f"only: no backward under shading {rs.shading}")
+        *saved, viewmatrix, projmatrix, campos = ctx.saved_tensors
+        grads = _contiguous((grad_color, grad_depth, grad_inv_depth, grad_final_T))
+        if all(t is None for t in grads):  # nothing reaches the outputs
+            return (None,) * 13
+        need = ctx.needs_input_grad
+        with_camera = any(need[10:13])
+        if viewmatrix is None or projmatrix is None or campos is None:
+            viewmatrix, projmatrix, campos = rs.viewmatrix, rs.projmatrix, rs.campos
+        g = _backward(rs, saved, grads, (viewmatrix, projmatrix, campos) if with_camera else None,
+                      absgrad=True)
+        like = lambda d, t: d.reshape(t.shape).to(device=t.device, dtype=t.dtype)  # noqa: E731
+        return (*_input_grads(ctx.has_means2D, saved, g), g[11] if need[9] else None,
+                like(g[8], viewmatrix) if need[10] else None,
+                like(g[9], projmatrix) if need[11] else None,
+                like(g[10], campos) if need[12] else None)
+
+
 class GaussianRasterizer(torch.nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -918,13 +1005,25 @@ class GaussianRasterizer(torch.nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                rotations=None, cov3D_precomp=None, features=None):
+                rotations=None, cov3D_precomp=None, means2D_abs=None, features=None):
         """upstream's forward; features (not upstream's; (P, C) float32, 1 <= C <= 256): the call
         returns its usual outputs followed by feature_map (C, rows, W), the channels composited
         under the colour's weights without a background term (gsr_forward_features in
         include/gsr.h), differentiable with respect to features and everything the colour
         reaches.  Composes with depth_maps, camera gradients, antialiasing and tile_rows; not
-        with a shading, nor with the deterministic backward (RuntimeError at backward)."""
+        with a shading, nor with the deterministic backward (RuntimeError at backward).
+
+        means2D_abs (not upstream's; pass it by keyword: it stands before features, which stays
+        the last parameter; a (P, 3) float32 leaf on the scene's device that requires a
+        gradient, used the way means2D is: its value is never read): after backward() its .grad
+        is dL_dmeans2D_abs, means2D's gradient with every pixel's term taken by its absolute
+        value before the sum over pixels (AbsGS; gsr_backward_abs in include/gsr.h), the number
+        to feed `optim.densification_stats` in place of means2D.grad.  It accumulates over
+        backward() calls like any .grad.  The outputs are those of the call without it.  Composes
+        with depth_maps, camera gradients, antialiasing, tile_rows and deterministic; ValueError
+        for a tensor of another shape, dtype or device or one that requires no gradient;
+        RuntimeError together with features (the absolute value of a pixel's total cannot be
+        split over the feature channels' passes), and at backward with a shading."""
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -932,6 +1031,16 @@ class GaussianRasterizer(torch.nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or '
                             'precomputed 3D covariance!')
+        if means2D_abs is not None:
+            if features is not None:
+                raise RuntimeError(
+                    "means2D_abs with features: the feature channels add their share of "
+                    "dL/dalpha in passes of their own, and the absolute value of a pixel's total "
+                    "cannot be split over passes")
+            _check_means2D_abs(means2D_abs, means3D)
+            return _RasterizeGaussiansAbs.apply(means3D, means2D, shs, colors_precomp, opacities,
+                                                scales, rotations, cov3D_precomp, rs, means2D_abs,
+                                                rs.viewmatrix, rs.projmatrix, rs.campos)
         if features is not None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales,
                                        rotations, cov3D_precomp, rs, features=features)

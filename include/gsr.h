@@ -566,6 +566,44 @@ int gsr_backward_features(gsr_context *ctx, const gsr_gaussians *g, const gsr_ra
                           const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
                           const gsr_backward_order *order, const gsr_feature_gradients *feat,
                           gsr_gradients *grads, void *stream);
+/* gsr_backward_features that also returns the absolute gradient of the 2D means (AbsGS'
+ * "homodirectional" gradient, gsplat's absgrad), for densification: dL_dmeans2D is a signed sum
+ * over the pixels a Gaussian covers, and over a blurry region the pixels' terms point in opposite
+ * directions and cancel; this output adds their magnitudes.  (Additive to ABI 4; no existing
+ * struct, entry point or kernel changes.)
+ * With v0_i(p), v1_i(p) pixel p's addends to the x and y word of Gaussian i's 2D gradient row in
+ * the blend's backward -- dL/dalpha_i(p) = T_i (gc_i - r_i) times d alpha_i / d mean2D_i, in
+ * pixels, where the per-splat term gc_i = g . c_i + gd z_i + gi / z_i holds every image-like
+ * gradient of the call (colour and planes), so "per pixel" is the pixel's total over all channels,
+ * not per channel; the gates and the 0.99 cap are gsr_backward's, and a capped or
+ * non-contributing (pixel, splat) pair adds 0:
+ *   dL_dmeans2D_abs[i] = (0.5 W sum_p |v0_i(p)|, 0.5 H sum_p |v1_i(p)|, 0)      [P, 3] float32
+ * in dL_dmeans2D's shape and units (its factors 0.5 W, 0.5 H), so that dL_dmeans2D[i] is the same
+ * sums without the bars.  The absolute value is taken per pixel, in float32, before any sum across
+ * pixels; the sums then go the way of the row's other words (float atomics, or with
+ * deterministic == 1 the slots and the gather in double: the same bits on every call).  Exact 0.0
+ * in all three words for a Gaussian the forward culls, on a strip for a Gaussian without a tile in
+ * the strip, and for a Gaussian no pixel composites.  The call zeroes, then fills, as for every
+ * other gradient; over a partition of the tile rows into strips the strips' outputs add up to the
+ * frame's.  Every other gradient of the call is what it is without the option: the same bits with
+ * deterministic == 1, the same up to the order of the atomics without.
+ * With deterministic == 1 a slot holds two more sums: 176 B per list entry (192 B with plane
+ * gradients) where gsr_backward_ordered has 144 B (160 B); at K = 9,594,635 that is 1.69 GB
+ * (1.84 GB).  The marks and the K < 2^30 rule are unchanged.  Timed inside ms[1] (the sums) and
+ * ms[2] (the scaling) of gsr_backward_times.
+ * A NULL abs, or one with dL_dmeans2D_abs NULL, is gsr_backward_features itself: the same kernels,
+ * the same arguments.  Refused with GSR_E_INVALID and nothing written: dL_dmeans2D_abs together
+ * with a feature gradient (the feature channels add their share of dL/dalpha in passes of their
+ * own, and the absolute value of a pixel's total cannot be split over passes).  P == 0 writes
+ * nothing. */
+typedef struct {
+    float *dL_dmeans2D_abs; /* [P, 3] or NULL */
+} gsr_abs_gradients;
+int gsr_backward_abs(gsr_context *ctx, const gsr_gaussians *g, const gsr_raster_settings *s,
+                     const gsr_backward_inputs *in, const gsr_plane_gradients *planes,
+                     const gsr_camera_gradients *camera, const gsr_filter_settings *filter,
+                     const gsr_backward_order *order, const gsr_feature_gradients *feat,
+                     const gsr_abs_gradients *abs, gsr_gradients *grads, void *stream);
 /* The stage times (ms, HIP events on the backward's stream) of the last gsr_backward run while
  * gsr_set_timing was not 0: ms[0] the rebuild (per-Gaussian stage, depth sort, lists), ms[1] the
  * blend's backward (with the zeroing of its sums), ms[2] the per-Gaussian backward.  Waits for

@@ -42,11 +42,17 @@ the k_blend_bwd_features_q launches inside blend_bwd_ms); with --planes, --camer
 and --strip, not with --deterministic.  The atomic figures are not reported (--contributions counts
 the colour pass's).  tools/bench_features.py compares the pair with what a caller had to do before.
 
+--absgrad: the backward is gsr_backward_abs, which also returns dL_dmeans2D_abs (the
+k_blend_bwd*_abs_q instantiations: two more sums per (splat, quadrant), 8 B more per contribution,
+inside blend_bwd_ms; k_means2d_abs inside preprocess_bwd_ms); with --planes, --camera,
+--antialiasing, --deterministic and --strip, not with --features (the library refuses the pair).
+With --deterministic the slots hold two more words (det_workspace_MB).
+
 Each GPU step runs in a child process under its own time limit (--limit seconds).
 
 Usage: python tools/bench_backward.py [--config c3] [--steps 50] [--warmup 10] [--planes]
                                       [--camera] [--antialiasing] [--deterministic]
-                                      [--strip r/N] [--features C]
+                                      [--strip r/N] [--features C] [--absgrad]
 """
 import argparse
 import ctypes
@@ -110,11 +116,13 @@ def worker(a):
                                                    tx, ty, dL, scene.sh, scene.deg, campos,
                                                    camera=bool(a.camera),
                                                    deterministic=bool(a.deterministic),
+                                                   absgrad=bool(a.absgrad),
                                                    **plane_grads, **aa, **bwd_strip)
 
     out = {"config": a.config, "steps": a.steps, "planes": bool(a.planes),
            "camera": bool(a.camera), "antialiasing": bool(a.antialiasing),
-           "deterministic": bool(a.deterministic), "features": a.features}
+           "deterministic": bool(a.deterministic), "features": a.features,
+           "absgrad": bool(a.absgrad)}
     if a.strip:
         out.update(strip=a.strip, tile_rows=list(fwd_strip["tile_rows"]), rows=n_rows)
     if a.step == "forward":
@@ -131,9 +139,9 @@ def worker(a):
         out.update(forward_ms=round(statistics.fmean(ms), 5),
                    forward_ms_min_max=[round(min(ms), 5), round(max(ms), 5)],
                    num_rendered=res.num_rendered)
-        if a.deterministic:  # 4 slots of 9 (10) floats and 4 marks per list entry
-            out.update(det_workspace_MB=round(
-                res.num_rendered * (4 * 4 * (10 if a.planes else 9) + 4) / 1e6, 2))
+        if a.deterministic:  # 4 slots of 9 (10; --absgrad: 2 more) floats, 4 marks per list entry
+            sums = (10 if a.planes else 9) + (2 if a.absgrad else 0)
+            out.update(det_workspace_MB=round(res.num_rendered * (4 * 4 * sums + 4) / 1e6, 2))
         # the per-Gaussian stage of the forward: the library's own stage events, the mean over
         # these frames
         _lib.check(lib.gsr_set_timing(ctx, 1), "gsr_set_timing")
@@ -183,8 +191,12 @@ def main():
                          "and gsr_backward_strip")
     ap.add_argument("--features", type=int, default=0, metavar="C",
                     help="C feature channels per Gaussian beside the colour, forward and backward")
+    ap.add_argument("--absgrad", action="store_true",
+                    help="gsr_backward_abs: also dL_dmeans2D_abs, the absolute means2D gradient")
     ap.add_argument("--step", default=None, choices=["forward", "backward"], help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.absgrad and a.features:
+        sys.exit("bench_backward: --absgrad and --features exclude each other (gsr_backward_abs)")
     if a.step:
         return worker(a)
     out = {}
@@ -196,7 +208,8 @@ def main():
                            (["--antialiasing"] if a.antialiasing else []) +
                            (["--deterministic"] if a.deterministic else []) +
                            (["--strip", a.strip] if a.strip else []) +
-                           (["--features", str(a.features)] if a.features else []),
+                           (["--features", str(a.features)] if a.features else []) +
+                           (["--absgrad"] if a.absgrad else []),
                            capture_output=True, text=True, timeout=a.limit)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
@@ -205,7 +218,8 @@ def main():
     if a.deterministic or a.strip or a.features:  # no colour-pass atomic traffic to report
         print(json.dumps(out))
         return
-    atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0))
+    atomic_bytes = a.contributions * (BYTES_PER_CONTRIBUTION + (4 if a.planes else 0) +
+                                      (8 if a.absgrad else 0))
     out["atomic_MB_per_frame_upper"] = round(atomic_bytes / 1e6, 1)
     out["atomic_GBs_if_all_added"] = round(atomic_bytes / (out["blend_bwd_ms"] * 1e-3) / 1e9, 1)
     out["atomic_rate_share"] = round(out["atomic_GBs_if_all_added"] / ATOMIC_RATE_GBS, 3)
